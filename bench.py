@@ -10,8 +10,8 @@ bitmap (10 % null), boolean mask with 10 % selectivity, FilterOptions::DROP:
          + compute.take(values, indices, boundscheck=False)   # the Table/RecordBatch filter path
 `value` = input rows per second through one whole step (Mrows/s), all N ranks together.
 Filter/take do not shard (north_star: "filter/take/cast stay single-GPU"): with N > 1 every rank runs an
-independent replica on its own GPU ("replicas only", weak scaling).  The sharded paths ride in the same JSON
-line: `hash_sum` (configs[3]: 4B rows / 10M keys, rows split over the N ranks, local aggregate -> ONE
+independent replica on its own GPU ("replicas only", weak scaling).  With `--full` the sharded paths ride in the
+same JSON line: `hash_sum` (configs[3]: 4B rows / 10M keys, rows split over the N ranks, local aggregate -> ONE
 all-to-all of 24-byte partials -> merge; strong scaling) and `sort_indices` (configs[4]: 2B uint64 rows,
 splitters -> ONE all-to-all of 12-byte records -> local sort).
 
@@ -29,6 +29,13 @@ libarrow.so, kind "reference"; the C oracle as kind "port" if the wheel is absen
 same data: one thread (how the kernel layer executes) and the multi-core Acero plan; `value` = the better.
 `--backend emu` (tests only) runs the same file on CPU tensors + gloo with the kernel sources under the
 SIMT emulator of tests/emu: it checks the launcher and the multi-rank plumbing, never performance.
+
+A plain run does only what `value` needs: it generates the inputs, warms up, times `--steps` steps of the route
+`value` stands for and prints the line (`metric`, `value`, `unit`, `ms_per_step`, `config`, ...).  Everything else
+named above (the mirror loop's kernel events and `roofline`, the copy ceiling, `parity_spot_check`, `cpu_baseline`,
+the other paths and the sharded legs) runs with `--full`.  `--dump-outputs DIR` writes what the timed route returned
+in its last step (filter result, row numbers, take result) as float64 .npy files (dump_outputs); the inputs depend on
+the arguments alone, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -627,6 +634,58 @@ class PluginSession:
         assert self.lib.arrow_amd_copy_to_device(c_arr, c_schema, c_dev) == 0, self.lib.arrow_amd_plugin_last_error()
         return pa.Array._import_from_c_device(ct.addressof(c_dev), arr.type)
 
+    def to_numpy(self, darr):
+        """A device-resident pyarrow array of a fixed-width type -> (values, valid or None) on the host
+        (arrow_amd_copy_to_host)."""
+        ct, pa = self.ctypes, self.pa
+        c_dev, c_schema, c_arr, c_schema2 = (ct.create_string_buffer(k) for k in (128, 72, 80, 72))
+        darr._export_to_c_device(ct.addressof(c_dev), ct.addressof(c_schema))
+        assert self.lib.arrow_amd_copy_to_host(c_dev, c_schema, c_arr, c_schema2) == 0, self.lib.arrow_amd_plugin_last_error()
+        h = pa.Array._import_from_c(ct.addressof(c_arr), ct.addressof(c_schema2))
+        vb, db = h.buffers()
+        n, off = len(h), h.offset
+        dtype = h.type.to_pandas_dtype()
+        values = np.frombuffer(db, dtype=dtype, count=off + n)[off:] if n else np.zeros(0, dtype)
+        valid = None
+        if vb is not None:
+            valid = np.unpackbits(np.frombuffer(vb, dtype=np.uint8), bitorder="little")[off:off + n].astype(bool)
+        return values, valid
+
+
+DUMP_SAMPLE_ROWS = 1 << 19    # rows per output that --dump-outputs writes (a seeded sample of a longer output)
+DUMP_SEED = 20240601
+
+
+def dump_outputs(path: str, outputs: dict) -> None:
+    """--dump-outputs: the arrays the timed path returned in its last step, as float64 .npy files that a run of another
+    build with the same arguments can be compared with, output for output.  `outputs` maps a name to (int64 values,
+    valid or None).  Per output: `<name>.npy` = its values on a fixed, seeded sample of its rows (every row when it has
+    at most DUMP_SAMPLE_ROWS), shape (rows, 2): the signed upper and the lower 32 bits, both exact in float64, 0 under
+    a null; `<name>_valid.npy` = the validity of those rows (float32 0 / 1); `<name>_rows.npy` = the row numbers.
+    `checksums.npy` covers every row: per output (in `outputs` order) [rows, valid rows, upper 32 bits, lower 32 bits
+    of the wrap-around sum of the valid values]."""
+    os.makedirs(path, exist_ok=True)
+
+    def hi_lo(v):
+        v = np.asarray(v, dtype=np.int64)
+        return np.stack([(v >> 32).astype(np.float64), (v & 0xFFFFFFFF).astype(np.float64)], axis=-1)
+
+    sums = []
+    for name, (values, valid) in outputs.items():
+        values = np.asarray(values).astype(np.int64, copy=False)
+        n = len(values)
+        ok = np.ones(n, dtype=bool) if valid is None else np.asarray(valid, dtype=bool)
+        if n <= DUMP_SAMPLE_ROWS:
+            rows = np.arange(n)
+        else:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE_ROWS))
+        np.save(os.path.join(path, f"{name}.npy"), hi_lo(np.where(ok[rows], values[rows], 0)))
+        np.save(os.path.join(path, f"{name}_valid.npy"), ok[rows].astype(np.float32))
+        np.save(os.path.join(path, f"{name}_rows.npy"), rows.astype(np.float64))
+        total = int(np.where(ok, values, 0).view(np.uint64).sum(dtype=np.uint64))
+        sums.append([n, int(ok.sum()), float(total >> 32), float(total & 0xFFFFFFFF)])
+    np.save(os.path.join(path, "checksums.npy"), np.array(sums, dtype=np.float64).reshape(-1, 4))
+
 
 _PLUGIN = [None]
 
@@ -646,13 +705,17 @@ def run_filter_take(args, rank, world, device):
     first_row = rank * n     # every replica reads its own stretch of the streams
     values, validity, mask, _ = gen_filter_inputs(n, device, first_row, args.null_p, args.selectivity)
     _sync(device)
+    if not EMU:
+        # the generator's temporaries (GBs) go back to the device before the routes allocate their outputs: the plugin's
+        # pool cannot reuse torch's cached blocks, and a route timed with them still held measured ~2 % slower
+        torch.cuda.empty_cache()
     log(f"[rank {rank}] generated {n} rows in {time.time() - t0:.1f}s")
     dv = amd.Array(amd.array.int64, n, [validity, values], -1, 0)
     dm = amd.Array(amd.array.bool_, n, [None, mask], 0, 0)
 
     # ---- the reference's CPU kernels FIRST (rank 0, N = 1): registering the plugin re-routes pyarrow's own functions
     cpu = {}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu["filter_take"] = cpu_baseline_filter_take(values, validity, mask, n, args.cpu_sample_rows, args.cpu_budget_s)
         if args.extras and not EMU:
             for name, fn in (("hash_sum", lambda: cpu_baseline_hash_sum(min(args.hash_sum_rows, args.cpu_groupby_rows), args.groups, args.cpu_budget_s)),
@@ -671,27 +734,34 @@ def run_filter_take(args, rank, world, device):
         tk = amd.compute.take(dv, idx, boundscheck=False)
         return out, idx, tk
 
-    out = idx = tk = None
-    for _ in range(args.warmup):
-        out, idx, tk = step()
-    timer = _WallTimer() if EMU else tracing.KernelTimer(device)
-    tracing.install(timer)
-    _barrier(world)
-    _sync(device)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        out, idx, tk = step()
-    _sync(device)
-    _barrier(world)
-    mirror_elapsed = time.perf_counter() - t0
-    tracing.install(None)
-    selected = out.length
-    mirror_elapsed = _max_over_ranks(mirror_elapsed, world, device)
+    def time_mirror():
+        out = idx = tk = None
+        for _ in range(args.warmup):
+            out, idx, tk = step()
+        timer = _WallTimer() if EMU else tracing.KernelTimer(device)
+        tracing.install(timer)
+        _barrier(world)
+        _sync(device)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            out, idx, tk = step()
+        _sync(device)
+        _barrier(world)
+        mirror_elapsed = time.perf_counter() - t0
+        tracing.install(None)
+        return out, idx, tk, timer, _max_over_ranks(mirror_elapsed, world, device)
+
+    # a plain run times the one route `value` stands for; --full times the mirror first (kernel events, roofline) and
+    # diffs the two routes' results
+    out = idx = tk = timer = mirror_elapsed = None
+    if args.full or EMU:
+        out, idx, tk, timer, mirror_elapsed = time_mirror()
 
     # ---- the drop-in route: the same step through UNMODIFIED pyarrow.compute on device-resident
     # arrays — Arrow's dispatch, executors and output allocation in the timed region; this is `value`.  The arrays are
     # the very HBM buffers above, wrapped without a copy.
-    elapsed, api, api_error, cf_check = mirror_elapsed, "arrow_amd.compute (Python mirror of the C ABI)", None, None
+    elapsed, api, api_error, cf_check = None, "arrow_amd.compute (Python mirror of the C ABI)", None, None
+    cf_last = None           # the drop-in route's filter, row numbers and take of its last timed step
     if not EMU:
         try:
             import pyarrow as pa
@@ -717,25 +787,32 @@ def run_filter_take(args, rank, world, device):
                 res = cf_step()
             _sync(device)
             _barrier(world)
-            elapsed = _max_over_ranks(time.perf_counter() - t0, world, device)
+            cf_elapsed = _max_over_ranks(time.perf_counter() - t0, world, device)
             calls = {f.decode(): plug.lib.arrow_amd_plugin_calls(f, 1) - g0[f] for f in g0}
             assert calls["array_filter"] >= 2 * args.steps and calls["array_take"] >= args.steps, calls
-            # the two routes agree: lengths, null counts, wrap-around sums of the valid values (device reductions)
             o, rows, t2 = res
-            cf_check = bool(len(o) == selected == len(t2) == len(rows) and
-                            pc.sum(o).as_py() == pc.sum(t2).as_py() == pc.sum(plug.wrap(pa.int64(), selected, out.data, out.validity, -1)).as_py())
+            del res
+            if out is not None:
+                # the two routes agree: lengths, null counts, wrap-around sums of the valid values (device reductions)
+                cf_check = bool(len(o) == out.length == len(t2) == len(rows) and
+                                pc.sum(o).as_py() == pc.sum(t2).as_py() == pc.sum(plug.wrap(pa.int64(), out.length, out.data, out.validity, -1)).as_py())
             api = "pyarrow.compute on device-resident arrays through libarrow_amd_plugin.so: pc.filter + pc.indices_nonzero + pc.take"
-            del res, o, rows, t2
+            elapsed, cf_last = cf_elapsed, (o, rows, t2)
+            del o, rows, t2
         except Exception as e:
             api_error = f"{type(e).__name__}: {e}"[:300]
+    if elapsed is None:
+        # the emulated backend, or the drop-in route failed: `value` is the mirror's
+        if mirror_elapsed is None:
+            out, idx, tk, timer, mirror_elapsed = time_mirror()
+        elapsed = mirror_elapsed
+    selected = out.length if out is not None else len(cf_last[0])
+    if args.dump_outputs and rank == 0:
+        got = [plug.to_numpy(a) for a in cf_last] if cf_last is not None else [a.to_numpy() for a in (out, idx, tk)]
+        dump_outputs(args.dump_outputs, dict(zip(("filter", "take_indices", "take"), got)))
+        del got
+    cf_last = None
 
-    filt_ms = timer.elapsed_ms("arx_filter_exec")
-    take_ms = timer.elapsed_ms("arx_take")
-    m2i_ms = timer.elapsed_ms("arx_mask_to_indices")
-    avg_filter_ms = float(np.mean(filt_ms))
-    alg_bytes = 8 * n + n / 8 + n / 8 + 8 * selected + selected / 8
-    achieved = alg_bytes / (avg_filter_ms * 1e-3) / 1e9
-    take_bytes = selected * 20.25
     result = {
         "metric": "filter_take_mrows_per_s",
         "value": round(world * n * args.steps / elapsed / 1e6, 2),
@@ -752,9 +829,9 @@ def run_filter_take(args, rank, world, device):
         "api": api,
         **({"api_error_fell_back_to_the_mirror": api_error} if api_error else {}),
         **({"callfunction_results_equal_the_mirrors": cf_check} if cf_check is not None else {}),
-        "python_mirror": {"what": "the same step through arrow_amd.compute (ctypes over the C ABI): filter + get_take_indices (uint32) + take",
-                          "ms_per_step": round(mirror_elapsed / args.steps * 1e3, 4),
-                          "mrows_per_s": round(world * n * args.steps / mirror_elapsed / 1e6, 2)},
+        **({"python_mirror": {"what": "the same step through arrow_amd.compute (ctypes over the C ABI): filter + get_take_indices (uint32) + take",
+                              "ms_per_step": round(mirror_elapsed / args.steps * 1e3, 4),
+                              "mrows_per_s": round(world * n * args.steps / mirror_elapsed / 1e6, 2)}} if args.full else {}),
         "config": {
             "workload": f"Filter+Take int64[{n}] + validity ({args.null_p:.0%} null), boolean mask "
                         f"{args.selectivity:.0%} true, FilterOptions::DROP; take indices = the mask's row numbers "
@@ -762,21 +839,31 @@ def run_filter_take(args, rank, world, device):
                         "no boundscheck; inputs = splitmix64 streams of SURVEY.md 8(d) (seeds 1,2,3)",
             "rows": n, "selected_rows": int(selected), "parallelism": "replicas" if world > 1 else "single-gpu",
         },
-        "roofline": {
-            "bound": "hbm", "kernel": "compact_sparse_kernel<8> (arx_filter_exec)",
-            "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 4),
-            "algorithmic_bytes_per_launch": int(alg_bytes),
-            "avg_kernel_ms": round(avg_filter_ms, 4),
-            "traffic": load_traffic("filter", n),
-            "traffic_source": "profiles/filter_traffic.json (this round's record run: profiles/r06_record_pmc_fetch_write_and_calibration.txt)",
-            "timed_in": "HIP events around the C-ABI calls of the mirror loop (the plugin launches the same entry point on its own stream)",
-        },
-        "kernel_ms": {"arx_filter_exec": round(avg_filter_ms, 4),
-                      "arx_mask_to_indices": round(float(np.mean(m2i_ms)), 4),
-                      "arx_take": round(float(np.mean(take_ms)), 4),
-                      "take_algorithmic_GBps": round(take_bytes / max(float(np.mean(take_ms)), 1e-9) / 1e6, 1)},
     }
+    if not args.full:
+        return result
+
+    filt_ms = timer.elapsed_ms("arx_filter_exec")
+    take_ms = timer.elapsed_ms("arx_take")
+    m2i_ms = timer.elapsed_ms("arx_mask_to_indices")
+    avg_filter_ms = float(np.mean(filt_ms))
+    alg_bytes = 8 * n + n / 8 + n / 8 + 8 * selected + selected / 8
+    achieved = alg_bytes / (avg_filter_ms * 1e-3) / 1e9
+    take_bytes = selected * 20.25
+    result["roofline"] = {
+        "bound": "hbm", "kernel": "compact_sparse_kernel<8> (arx_filter_exec)",
+        "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": round(achieved / HBM_PEAK_GBS, 4),
+        "algorithmic_bytes_per_launch": int(alg_bytes),
+        "avg_kernel_ms": round(avg_filter_ms, 4),
+        "traffic": load_traffic("filter", n),
+        "traffic_source": "profiles/filter_traffic.json (this round's record run: profiles/r06_record_pmc_fetch_write_and_calibration.txt)",
+        "timed_in": "HIP events around the C-ABI calls of the mirror loop (the plugin launches the same entry point on its own stream)",
+    }
+    result["kernel_ms"] = {"arx_filter_exec": round(avg_filter_ms, 4),
+                           "arx_mask_to_indices": round(float(np.mean(m2i_ms)), 4),
+                           "arx_take": round(float(np.mean(take_ms)), 4),
+                           "take_algorithmic_GBps": round(take_bytes / max(float(np.mean(take_ms)), 1e-9) / 1e6, 1)}
     if rank == 0 and not EMU:
         try:
             ceiling = copy_ceiling(amd, device)
@@ -1288,7 +1375,7 @@ def hash_sum_leg(args, rank, world, device, rows_total, steps, warmup):
                         "frac": round(per_gpu / HBM_PEAK_GBS, 4), "algorithmic_bytes_per_row": 12,
                         "traffic": load_traffic("groupby", rows // world, form="lines"),
                         "traffic_source": "profiles/groupby_traffic.json (this round's FETCH_SIZE x 2 + WRITE_SIZE passes: profiles/r06_record_sort_groupby_pmc_fetch_write.txt)"}}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not EMU:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not EMU:
         if "hash_sum" in _CPU_PRE:      # taken before the plugin was registered (run_filter_take)
             leg["cpu_baseline"] = _CPU_PRE["hash_sum"]
         else:
@@ -1344,7 +1431,7 @@ def sort_leg(args, rank, world, device, rows_total, steps, warmup):
                         "achieved": round(per_gpu, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                         "frac": round(per_gpu / HBM_PEAK_GBS, 4), "algorithmic_bytes_per_row": 16,
                         "traffic": load_traffic("sort", rows // world, form="rec8")}}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not EMU:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not EMU:
         if "sort_indices" in _CPU_PRE:
             leg["cpu_baseline"] = _CPU_PRE["sort_indices"]
         else:
@@ -1588,7 +1675,14 @@ def main():
     ap.add_argument("--option", action="append", default=[], help="name=value for arx_set_option")
     ap.add_argument("--backend", default="hip", choices=["hip", "emu"],
                     help="emu = CPU tensors + gloo + the SIMT emulator of tests/emu (plumbing tests only)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the mirror loop with its kernel events and roofline, the copy "
+                         "ceiling, the parity spot check, the CPU baselines and the other paths and sharded legs")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write the timed path's outputs of its last step to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "filter_take":
+        ap.error("--dump-outputs is implemented for --workload filter_take")
     if args.rows is None:
         args.rows = {"filter_take": 1_000_000_000, "hash_sum": 4_000_000_000, "sort_indices": 2_000_000_000}[args.workload]
     EMU = args.backend == "emu"

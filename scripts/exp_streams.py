@@ -21,7 +21,8 @@ def main():
     args = argparse.Namespace(gpus=1, steps=a.steps, warmup=3, workload="filter_take", rows=a.rows, groups=10_000_000,
                               hash_sum_rows=0, sort_rows=1 << 26, stream_rows=a.rows, callfunction_rows=a.rows,
                               extras_timeout=300.0, selectivity=0.10, null_p=0.10, cpu_sample_rows=0, cpu_groupby_rows=0,
-                              cpu_sort_rows=0, cpu_budget_s=0.0, no_cpu_baseline=True, extras=False, option=[], backend="hip")
+                              cpu_sort_rows=0, cpu_budget_s=0.0, no_cpu_baseline=True, extras=False, option=[], backend="hip",
+                              full=True, dump_outputs=None)
     device = torch.device("cuda:0")
     torch.cuda.set_device(device)
     import arrow_amd as amd

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 for opt in "$@"; do
   tag=$(echo "$opt" | tr ' =' '__')
   args=""; for kv in $opt; do [ "$kv" = "none" ] || args="$args --option $kv"; done
-  timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras $args > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err
+  timeout 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras $args > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err
   python - <<PY
 import json
 d=json.load(open("$OUT/bench_$tag.json"))

@@ -4,7 +4,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/sweep; mkdir -p $OUT
 for sel in 0.01 0.1 0.25 0.26 0.5 0.9; do
-  timeout 600 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras --selectivity $sel > $OUT/bench_$sel.json 2> $OUT/bench_$sel.err
+  timeout 600 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extras --selectivity $sel > $OUT/bench_$sel.json 2> $OUT/bench_$sel.err
   python - <<PY
 import json
 d=json.load(open("$OUT/bench_$sel.json"))

@@ -230,7 +230,7 @@ def test_bench_launcher_starts_two_ranks_end_to_end():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "emu", "--rows", "20000",
            "--steps", "1", "--warmup", "1", "--hash-sum-rows", "40000", "--groups", "700", "--sort-rows", "30000",
-           "--stream-rows", "20000", "--no-cpu-baseline"]
+           "--stream-rows", "20000", "--no-cpu-baseline", "--full"]
     # (round 6: at two ranks the sharded sort loses to one GPU and the leg DECLINES — checked first; --force-sharded-sort
     #  runs the leg for the rest of this test)
     r = subprocess.run(cmd + ["--no-extras"][:0], capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
@@ -260,7 +260,7 @@ def test_bench_single_rank_line_has_every_leg():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--backend", "emu", "--rows", "20000", "--steps", "1",
            "--warmup", "1", "--hash-sum-rows", "20000", "--groups", "300", "--sort-rows", "10000", "--stream-rows",
-           "10000", "--no-cpu-baseline"]
+           "10000", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
