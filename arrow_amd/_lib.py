@@ -245,6 +245,13 @@ SIGNATURES = {
     "arx_binary_key_chunk": (_int, [_bspan, _i64, _p, _p, _p]),
     "arx_binary_sort_chunk": (_int, [_bspan, _i64, _p, _p]),
     "arx_binary_key_hash": (_int, [_bspan, _int, _p, _p]),
+    "arx_set_lookup_state_bytes": (_sz, [_i64, _int]),
+    "arx_set_lookup_build": (_int, [_p, _span, _int, _p]),
+    "arx_set_lookup_build_binary": (_int, [_p, _bspan, _int, _int, _p]),
+    "arx_set_lookup_is_in": (_int, [_p, _i64, _int, _span, _int, _p, _p]),
+    "arx_set_lookup_index_in": (_int, [_p, _i64, _int, _span, _int, _p, _p, _p]),
+    "arx_set_lookup_is_in_binary": (_int, [_p, _bspan, _int, _int, _bspan, _int, _int, _p, _p]),
+    "arx_set_lookup_index_in_binary": (_int, [_p, _bspan, _int, _int, _bspan, _int, _int, _p, _p, _p]),
     "arx_binary_key_verify": (_int, [_bspan, _p, _p, C.POINTER(_i64), _p, _p]),
     "arx_group_first_rows": (_int, [_p, _i64, _i64, _p, _p]),
     "arx_group_edge_rows": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p]),

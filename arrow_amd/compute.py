@@ -2430,3 +2430,121 @@ def group_by_sum(keys: Array, values: Array, capacity: int | None = None,
     op = GroupBySum(cap, keys.device, options)
     op.consume(keys, values)
     return op.finalize()
+
+
+# --------------------------------------------------------------------------- set lookup
+# is_in / index_in (compute/kernels/scalar_set_lookup.cc): the value set becomes a device hash table once per call
+# (arx_set_lookup_build*), every row is looked up once (arx_set_lookup_is_in / _index_in*).  Bits of the string hash the
+# binary tables keep: 64 in production; tests lower it to force collisions, which the byte comparison resolves.
+SET_LOOKUP_HASH_BITS = 64
+
+
+def _pa_type(t: DataType):
+    """The pyarrow type of a device array's type (without touching its buffers)."""
+    import pyarrow as pa
+
+    from .array import _PA_ALIAS, _pa_temporal, is_temporal
+
+    if is_base_binary(t):
+        return pa.binary() if t.name == "binary" else pa.string()
+    if is_temporal(t):
+        return _pa_temporal(t.name)
+    return pa.type_for_alias(_PA_ALIAS[t.name])
+
+
+def _value_set_pyarrow(value_set):
+    import pyarrow as pa
+
+    if isinstance(value_set, Array):
+        return value_set.to_pyarrow()
+    if isinstance(value_set, pa.ChunkedArray):      # indexed across its chunks
+        return value_set.combine_chunks() if value_set.num_chunks else pa.array([], value_set.type)
+    if isinstance(value_set, pa.Array):
+        return value_set
+    return pa.array(list(value_set))
+
+
+def _resolve_set_lookup(values: Array, value_set, skip_nulls: bool):
+    """SetLookupState's type resolution: the value set is cast to the input's type when that cast is safe, otherwise
+    the input is compared in the value set's type (a device cast).  Pairs the reference refuses raise its own error: a
+    zero-length call of the reference settles them."""
+    import pyarrow as pa
+    import pyarrow.compute as pc
+
+    from .array import type_from_name
+
+    vt = _pa_type(values.type)
+    vs = _value_set_pyarrow(value_set)
+    pc.is_in(pa.array([], vt), value_set=vs, skip_nulls=skip_nulls)
+    if vs.type == vt:
+        return values, vs
+    try:
+        return values, vs.cast(vt, safe=True)
+    except (pa.ArrowInvalid, pa.ArrowNotImplementedError, pa.ArrowTypeError):
+        try:
+            set_type = type_from_name(str(vs.type))
+        except Exception:
+            raise ArrowNotImplementedError(f"is_in / index_in of {values.type.name} values against a {vs.type} value set on the "
+                                           "device: no device cast between them") from None
+        return cast(values, set_type), vs
+
+
+def _set_lookup(values: Array, value_set, skip_nulls: bool, index: bool):
+    if not isinstance(values, Array):
+        raise TypeError("is_in / index_in: values must be an arrow_amd.Array")
+    probe, vs = _resolve_set_lookup(values, value_set, bool(skip_nulls))
+    dev = values.device
+    lib, stream = _lib_and_stream(dev)
+    t = probe.type
+    try:
+        dset = Array.from_pyarrow(vs, device=dev)
+    except KeyError:
+        raise ArrowNotImplementedError(f"is_in / index_in of {t.name} values on the device") from None
+    m = len(vs)
+    binary = is_base_binary(t)
+    if not binary and t != bool_ and t.byte_width not in (1, 2, 4, 8, 16):
+        raise ArrowNotImplementedError(f"is_in / index_in of {t.name} values on the device")
+    kw = -1 if binary else (0 if t == bool_ else t.byte_width)
+    state = alloc(int(lib.arx_set_lookup_state_bytes(m, kw)), dev)
+    n = probe.length
+    words = alloc(max(1, (n + 63) // 64) * 8, dev)
+    out_index = alloc(max(1, n) * 4, dev) if index else None
+    idx_ptr = out_index.data_ptr() if index else None
+    skip = int(bool(skip_nulls))
+    if binary:
+        bits = SET_LOOKUP_HASH_BITS
+        sspan, vspan = dset.binary_span(), probe.binary_span()
+        check(lib.arx_set_lookup_build_binary(state.data_ptr(), C.byref(sspan), 4, bits, stream))
+        if index:
+            check(lib.arx_set_lookup_index_in_binary(state.data_ptr(), C.byref(sspan), 4, bits, C.byref(vspan), 4, skip, idx_ptr,
+                                                     words.data_ptr(), stream))
+        else:
+            check(lib.arx_set_lookup_is_in_binary(state.data_ptr(), C.byref(sspan), 4, bits, C.byref(vspan), 4, skip,
+                                                  words.data_ptr(), stream))
+    else:
+        sspan, vspan = dset.span(), probe.span()
+        check(lib.arx_set_lookup_build(state.data_ptr(), C.byref(sspan), kw, stream))
+        if index:
+            check(lib.arx_set_lookup_index_in(state.data_ptr(), m, kw, C.byref(vspan), skip, idx_ptr, words.data_ptr(), stream))
+        else:
+            check(lib.arx_set_lookup_is_in(state.data_ptr(), m, kw, C.byref(vspan), skip, words.data_ptr(), stream))
+    if not index:
+        return Array(bool_, n, [None, words], 0, 0)
+    out = Array(int32, n, [words, out_index], kUnknownNullCount, 0)
+    nbytes = (n + 7) // 8
+    out.set_lazy_null_count(
+        lambda: n - int(np.unpackbits(words[:nbytes].cpu().numpy(), bitorder="little")[:n].sum()) if n else 0)
+    return out
+
+
+def is_in(values: Array, value_set, *, skip_nulls: bool = False) -> Array:
+    """compute::IsIn (scalar_set_lookup.cc): a boolean array, true where the row's value is in `value_set` (a pyarrow
+    array or chunked array, a Python list or an arrow_amd.Array), never null.  Values compare by their bits; a null row
+    matches a null in the set unless skip_nulls.  The result stays on the device."""
+    return _set_lookup(values, value_set, skip_nulls, False)
+
+
+def index_in(values: Array, value_set, *, skip_nulls: bool = False) -> Array:
+    """compute::IndexIn (scalar_set_lookup.cc): int32, the index of the row's value's first occurrence in `value_set`
+    (chunks counted one after the other), null where the value is absent.  The result stays on the device."""
+    return _set_lookup(values, value_set, skip_nulls, True)

@@ -92,6 +92,7 @@ namespace {
 #include "plugin/hash_aggregate_more.inc"
 #include "plugin/hash_aggregate_bool.inc"
 #include "plugin/vector_hash.inc"
+#include "plugin/set_lookup.inc"
 #include "plugin/scalar_aggregate.inc"
 #include "plugin/coalesce.inc"
 #include "plugin/acero_node.inc"

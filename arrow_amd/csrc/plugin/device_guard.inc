@@ -228,7 +228,7 @@ const char* const kGuardedFunctions[] = {
     "array_filter", "array_take", "array_sort_indices", "equal", "not_equal", "greater", "greater_equal", "less", "less_equal",
     "add", "subtract", "multiply", "divide", "add_checked", "subtract_checked", "multiply_checked", "divide_checked",
     "and_kleene", "or_kleene", "invert", "unique", "value_counts", "dictionary_encode", "indices_nonzero",
-    "sum", "mean", "min_max", "min", "max", "coalesce"};
+    "sum", "mean", "min_max", "min", "max", "coalesce", "is_in", "index_in"};
 
 // before the shim registers anything: how many kernels of each guarded function are the reference's
 arrow::Result<std::vector<int>> CountStockKernels(cp::FunctionRegistry* reg) {

@@ -382,6 +382,9 @@ Status RegisterAll() {
   ARROW_RETURN_NOT_OK(RegisterValidityNP<kIsValid>(reg, "is_valid"));
   ARROW_RETURN_NOT_OK(RegisterValidityNP<kIsNull>(reg, "is_null"));
   ARROW_RETURN_NOT_OK(RegisterValidityNP<kTrueUnlessNull>(reg, "true_unless_null"));
+  // is_in / index_in against a device hash table of the value set (plugin/set_lookup.inc)
+  ARROW_RETURN_NOT_OK(RegisterSetLookup(reg, "is_in", false));
+  ARROW_RETURN_NOT_OK(RegisterSetLookup(reg, "index_in", true));
   // the reference's kernels of the functions extended above refuse device-resident arrays instead of reading them
   ARROW_RETURN_NOT_OK(InstallDeviceGuards(reg, stock_kernel_counts));
   ARROW_RETURN_NOT_OK(RefreshMinMaxKernels(reg));   // (the guards re-added kernels: pointers into min_max's list moved)

@@ -1281,6 +1281,39 @@ int arx_snappy_decompress_pages(const void* compressed, const ArxSnappyPage* pag
 int arx_gzip_decompress_pages(const void* compressed, const ArxSnappyPage* pages, int64_t num_pages, void* out,
                               uint32_t* status, void* stream);
 
+/* Set lookup — is_in / index_in (SetLookupState + the IsIn / IndexIn visitors, compute/kernels/scalar_set_lookup.cc): the
+ * value set becomes a device hash table of its distinct values, each with the index of its first occurrence, plus the
+ * index of its first null; every input row is then looked up once.  Values compare by their bits (NaN payloads and
+ * -0.0 / 0.0 stay apart, like the reference's physical-type memo tables).  key_width: 1, 2, 4, 8, 16 for fixed-width
+ * values (every integer, float and temporal type, decimal128), 0 for boolean (bit-packed) values.  A null row matches
+ * the set's null unless skip_nulls != 0.
+ * state: arx_set_lookup_state_bytes(set_length, key_width) device bytes, 16-byte aligned; a binary set takes key_width
+ * -1 here.  The probes restate the set's length (and for binary sets the set itself, whose buffers must outlive the
+ * state) instead of reading it back from the device.  0 <= set_length <= 2^30 (twice the length must fit the
+ * table's 32-bit slot count); outside that arx_set_lookup_state_bytes returns 0 and build / probe return
+ * ARX_CAPACITY_ERROR.
+ * arx_set_lookup_build / _build_binary: synchronous (the table is filled in rounds, each read back).  hash_bits: bits of
+ * the 64-bit string hash kept (64 in production; fewer force collisions in tests, which the byte comparison resolves);
+ * the probes of a binary set take the same value.  offset widths: 4 (utf8 / binary) or 8 (large_utf8 / large_binary),
+ * the set's and the input's independently.
+ * arx_set_lookup_is_in: out_bits = ceil(length / 64) words, bit i set iff row i is in the set (never null).
+ * arx_set_lookup_index_in: out_index[i] = the index of row i's first occurrence in the set (int32; 0 where absent),
+ * out_validity = ceil(length / 64) words, bit i clear where row i is absent.  Outputs start at offset 0.  The probes are
+ * asynchronous.  arx_get_counter("set_lookup_lds_probes" / "set_lookup_global_probes") counts the probes whose table
+ * was read from LDS (at most 64 KiB of table) or from global memory. */
+size_t arx_set_lookup_state_bytes(int64_t set_length, int key_width);
+int arx_set_lookup_build(void* state, const ArxSpan* value_set, int key_width, void* stream);
+int arx_set_lookup_build_binary(void* state, const ArxBinarySpan* value_set, int offset_width, int hash_bits, void* stream);
+int arx_set_lookup_is_in(const void* state, int64_t set_length, int key_width, const ArxSpan* values, int skip_nulls,
+                         void* out_bits, void* stream);
+int arx_set_lookup_index_in(const void* state, int64_t set_length, int key_width, const ArxSpan* values, int skip_nulls,
+                            int32_t* out_index, void* out_validity, void* stream);
+int arx_set_lookup_is_in_binary(const void* state, const ArxBinarySpan* value_set, int set_offset_width, int hash_bits,
+                                const ArxBinarySpan* values, int offset_width, int skip_nulls, void* out_bits, void* stream);
+int arx_set_lookup_index_in_binary(const void* state, const ArxBinarySpan* value_set, int set_offset_width, int hash_bits,
+                                   const ArxBinarySpan* values, int offset_width, int skip_nulls, int32_t* out_index,
+                                   void* out_validity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
