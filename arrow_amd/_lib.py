@@ -252,6 +252,14 @@ SIGNATURES = {
     "arx_set_lookup_index_in": (_int, [_p, _i64, _int, _span, _int, _p, _p, _p]),
     "arx_set_lookup_is_in_binary": (_int, [_p, _bspan, _int, _int, _bspan, _int, _int, _p, _p]),
     "arx_set_lookup_index_in_binary": (_int, [_p, _bspan, _int, _int, _bspan, _int, _int, _p, _p, _p]),
+    "arx_hash_join_workspace_bytes": (_sz, [_i64]),
+    "arx_hash_join_key_validity": (_int, [_span, _int, _i64, _p, _p]),
+    "arx_hash_join_bool_key": (_int, [_span, _p, _p]),
+    "arx_hash_join_group_offsets": (_int, [_p, _p, _i64, _i64, _p, _p, _sz, _p]),
+    "arx_hash_join_probe_count": (_int, [_p, _p, _i64, _p, _i64, _int, _p, _i64, _p, _p, _sz, C.POINTER(_i64), _p]),
+    "arx_hash_join_expand": (_int, [_p, _p, _p, _i64, _p, _p, _int, _i64, _p, _p, _p, _p]),
+    "arx_hash_join_build_mask": (_int, [_p, _p, _i64, _p, _int, _p, _p]),
+    "arx_hash_join_append_build_rows": (_int, [_p, _i64, _i64, _p, _p, _p, _p, _p]),
     "arx_binary_key_verify": (_int, [_bspan, _p, _p, C.POINTER(_i64), _p, _p]),
     "arx_group_first_rows": (_int, [_p, _i64, _i64, _p, _p]),
     "arx_group_edge_rows": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p]),

@@ -2548,3 +2548,233 @@ def index_in(values: Array, value_set, *, skip_nulls: bool = False) -> Array:
     """compute::IndexIn (scalar_set_lookup.cc): int32, the index of the row's value's first occurrence in `value_set`
     (chunks counted one after the other), null where the value is absent.  The result stays on the device."""
     return _set_lookup(values, value_set, skip_nulls, True)
+
+
+# --------------------------------------------------------------------------- hash join
+# The equi-join of HashJoinNode (acero/hash_join_node.cc): key rows -> ids through the Grouper (right input consumed,
+# left input looked up), then csrc/hash_join.hip: group offsets, probe count (the one read-back), expand, and the
+# build-side mask for right semi / anti and the right-only tail of right / full outer joins.
+JOIN_TYPES = ("left semi", "right semi", "left anti", "right anti", "inner", "left outer", "right outer", "full outer")
+# Output rows a join may produce before arx_hash_join_probe_count refuses it with a capacity error (two int64 index
+# arrays of this many rows are allocated next).  None: what the device's free memory holds.
+HASH_JOIN_MAX_OUTPUT_ROWS = None
+
+
+def _join_type_code(join_type) -> int:
+    if isinstance(join_type, int):
+        if 0 <= join_type < len(JOIN_TYPES):
+            return join_type
+    elif str(join_type).lower().replace("_", " ") in JOIN_TYPES:
+        return JOIN_TYPES.index(str(join_type).lower().replace("_", " "))
+    raise ArrowInvalid(f"hash join: unknown join type {join_type!r}; one of {', '.join(JOIN_TYPES)}")
+
+
+def _as_device_key(a, device):
+    if isinstance(a, Array):
+        return a
+    import pyarrow as pa
+
+    if isinstance(a, pa.ChunkedArray):
+        a = a.combine_chunks() if a.num_chunks else pa.array([], a.type)
+    if isinstance(a, pa.Array) and pa.types.is_dictionary(a.type):
+        raise ArrowNotImplementedError(f"hash join on the device: dictionary keys ({a.type}) are not supported")
+    try:
+        return Array.from_pyarrow(a, device=device)
+    except (KeyError, ArrowNotImplementedError):
+        raise ArrowNotImplementedError(f"hash join on the device: keys of type {a.type}") from None
+
+
+def _bool_key(a: Array) -> Array:
+    """A boolean key column as one byte per row (the Grouper's fixed-width form), same validity and offset."""
+    lib, stream = _lib_and_stream(a.device)
+    out = alloc(max(1, a.offset + a.length), a.device)
+    span = a.span()
+    check(lib.arx_hash_join_bool_key(C.byref(span), out.data_ptr() + a.offset, stream))
+    return Array(uint8, a.length, [a.buffers[0], out], a.null_count, a.offset)
+
+
+def _zero_column(t: DataType, n: int, device) -> Array:
+    return Array(t, n, [None, alloc(max(1, n) * t.byte_width, device, zero=True)], 0, 0)
+
+
+def _join_key_columns(left_keys, right_keys):
+    """Each key pair as the Grouper's fixed-width columns, the same list of types on both sides: fixed-width keys as
+    they are (compared by their bits), booleans as bytes, utf8 / binary as (length, 12-byte chunks) with the shorter
+    side's missing chunks zero, which is what its own zero padding would hold."""
+    lcols, rcols = [], []
+    for a, b in zip(left_keys, right_keys):
+        if a.type != b.type:
+            raise ArrowInvalid(f"hash join: key types differ: {a.type.name} on the left, {b.type.name} on the right")
+        t = a.type
+        if is_base_binary(t):
+            (la, ca), (lb, cb) = binary_key_columns(a), binary_key_columns(b)
+            for _ in range(len(ca), len(cb)):
+                ca.append((_zero_column(uint64, a.length, a.device), _zero_column(uint32, a.length, a.device)))
+            for _ in range(len(cb), len(ca)):
+                cb.append((_zero_column(uint64, b.length, b.device), _zero_column(uint32, b.length, b.device)))
+            lcols += [la] + [c for pair in ca for c in pair]
+            rcols += [lb] + [c for pair in cb for c in pair]
+        elif t == bool_:
+            lcols.append(_bool_key(a))
+            rcols.append(_bool_key(b))
+        elif t.bit_width in (8, 16, 32, 64):
+            lcols.append(a)
+            rcols.append(b)
+        else:
+            raise ArrowNotImplementedError(f"hash join on the device: keys of type {t.name}")
+    return lcols, rcols
+
+
+def _key_validity(arrays, n: int, device):
+    """The AND of the arrays' validity (arx_hash_join_key_validity) as a bitmap tensor, None if none can be null."""
+    arrays = [a for a in arrays if a.may_have_nulls()]
+    if not arrays or n == 0:
+        return None
+    lib, stream = _lib_and_stream(device)
+    out = alloc(bitmap_nbytes(n), device)
+    spans = (_lib.ArxSpan * len(arrays))(*[a.span() for a in arrays])
+    check(lib.arx_hash_join_key_validity(spans, len(arrays), n, out.data_ptr(), stream))
+    return out
+
+
+def _max_output_rows(device, payload_row_bytes: int = 0) -> int:
+    """Output rows a join may produce: HASH_JOIN_MAX_OUTPUT_ROWS, or what free device memory holds at two int64 index
+    arrays and a bitmap (17 bytes) plus `payload_row_bytes` of gathered columns per row."""
+    if HASH_JOIN_MAX_OUTPUT_ROWS is not None:
+        return int(HASH_JOIN_MAX_OUTPUT_ROWS)
+    if device.type == "cuda":
+        free, _ = torch.cuda.mem_get_info(device)
+        return int(free) // (17 + payload_row_bytes)
+    return 1 << 40
+
+
+def _payload_row_bytes(columns) -> int:
+    """Bytes per output row of gathering `columns` (values, offsets and the average string, validity)."""
+    total = 0
+    for c in columns:
+        if is_base_binary(c.type):
+            nbytes = int(c.buffers[2].numel()) if c.buffers[2] is not None else 0
+            total += 4 + 1 + -(-nbytes // max(1, c.length))
+        else:
+            total += max(1, c.type.byte_width) + 1
+    return total
+
+
+def _ptr_or_none(t):
+    return None if t is None else t.data_ptr()
+
+
+def hash_join_indices(left_keys, right_keys, join_type="inner", null_equals_null=False, max_output_rows=None):
+    """The row pairs of the equi-join of the left (probe) and right (build) inputs on their key columns, as
+    (left_indices, right_indices): int64 device Arrays, null where a side is unmatched (outer joins).  Semi / anti joins
+    return only their side's indices and None for the other.  Keys: lists of equal-typed columns (fixed-width types
+    compared by their bits, boolean, utf8 / binary).  null_equals_null: JoinKeyCmp::IS (a bool, or one per key column);
+    otherwise a null key matches nothing.  Row order: inner / outer rows follow the left rows, the right rows of one left
+    row ascend, the right-only rows of right / full outer joins come last in right-row order; semi / anti rows are in
+    input order.  A join of more than max_output_rows rows (default: what free device memory holds) raises
+    ArrowCapacityError before the output is allocated."""
+    jt = _join_type_code(join_type)
+    left_keys, right_keys = list(left_keys), list(right_keys)
+    if not left_keys or len(left_keys) != len(right_keys):
+        raise ArrowInvalid("hash join: the same positive number of key columns on both sides is required")
+    dev = next((k.device for k in left_keys + right_keys if isinstance(k, Array)), None)
+    if dev is None:
+        from .array import default_device
+        dev = default_device()
+    left_keys = [_as_device_key(k, dev) for k in left_keys]
+    right_keys = [_as_device_key(k, dev) for k in right_keys]
+    nl, nb = left_keys[0].length, right_keys[0].length
+    if any(k.length != nl for k in left_keys) or any(k.length != nb for k in right_keys):
+        raise ArrowInvalid("Array arguments must all be the same length")
+    eq_is = list(null_equals_null) if isinstance(null_equals_null, (list, tuple)) else [bool(null_equals_null)] * len(left_keys)
+    if len(eq_is) != len(left_keys):
+        raise ArrowInvalid("hash join: null_equals_null needs one entry per key column")
+    lib, stream = _lib_and_stream(dev)
+    lcols, rcols = _join_key_columns(left_keys, right_keys)
+    grouper = Grouper([c.type for c in rcols], max(1, nb), dev)
+    build_ids = grouper.consume(rcols)
+    num_groups = grouper.num_groups
+    probe_ids = grouper.lookup(lcols)
+    build_valid = _key_validity([k for k, s in zip(right_keys, eq_is) if not s], nb, dev)
+    probe_valid = _key_validity([probe_ids] + [k for k, s in zip(left_keys, eq_is) if not s], nl, dev)
+    bids, pids = build_ids.values_ptr(), probe_ids.values_ptr()
+
+    offsets = alloc((nl + 1) * 8, dev)
+    ws = _workspace(dev, lib.arx_hash_join_workspace_bytes(max(num_groups, nl)), "hash_join")
+    group_offsets = alloc((num_groups + 1) * 8, dev)
+    check(lib.arx_hash_join_group_offsets(bids, _ptr_or_none(build_valid), nb, num_groups, group_offsets.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), stream))
+    right_side = jt in (1, 3, 6, 7)
+    matched = alloc(max(1, num_groups), dev, zero=True) if right_side else None
+    total = C.c_int64(0)
+    limit = _max_output_rows(dev) if max_output_rows is None else int(max_output_rows)
+    check(lib.arx_hash_join_probe_count(pids, _ptr_or_none(probe_valid), nl, group_offsets.data_ptr(), num_groups, jt,
+                                        _ptr_or_none(matched), limit, offsets.data_ptr(), ws.data_ptr(),
+                                        ws.numel(), C.byref(total), stream))
+    total = total.value
+
+    def build_rows(want_matched: int) -> Array:
+        mask = alloc(bitmap_nbytes(nb), dev)
+        check(lib.arx_hash_join_build_mask(bids, _ptr_or_none(build_valid), nb, matched.data_ptr(), want_matched,
+                                           mask.data_ptr(), stream))
+        return indices_nonzero(Array(bool_, nb, [None, mask], 0, 0))
+
+    if jt in (1, 3):          # right semi / right anti
+        rows = build_rows(1 if jt == 1 else 0)
+        return None, Array(int64, rows.length, rows.buffers, 0, rows.offset)
+    pairs = jt in (4, 5, 6, 7)
+    sorted_rows = None
+    if pairs and total:
+        sorted_rows = sort_indices(Array(uint32, nb, [build_valid, build_ids.data],
+                                         kUnknownNullCount if build_valid is not None else 0, 0))
+    tail = build_rows(0) if jt in (6, 7) else None
+    n_out = total + (tail.length if tail is not None else 0)
+    if n_out > limit:     # the right-only tail of a right / full outer join counts too
+        raise _lib.ArrowCapacityError(f"hash join: the output would have {n_out} rows, more than the {limit} that can "
+                                      "be allocated")
+    out_left = alloc(max(1, n_out) * 8, dev)
+    out_right = alloc(max(1, n_out) * 8, dev) if pairs else None
+    right_valid = alloc(bitmap_nbytes(n_out), dev) if jt in (5, 7) else None
+    check(lib.arx_hash_join_expand(offsets.data_ptr(), pids, _ptr_or_none(probe_valid), nl, group_offsets.data_ptr(),
+                                   _ptr_or_none(sorted_rows.data if sorted_rows is not None else None), jt, total,
+                                   out_left.data_ptr(), _ptr_or_none(out_right), _ptr_or_none(right_valid), stream))
+    left_valid = None
+    if tail is not None and tail.length:
+        left_valid = alloc(bitmap_nbytes(n_out), dev)
+        check(lib.arx_hash_join_append_build_rows(tail.values_ptr(), tail.length, total, out_left.data_ptr(),
+                                                  left_valid.data_ptr(), out_right.data_ptr(),
+                                                  _ptr_or_none(right_valid), stream))
+
+    def idx(buf, valid, nulls):
+        a = Array(int64, n_out, [valid, buf], kUnknownNullCount if valid is not None else 0, 0)
+        if valid is not None and nulls is not None:
+            a._null_count = nulls
+        return a
+
+    left = idx(out_left, left_valid, tail.length if left_valid is not None else None)
+    if not pairs:
+        return left, None
+    return left, idx(out_right, right_valid, None)
+
+
+def hash_join(left_columns, right_columns, left_keys, right_keys, join_type="inner", left_output=None,
+              right_output=None, left_suffix="", right_suffix="", null_equals_null=False):
+    """HashJoinNode over whole inputs held on the device: left_columns / right_columns map names to Arrays (fixed-width,
+    boolean, utf8 / binary), left_keys / right_keys name the key columns.  Output columns: left_output then right_output
+    (default: every column of the side(s) the join type emits), names that occur on both sides get the suffixes
+    (HashJoinSchema's rule).  Returns a list of (name, Array), gathered with `take` by hash_join_indices' row pairs."""
+    jt = _join_type_code(join_type)
+    left_columns, right_columns = dict(left_columns), dict(right_columns)
+    as_list = lambda k: [k] if isinstance(k, str) else list(k)   # noqa: E731
+    lk, rk = as_list(left_keys), as_list(right_keys)
+    lo = [] if jt in (1, 3) else (list(left_columns) if left_output is None else as_list(left_output))
+    ro = [] if jt in (0, 2) else (list(right_columns) if right_output is None else as_list(right_output))
+    payload = [left_columns[n] for n in lo] + [right_columns[n] for n in ro]
+    dev = next(iter(left_columns.values())).device
+    li, ri = hash_join_indices([left_columns[k] for k in lk], [right_columns[k] for k in rk], jt, null_equals_null,
+                               max_output_rows=_max_output_rows(dev, _payload_row_bytes(payload)))
+    out = []
+    for names, cols, ix, suffix, other in ((lo, left_columns, li, left_suffix, ro), (ro, right_columns, ri, right_suffix, lo)):
+        for name in names:
+            out.append((name + suffix if name in other else name, take(cols[name], ix, boundscheck=False)))
+    return out

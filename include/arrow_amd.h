@@ -1314,6 +1314,59 @@ int arx_set_lookup_index_in_binary(const void* state, const ArxBinarySpan* value
                                    const ArxBinarySpan* values, int offset_width, int skip_nulls, int32_t* out_index,
                                    void* out_validity, void* stream);
 
+/* Hash join — the equi-join of HashJoinNode (acero/hash_join_node.cc; SwissJoin, acero/swiss_join.cc) after the Grouper:
+ * the right (build) input's key rows are consumed (arx_grouper_consume: dense uint32 ids, G groups), the left (probe)
+ * input's are looked up (arx_grouper_lookup: an id or null).  Under JoinKeyCmp::EQ a null in any key column matches
+ * nothing (JoinKeyCmp::IS: null equals null, the Grouper's own rule); the caller folds the EQ key columns' validity into
+ * the id validity with arx_hash_join_key_validity.  Keys compare by their bits (-0.0 and 0.0 differ, a NaN matches
+ * the same NaN), as the Grouper and the reference's row encoder do.  join_type: arrow::acero::JoinType's values,
+ * LEFT_SEMI 0, RIGHT_SEMI 1, LEFT_ANTI 2, RIGHT_ANTI 3, INNER 4, LEFT_OUTER 5, RIGHT_OUTER 6, FULL_OUTER 7.
+ * Row order (the reference leaves it unspecified): inner / outer rows follow the probe rows; within one probe row the
+ * build rows ascend; the right-only rows of right / full outer joins come last in build-row order; semi / anti outputs
+ * are in input row order.  Bitmaps here start at offset 0, ceil(length / 64) 64-bit words, 8-byte aligned; NULL = all
+ * valid.  ws: arx_hash_join_workspace_bytes(length) device bytes, 8-byte aligned (length = G for the group offsets,
+ * the probe length for the probe count).
+ * arx_hash_join_key_validity: out_bits = the AND of the columns' validity bitmaps (columns of `length` rows, any offset;
+ * none with nulls: all ones).  Asynchronous.
+ * arx_hash_join_bool_key: out[i] = bit i of a boolean column's values (one byte per row, the Grouper's key form).  Async.
+ * arx_hash_join_group_offsets: out_group_offsets[G + 1] (int64) = exclusive scan of the number of valid build rows per
+ * id, out_group_offsets[G] = their total.  The build rows of a group in ascending order are the stable sort of the ids
+ * with invalid rows last (arx_sort_indices, ARX_KEY_UINT32, nulls at end): group g's rows are sorted[offsets[g] ..
+ * offsets[g + 1]).  Asynchronous.
+ * arx_hash_join_probe_count: synchronous (one read-back: the total).  out_offsets[num_probe_rows + 1] (int64) = the
+ * exclusive scan of every probe row's output rows: its group's size (inner, right outer), at least 1 (left / full
+ * outer), 0 or 1 (left semi: matched, left anti: unmatched), 0 (right semi / anti); *out_total = the sum.  For right
+ * semi / anti / outer and full outer, matched[g] (G bytes, caller-zeroed, may be NULL otherwise) is set to 1 for every
+ * group a probe row hits.  A total above max_output (>= 0; -1: no limit) or above INT64_MAX returns
+ * ARX_CAPACITY_ERROR before anything is allocated for the output.
+ * arx_hash_join_expand: output slot j in [0, total) gets out_left[j] = its probe row and, for inner / outer joins,
+ * out_right[j] = its build row (build_rows_by_group: the sorted rows above, uint64); an unmatched left / full outer row
+ * gets a null right index (0, bit clear in out_right_validity; may be NULL when no row can be unmatched).  Semi / anti
+ * joins: out_right, group_offsets and build_rows_by_group unused.  Load-balanced over output slots (512 per workgroup),
+ * so one key with many build rows does not serialise a lane.  out_left / out_right: 16-byte aligned.  Asynchronous.
+ * arx_hash_join_build_mask: out_bits bit i = (build row i's key valid and matched[id_i]) == (want_matched != 0): the
+ * rows of a right semi join (want_matched 1), of a right anti join and of the right-only tail (0), to compact with
+ * arx_filter_count + arx_mask_to_indices (index_width 8).  Asynchronous.
+ * arx_hash_join_append_build_rows: slots [start, start + count) get a null left index and out_right = build_rows[k]
+ * (uint64 row numbers); out_left_validity (ceil((start + count) / 64) words) is written whole: valid below start, null
+ * from it; out_right_validity (may be NULL) keeps its bits below start and is set from it.  Asynchronous. */
+size_t arx_hash_join_workspace_bytes(int64_t length);
+int arx_hash_join_key_validity(const ArxSpan* columns, int num_columns, int64_t length, void* out_bits, void* stream);
+int arx_hash_join_bool_key(const ArxSpan* values, uint8_t* out, void* stream);
+int arx_hash_join_group_offsets(const uint32_t* build_ids, const void* build_valid, int64_t num_build_rows,
+                                int64_t num_groups, int64_t* out_group_offsets, void* ws, size_t ws_bytes, void* stream);
+int arx_hash_join_probe_count(const uint32_t* probe_ids, const void* probe_valid, int64_t num_probe_rows,
+                              const int64_t* group_offsets, int64_t num_groups, int join_type, uint8_t* matched,
+                              int64_t max_output, int64_t* out_offsets, void* ws, size_t ws_bytes, int64_t* out_total,
+                              void* stream);
+int arx_hash_join_expand(const int64_t* offsets, const uint32_t* probe_ids, const void* probe_valid, int64_t num_probe_rows,
+                         const int64_t* group_offsets, const uint64_t* build_rows_by_group, int join_type, int64_t total,
+                         int64_t* out_left, int64_t* out_right, void* out_right_validity, void* stream);
+int arx_hash_join_build_mask(const uint32_t* build_ids, const void* build_valid, int64_t num_build_rows,
+                             const uint8_t* matched, int want_matched, void* out_bits, void* stream);
+int arx_hash_join_append_build_rows(const uint64_t* build_rows, int64_t count, int64_t start, int64_t* out_left,
+                                    void* out_left_validity, int64_t* out_right, void* out_right_validity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
