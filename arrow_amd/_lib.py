@@ -22,7 +22,7 @@ ARX_INDEX_ERROR = -7
 ARX_NOT_IMPLEMENTED = -10
 ARX_DEVICE_ERROR = -100
 
-ABI_VERSION = 3  # ARX_ABI_VERSION of include/arrow_amd.h
+ABI_VERSION = 4  # ARX_ABI_VERSION of include/arrow_amd.h
 
 FILTER_DROP, FILTER_EMIT_NULL = 0, 1
 SORT_ASCENDING, SORT_DESCENDING = 0, 1
@@ -147,25 +147,6 @@ SIGNATURES = {
     "arx_levels_ge_bitmap": (_int, [_p, _i64, _u32, _p, _p, _p]),
     "arx_lz4_decompress_streams": (_int, [_p, _p, _p, _i64, _p, _p, _p]),
     "arx_lz4_frame_scan": (_int, [_p, _sz, _u64, _p, _i64, C.POINTER(_i64), C.POINTER(_u64)]),
-    "arx_cast_f64_f32": (_int, [_p, _i64, _p, _p]),
-    "arx_cast_i64_i32": (_int, [_span, _int, _p, _sz, _p, _p]),
-    "arx_cast_i32_i64": (_int, [_p, _i64, _p, _p]),
-    "arx_cast_i64_f64": (_int, [_span, _int, _p, _sz, _p, _p]),
-    "arx_greater_f64": (_int, [_p, _p, _i64, _p, _p]),
-    "arx_greater_f64_array_scalar": (_int, [_p, C.c_double, _i64, _p, _p]),
-    "arx_greater_f64_scalar_array": (_int, [C.c_double, _p, _i64, _p, _p]),
-    "arx_greater_i64": (_int, [_p, _p, _i64, _p, _p]),
-    "arx_arith_i64": (_int, [_int, _p, _i64, _p, _i64, _i64, _p, _p]),
-    "arx_arith_f64": (_int, [_int, _p, C.c_double, _p, C.c_double, _i64, _p, _p]),
-    "arx_arith_checked_i64": (_int, [_int, _p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _p, _p, _p]),
-    "arx_compare_f64": (_int, [_int, _p, C.c_double, _p, C.c_double, _i64, _p, _p]),
-    "arx_compare_i64": (_int, [_int, _p, _i64, _p, _i64, _i64, _p, _p]),
-    "arx_greater_i64_array_scalar": (_int, [_p, _i64, _i64, _p, _p]),
-    "arx_greater_i64_scalar_array": (_int, [_i64, _p, _i64, _p, _p]),
-    "arx_add_i64_array_scalar": (_int, [_p, _i64, _i64, _p, _p]),
-    "arx_add_f64_array_scalar": (_int, [_p, C.c_double, _i64, _p, _p]),
-    "arx_add_i64": (_int, [_p, _p, _i64, _p, _p]),
-    "arx_add_f64": (_int, [_p, _p, _i64, _p, _p]),
     "arx_bitmap_copy": (_int, [_p, _i64, _i64, _p, _p]),
     "arx_buffer_copy": (_int, [_p, _p, _i64, _p]),
     "arx_delta_scan_miniblocks": (_int, [_p, _sz, _u64, _p, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64),
@@ -176,8 +157,6 @@ SIGNATURES = {
     "arx_byte_stream_split_decode": (_int, [_p, _i64, _int, _p, _p]),
     "arx_delta_byte_array_lengths": (_int, [_p, _p, _i64, _p, _i64, _p, _p, _p]),
     "arx_delta_byte_array_expand": (_int, [_p, _p, _p, _i64, _p, C.c_int32, _p, _p, _i64, _p, _p, _p]),
-    "arx_divide_i64": (_int, [_p, _i64, _p, _i64, _p, _i64, _p, _i64, _i64, _int, _p, _p, _p]),
-    "arx_divide_f64": (_int, [_p, C.c_double, _p, _i64, _p, C.c_double, _p, _i64, _i64, _int, _p, _p, _p]),
     "arx_bitmap_copy_at": (_int, [_p, _i64, _i64, _p, _i64, _p]),
     "arx_binary_rebase_offsets": (_int, [_p, _i64, C.c_int32, _p, _p]),
     "arx_bitmap_and": (_int, [_p, _i64, _p, _i64, _i64, _p, _p]),

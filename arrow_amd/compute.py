@@ -333,48 +333,6 @@ def _exec_binary_filter(args, options):
     return _exec_binary_take([values, indices], TakeOptions(boundscheck=False))
 
 
-def _exec_cast_f64_f32(args, options):
-    """CastFloatingToFloating (scalar_cast_numeric.cc:56-60) under ScalarExecutor."""
-    (arr,) = args
-    dev = arr.device
-    lib, stream = _lib_and_stream(dev)
-    out = alloc(arr.length * 4, dev)
-    with tracing.span("arx_cast_f64_f32"):
-        check(lib.arx_cast_f64_f32(arr.values_ptr(), arr.length, out.data_ptr(), stream))
-    validity, nc = _propagate_validity([arr], arr.length, dev)
-    return Array(float32, arr.length, [validity, out], nc, 0)
-
-
-def _exec_cast_i64_i32(args, options):
-    """CastIntegerToInteger (scalar_cast_numeric.cc:46-54): IntegersCanFit unless allow_int_overflow."""
-    (arr,) = args
-    dev = arr.device
-    lib, stream = _lib_and_stream(dev)
-    n = arr.length
-    out = alloc(n * 4, dev)
-    ws = _workspace(dev, 64, "cast")
-    sp = arr.span()
-    check(lib.arx_cast_i64_i32(C.byref(sp), int(bool(getattr(options, "allow_int_overflow", False))), ws.data_ptr(),
-                               ws.numel(), out.data_ptr(), stream))
-    validity, nc = _propagate_validity([arr], n, dev)
-    return Array(int32, n, [validity, out], nc, 0)
-
-
-def _exec_cast_i64_f64(args, options):
-    """CastIntegerToFloating (scalar_cast_numeric.cc:270-279): exactness check unless allow_float_truncate."""
-    (arr,) = args
-    dev = arr.device
-    lib, stream = _lib_and_stream(dev)
-    n = arr.length
-    out = alloc(n * 8, dev)
-    ws = _workspace(dev, 64, "cast")
-    sp = arr.span()
-    check(lib.arx_cast_i64_f64(C.byref(sp), int(bool(getattr(options, "allow_float_truncate", False))), ws.data_ptr(),
-                               ws.numel(), out.data_ptr(), stream))
-    validity, nc = _propagate_validity([arr], n, dev)
-    return Array(float64, n, [validity, out], nc, 0)
-
-
 # ARX_NUM_* of include/arrow_amd.h
 _NUM_TYPE_ID = {"int8": 0, "uint8": 1, "int16": 2, "uint16": 3, "int32": 4, "uint32": 5, "int64": 6, "uint64": 7,
                 "float": 8, "double": 9}
@@ -392,173 +350,22 @@ def _make_exec_cast_numeric(to_type: DataType):
         out = alloc(n * to_type.byte_width, dev)
         ws = _workspace(dev, 64, "cast")
         sp = arr.span()
-        check(lib.arx_cast_numeric(C.byref(sp), _NUM_TYPE_ID[arr.type.name], _NUM_TYPE_ID[to_type.name],
-                                   int(bool(getattr(options, "allow_int_overflow", False))),
-                                   int(bool(getattr(options, "allow_float_truncate", False))),
-                                   ws.data_ptr(), ws.numel(), out.data_ptr(), stream))
+        with tracing.span("arx_cast_numeric"):
+            check(lib.arx_cast_numeric(C.byref(sp), _NUM_TYPE_ID[arr.type.name], _NUM_TYPE_ID[to_type.name],
+                                       int(bool(getattr(options, "allow_int_overflow", False))),
+                                       int(bool(getattr(options, "allow_float_truncate", False))),
+                                       ws.data_ptr(), ws.numel(), out.data_ptr(), stream))
         validity, nc = _propagate_validity([arr], n, dev)
         return Array(to_type, n, [validity, out], nc, 0)
     return _exec
-
-
-def _exec_cast_i32_i64(args, options):
-    (arr,) = args
-    dev = arr.device
-    lib, stream = _lib_and_stream(dev)
-    n = arr.length
-    out = alloc(n * 8, dev)
-    check(lib.arx_cast_i32_i64(arr.values_ptr(), n, out.data_ptr(), stream))
-    validity, nc = _propagate_validity([arr], n, dev)
-    return Array(int64, n, [validity, out], nc, 0)
 
 
 def _scalar_value(x):
     return x.value if isinstance(x, Scalar) else x
 
 
-def _exec_greater(args, options):
-    """CompareKernel<..., Greater>::Exec (scalar_compare.cc:259-298)."""
-    left, right = args
-    arr = left if isinstance(left, Array) else right
-    dev = arr.device
-    lib, stream = _lib_and_stream(dev)
-    n = arr.length
-    out = alloc(bitmap_nbytes(n), dev, zero=True)
-    t = arr.type
-    if isinstance(left, Array) and isinstance(right, Array):
-        if left.length != right.length:
-            raise ArrowInvalid("Array arguments must all be the same length")
-        fn = lib.arx_greater_f64 if t == float64 else lib.arx_greater_i64
-        with tracing.span("arx_greater"):
-            check(fn(left.values_ptr(), right.values_ptr(), n, out.data_ptr(), stream))
-    elif isinstance(left, Array):
-        if t == float64:
-            check(lib.arx_greater_f64_array_scalar(left.values_ptr(), float(_scalar_value(right) or 0.0), n,
-                                                   out.data_ptr(), stream))
-        else:
-            check(lib.arx_greater_i64_array_scalar(left.values_ptr(), int(_scalar_value(right) or 0), n,
-                                                   out.data_ptr(), stream))
-    else:
-        if t == float64:
-            check(lib.arx_greater_f64_scalar_array(float(_scalar_value(left) or 0.0), right.values_ptr(), n,
-                                                   out.data_ptr(), stream))
-        else:
-            check(lib.arx_greater_i64_scalar_array(int(_scalar_value(left) or 0), right.values_ptr(), n,
-                                                   out.data_ptr(), stream))
-    validity, nc = _propagate_validity([left, right], n, dev)
-    return Array(bool_, n, [validity, out], nc, 0)
-
-
 _ARITH_CODE = {"add": 0, "subtract": 1, "multiply": 2}
-
-
-def _exec_arith(op_name, checked):
-    code = _ARITH_CODE[op_name]
-
-    def run(args, options):
-        """ScalarBinary<..., Add|Subtract|Multiply> / ScalarBinaryNotNull<..., *Checked>
-        (codegen_internal.h:814-; base_arithmetic_internal.h:45-150,290-364)."""
-        left, right = args
-        arr = left if isinstance(left, Array) else right
-        dev = arr.device
-        lib, stream = _lib_and_stream(dev)
-        n = arr.length
-        if isinstance(left, Array) and isinstance(right, Array) and left.length != right.length:
-            raise ArrowInvalid("Array arguments must all be the same length")
-        is_f = arr.type == float64
-        conv = float if is_f else int
-        lp = left.values_ptr() if isinstance(left, Array) else None
-        rp = right.values_ptr() if isinstance(right, Array) else None
-        ls = conv(_scalar_value(left) or 0) if lp is None else conv(0)
-        rs = conv(_scalar_value(right) or 0) if rp is None else conv(0)
-        out = alloc(n * 8, dev)
-        validity, nc = _propagate_validity([left, right], n, dev)
-        null_scalar = any(isinstance(a, Scalar) and not a.is_valid for a in (left, right))
-        if is_f:
-            check(lib.arx_arith_f64(code, lp, ls, rp, rs, n, out.data_ptr(), stream))
-        elif not checked or null_scalar:      # a null scalar makes every slot null: nothing to check
-            check(lib.arx_arith_i64(code, lp, ls, rp, rs, n, out.data_ptr(), stream))
-        else:
-            flag = torch.zeros(1, dtype=torch.int32, device=dev)
-
-            def vptr(a):
-                return (a.validity.data_ptr(), a.offset) if isinstance(a, Array) and a.may_have_nulls() else (None, 0)
-            (lvp, lvo), (rvp, rvo) = vptr(left), vptr(right)
-            check(lib.arx_arith_checked_i64(code, lp, ls, lvp, lvo, rp, rs, rvp, rvo, n, out.data_ptr(),
-                                            flag.data_ptr(), stream))
-            if int(flag.cpu()[0]) != 0:
-                raise ArrowInvalid("overflow")   # AddChecked::Call, base_arithmetic_internal.h:77
-        return Array(arr.type, n, [validity, out], nc, 0)
-    return run
-
-
-def _exec_divide(checked: bool):
-    def run(args, options):
-        """ScalarBinaryNotNull<..., Divide | DivideChecked> (base_arithmetic_internal.h:366-424): only slots where both
-        operands are valid are visited; the last failing slot names the error."""
-        left, right = args
-        arr = left if isinstance(left, Array) else right
-        dev = arr.device
-        lib, stream = _lib_and_stream(dev)
-        n = arr.length
-        if isinstance(left, Array) and isinstance(right, Array) and left.length != right.length:
-            raise ArrowInvalid("Array arguments must all be the same length")
-        is_f = arr.type == float64
-        conv = float if is_f else int
-        lp = left.values_ptr() if isinstance(left, Array) else None
-        rp = right.values_ptr() if isinstance(right, Array) else None
-        null_scalar = any(isinstance(a, Scalar) and not a.is_valid for a in (left, right))
-        ls = conv(_scalar_value(left) or 0) if lp is None else conv(0)
-        rs = conv(_scalar_value(right) or 0) if rp is None else conv(0)
-        if null_scalar:           # every slot is null: nothing is visited (keep the kernel away from a 0 divisor)
-            ls, rs = (ls, conv(1)) if rp is None else (ls, rs)
-        out = alloc(n * 8, dev)
-        validity, nc = _propagate_validity([left, right], n, dev)
-        errors = torch.zeros(2, dtype=torch.int64, device=dev)
-
-        def vptr(a):
-            return (a.validity.data_ptr(), a.offset) if isinstance(a, Array) and a.may_have_nulls() else (None, 0)
-        (lvp, lvo), (rvp, rvo) = vptr(left), vptr(right)
-        fn = lib.arx_divide_f64 if is_f else lib.arx_divide_i64
-        check(fn(lp, ls, lvp, lvo, rp, rs, rvp, rvo, n, 1 if checked else 0, out.data_ptr(), errors.data_ptr(), stream))
-        if not null_scalar:
-            last_overflow, last_zero = errors.cpu().tolist()
-            if last_zero > last_overflow:
-                raise ArrowInvalid("divide by zero")
-            if last_overflow:
-                raise ArrowInvalid("overflow")
-        return Array(arr.type, n, [validity, out], nc, 0)
-    return run
-
-
 _CMP_CODE = {"equal": 0, "not_equal": 1, "greater": 2, "greater_equal": 3, "less": 4, "less_equal": 5}
-
-
-def _exec_compare(op_name):
-    code = _CMP_CODE[op_name]
-
-    def run(args, options):
-        """CompareKernel<..., Op>::Exec (scalar_compare.cc:259-298) for Op in Equal ... LessEqual."""
-        left, right = args
-        arr = left if isinstance(left, Array) else right
-        dev = arr.device
-        lib, stream = _lib_and_stream(dev)
-        n = arr.length
-        if isinstance(left, Array) and isinstance(right, Array) and left.length != right.length:
-            raise ArrowInvalid("Array arguments must all be the same length")
-        out = alloc(bitmap_nbytes(n), dev, zero=True)
-        is_f = arr.type == float64
-        conv = float if is_f else int
-        lp = left.values_ptr() if isinstance(left, Array) else None
-        rp = right.values_ptr() if isinstance(right, Array) else None
-        ls = conv(_scalar_value(left) or 0) if lp is None else conv(0)
-        rs = conv(_scalar_value(right) or 0) if rp is None else conv(0)
-        fn = lib.arx_compare_f64 if is_f else lib.arx_compare_i64
-        with tracing.span("arx_compare"):
-            check(fn(code, lp, ls, rp, rs, n, out.data_ptr(), stream))
-        validity, nc = _propagate_validity([left, right], n, dev)
-        return Array(bool_, n, [validity, out], nc, 0)
-    return run
 
 
 def _numeric_operands(left, right):
@@ -583,6 +390,17 @@ def _numeric_operands(left, right):
     lp = left.values_ptr() if isinstance(left, Array) else None
     rp = right.values_ptr() if isinstance(right, Array) else None
     return arr, n, lp, lsp, rp, rsp, (lh, rh)
+
+
+def _validity_ptr(a):
+    """(validity bitmap pointer | None, bit offset) of an operand: None for a scalar and for an array without nulls."""
+    return (a.validity.data_ptr(), a.offset) if isinstance(a, Array) and a.may_have_nulls() else (None, 0)
+
+
+def _has_null_scalar(left, right) -> bool:
+    """A null scalar operand makes every slot of the result null: ScalarBinaryNotNull visits none, so no slot can fail
+    a check (codegen_internal.h; the all-null validity itself comes from _propagate_validity)."""
+    return any(isinstance(a, Scalar) and not a.is_valid for a in (left, right))
 
 
 def _num_type_id(t: DataType) -> int:
@@ -625,14 +443,10 @@ def _exec_arith_numeric(op_name, checked):
         lib, stream = _lib_and_stream(dev)
         out = alloc(n * arr.type.byte_width, dev)
         validity, nc = _propagate_validity([left, right], n, dev)
-        null_scalar = any(isinstance(a, Scalar) and not a.is_valid for a in (left, right))
         is_f = arr.type.name in ("float", "double")
-        do_check = checked and not is_f and not null_scalar      # a null scalar makes every slot null: nothing to check
+        do_check = checked and not is_f and not _has_null_scalar(left, right)
         flag = torch.zeros(1, dtype=torch.int32, device=dev) if do_check else None
-
-        def vptr(a):
-            return (a.validity.data_ptr(), a.offset) if isinstance(a, Array) and a.may_have_nulls() else (None, 0)
-        (lvp, lvo), (rvp, rvo) = vptr(left), vptr(right)
+        (lvp, lvo), (rvp, rvo) = _validity_ptr(left), _validity_ptr(right)
         with tracing.span("arx_arith_numeric"):
             check(lib.arx_arith_numeric(code, 1 if do_check else 0, _NUM_TYPE_ID[arr.type.name], lp, lsp, lvp, lvo, rp, rsp,
                                         rvp, rvo, n, out.data_ptr(), None if flag is None else flag.data_ptr(), stream))
@@ -651,16 +465,13 @@ def _exec_divide_numeric(checked: bool):
         arr, n, lp, lsp, rp, rsp, _keep = _numeric_operands(left, right)
         dev = arr.device
         lib, stream = _lib_and_stream(dev)
-        null_scalar = any(isinstance(a, Scalar) and not a.is_valid for a in (left, right))
-        if null_scalar and rp is None:      # every slot is null: nothing is visited (keep the kernel away from a 0 divisor)
+        null_scalar = _has_null_scalar(left, right)
+        if null_scalar and rp is None:      # nothing is visited: keep the kernel away from a 0 divisor
             _keep[1][0] = 1
         out = alloc(n * arr.type.byte_width, dev)
         validity, nc = _propagate_validity([left, right], n, dev)
         errors = torch.zeros(2, dtype=torch.int64, device=dev)
-
-        def vptr(a):
-            return (a.validity.data_ptr(), a.offset) if isinstance(a, Array) and a.may_have_nulls() else (None, 0)
-        (lvp, lvo), (rvp, rvo) = vptr(left), vptr(right)
+        (lvp, lvo), (rvp, rvo) = _validity_ptr(left), _validity_ptr(right)
         with tracing.span("arx_divide_numeric"):
             check(lib.arx_divide_numeric(1 if checked else 0, _NUM_TYPE_ID[arr.type.name], lp, lsp, lvp, lvo, rp, rsp, rvp, rvo, n,
                                          out.data_ptr(), errors.data_ptr(), stream))
@@ -672,30 +483,6 @@ def _exec_divide_numeric(checked: bool):
                 raise ArrowInvalid("overflow")
         return Array(arr.type, n, [validity, out], nc, 0)
     return run
-
-
-def _exec_add(args, options):
-    """ScalarBinary<..., Add> (codegen_internal.h:814, base_arithmetic_internal.h:45-80)."""
-    left, right = args
-    if not isinstance(left, Array):      # scalar + array: add commutes
-        left, right = right, left
-    dev = left.device
-    lib, stream = _lib_and_stream(dev)
-    n = left.length
-    out = alloc(n * 8, dev)
-    if isinstance(right, Array):
-        if left.length != right.length:
-            raise ArrowInvalid("Array arguments must all be the same length")
-        fn = lib.arx_add_i64 if left.type == int64 else lib.arx_add_f64
-        check(fn(left.values_ptr(), right.values_ptr(), n, out.data_ptr(), stream))
-    elif left.type == int64:
-        check(lib.arx_add_i64_array_scalar(left.values_ptr(), int(_scalar_value(right) or 0), n, out.data_ptr(),
-                                           stream))
-    else:
-        check(lib.arx_add_f64_array_scalar(left.values_ptr(), float(_scalar_value(right) or 0.0), n,
-                                           out.data_ptr(), stream))
-    validity, nc = _propagate_validity([left, right], n, dev)
-    return Array(left.type, n, [validity, out], nc, 0)
 
 
 def _exec_kleene(op_code):
@@ -1163,25 +950,15 @@ def _build_registry() -> FunctionRegistry:
     reg.add_function(Function("take", Function.META, 2, TakeOptions(), _take_meta))
 
     # one cast function per numeric target (GetCastFunction, cast.cc:207-214; kernels of
-    # scalar_cast_numeric.cc:797-858): the generic pair kernel first, the tuned ones after it (last match wins)
+    # scalar_cast_numeric.cc:797-858); arx_cast_numeric picks the kernel for the pair
     for to in (int8, uint8, int16, uint16, int32, uint32, int64, uint64, float32, float64):
         c = Function("cast_" + to.name, Function.SCALAR, 1)
         c.add_kernel(Kernel((_NUMERIC,), _make_exec_cast_numeric(to), to))
         _cast_table[to.name] = c
-    _cast_table["float"].add_kernel(Kernel((float64,), _exec_cast_f64_f32, float32))
-    _cast_table["int32"].add_kernel(Kernel((int64,), _exec_cast_i64_i32, int32))
-    _cast_table["int64"].add_kernel(Kernel((int32,), _exec_cast_i32_i64, int64))
-    _cast_table["double"].add_kernel(Kernel((int64,), _exec_cast_i64_f64, float64))
     reg.add_function(Function("cast", Function.META, 1, None, _cast_meta))
 
     from .array import type_from_name
     numeric_types = [type_from_name(nm) for nm in _NUM_TYPE_ID]
-    f = Function("greater", Function.SCALAR, 2)
-    for t in numeric_types:      # every numeric type first; the tuned 64-bit kernels are added after them and win
-        f.add_kernel(Kernel((t, t), _exec_compare_numeric("greater"), bool_))
-    f.add_kernel(Kernel((float64, float64), _exec_greater, bool_))
-    f.add_kernel(Kernel((int64, int64), _exec_greater, bool_))
-    reg.add_function(f)
     # temporal operands (timestamp / duration / time / date): the comparisons of their physical integers; both sides of
     # the same type and unit — the reference unifies units by implicit casts before dispatch (DispatchBest), and compares
     # a zoned timestamp only with a zoned one (scalar_compare.cc:299-313)
@@ -1201,39 +978,26 @@ def _build_registry() -> FunctionRegistry:
             return run(args, options)
         return Kernel((is_temporal, is_temporal), checked, bool_)
 
-
-    for name in ("equal", "not_equal", "greater_equal", "less", "less_equal"):
+    # one kernel per (function, numeric type) — which device kernel runs is the library's choice — plus the temporal pair
+    for name in _CMP_CODE:
         f = Function(name, Function.SCALAR, 2)
         for t in numeric_types:
             f.add_kernel(Kernel((t, t), _exec_compare_numeric(name), bool_))
-        f.add_kernel(Kernel((float64, float64), _exec_compare(name), bool_))
-        f.add_kernel(Kernel((int64, int64), _exec_compare(name), bool_))
         f.add_kernel(_temporal_pair_kernel(name))
         reg.add_function(f)
-    reg.get_function("greater").add_kernel(_temporal_pair_kernel("greater"))
 
-    f = Function("add", Function.SCALAR, 2)
-    for t in numeric_types:
-        f.add_kernel(Kernel((t, t), _exec_arith_numeric("add", False), t))
-    f.add_kernel(Kernel((int64, int64), _exec_add, int64))
-    f.add_kernel(Kernel((float64, float64), _exec_add, float64))
-    reg.add_function(f)
-    for name, op, checked in (("subtract", "subtract", False), ("multiply", "multiply", False),
+    for name, op, checked in (("add", "add", False), ("subtract", "subtract", False), ("multiply", "multiply", False),
                               ("add_checked", "add", True), ("subtract_checked", "subtract", True),
                               ("multiply_checked", "multiply", True)):
         f = Function(name, Function.SCALAR, 2)
         for t in numeric_types:
             f.add_kernel(Kernel((t, t), _exec_arith_numeric(op, checked), t))
-        f.add_kernel(Kernel((int64, int64), _exec_arith(op, checked), int64))
-        f.add_kernel(Kernel((float64, float64), _exec_arith(op, checked), float64))
         reg.add_function(f)
 
     for name, checked in (("divide", False), ("divide_checked", True)):
         f = Function(name, Function.SCALAR, 2)
         for t in numeric_types:
             f.add_kernel(Kernel((t, t), _exec_divide_numeric(checked), t))
-        f.add_kernel(Kernel((int64, int64), _exec_divide(checked), int64))
-        f.add_kernel(Kernel((float64, float64), _exec_divide(checked), float64))
         reg.add_function(f)
 
     for name, code in (("and_kleene", 0), ("or_kleene", 1)):

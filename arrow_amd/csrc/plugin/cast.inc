@@ -1,14 +1,15 @@
 // The cast meta-function override.
 // Part of the Arrow registration shim: included by ../arrow_plugin.cc inside its anonymous
 // namespace (one translation unit; the split is for reading, not for linkage).
-// ---------------------------------------------------------------- cast(float64 -> float32)
+// ---------------------------------------------------------------- cast between the numeric types
 // Cast kernels live in a private table (GetCastFunction, cpp/src/arrow/compute/cast.cc:207-214)
 // whose DispatchExact returns the FIRST exact-type match (cast.cc:170-205), so an added kernel
 // would never be chosen.  The public route is the one the registry offers: re-register the
 // "cast" MetaFunction (AddFunction(..., allow_overwrite=true), registry.h:69) with a wrapper that
-// takes float64 -> float32 arrays and hands every other cast to the stock meta-function.
-// Semantics: CastPrimitive<FloatType,DoubleType>::Exec (scalar_cast_internal.cc:41-53): every slot
-// converted; validity shared or copied like NullHandling::INTERSECTION does for one input.
+// takes device-resident numeric arrays (and large host float64 -> float32 ones) and hands every other
+// cast to the stock meta-function.
+// Semantics: CastPrimitive<O, I>::Exec (scalar_cast_internal.cc:41-53) + the checks of scalar_cast_numeric.cc;
+// validity shared or copied like NullHandling::INTERSECTION does for one input.
 class RocmCastMetaFunction : public cp::MetaFunction {
  public:
   explicit RocmCastMetaFunction(std::shared_ptr<cp::Function> stock)
@@ -19,30 +20,19 @@ class RocmCastMetaFunction : public cp::MetaFunction {
                                           const cp::FunctionOptions* options,
                                           cp::ExecContext* ctx) const override {
     const auto* cast_options = static_cast<const cp::CastOptions*>(options);
+    // large float64 -> float32 HOST arrays are staged through HBM; every other host cast stays on the stock kernels
     if (cast_options != nullptr && cast_options->to_type.type != nullptr &&
         cast_options->to_type.id() == Type::FLOAT && args.size() == 1 && args[0].is_array() &&
-        args[0].array()->type->id() == Type::DOUBLE) {
-      ArraySpan in(*args[0].array());
-      if (OnRocm(in)) return CastF64F32Device(*args[0].array());
-      if (args[0].length() >= g_min_rows_streaming.load() && IsHost(in)) return CastF64F32(*args[0].array(), ctx);
-    }
-    // integer casts on device-resident arrays: int64 -> int32 (IntegersCanFit unless allow_int_overflow)
-    // and int32 -> int64; host arrays stay on the stock kernels
-    if (cast_options != nullptr && cast_options->to_type.type != nullptr && args.size() == 1 && args[0].is_array()) {
-      const Type::type from = args[0].array()->type->id();
-      const Type::type to = cast_options->to_type.id();
-      if (((from == Type::INT64 && (to == Type::INT32 || to == Type::DOUBLE)) || (from == Type::INT32 && to == Type::INT64)) &&
-          OnRocm(ArraySpan(*args[0].array()))) {
-        return CastIntegerDevice(*args[0].array(), to,
-                                 to == Type::DOUBLE ? cast_options->allow_float_truncate : cast_options->allow_int_overflow);
-      }
+        args[0].array()->type->id() == Type::DOUBLE && args[0].length() >= g_min_rows_streaming.load() &&
+        IsHost(ArraySpan(*args[0].array()))) {
+      return CastF64F32(*args[0].array(), ctx);
     }
     if (args.size() == 1 && args[0].is_array() && DataOnRocm(*args[0].array())) {
       if (cast_options != nullptr && cast_options->to_type.type != nullptr &&
           cast_options->to_type.type->Equals(*args[0].array()->type)) {
         return args[0];      // same type: zero-copy, as the reference does (cast.cc:108-112)
       }
-      // every other pair of the ten numeric types: CastNumberToNumberUnsafe + the reference's checks
+      // every pair of the ten numeric types: CastNumberToNumberUnsafe + the reference's checks
       // (scalar_cast_numeric.cc:41-60, 62-207, 229-279) in arx_cast_numeric
       if (cast_options != nullptr && cast_options->to_type.type != nullptr) {
         const int from_num = NumTypeId(args[0].array()->type->id()), to_num = NumTypeId(cast_options->to_type.id());
@@ -115,79 +105,6 @@ class RocmCastMetaFunction : public cp::MetaFunction {
     return arrow::Datum(ArrayData::Make(options.to_type.GetSharedPtr(), n, {std::move(validity), std::move(out_values)}, null_count));
   }
 
-  static arrow::Result<arrow::Datum> CastIntegerDevice(const ArrayData& in, Type::type to, bool unchecked) {
-    const int64_t n = in.length;
-    hipStream_t st;
-    ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
-    const int out_width = to == Type::INT32 ? 4 : 8;
-    ARROW_ASSIGN_OR_RAISE(auto out_values, AllocDevice(n * out_width));
-    ArxSpan sp{};
-    ARROW_RETURN_NOT_OK(DeviceSpan(ArraySpan(in), &sp));
-    if (to == Type::INT32) {
-      void* ws = nullptr;
-      ARROW_RETURN_NOT_OK(t_scratch.Get(kFlag, 64, &ws));
-      ARROW_RETURN_NOT_OK(FromArx(arx_cast_i64_i32(&sp, unchecked ? 1 : 0, ws, 64,
-                                                   reinterpret_cast<int32_t*>(out_values->mutable_address()), st)));
-    } else if (to == Type::DOUBLE) {
-      void* ws = nullptr;
-      ARROW_RETURN_NOT_OK(t_scratch.Get(kFlag, 64, &ws));
-      ARROW_RETURN_NOT_OK(FromArx(arx_cast_i64_f64(&sp, unchecked ? 1 : 0, ws, 64,
-                                                   reinterpret_cast<double*>(out_values->mutable_address()), st)));
-    } else {
-      ARROW_RETURN_NOT_OK(FromArx(arx_cast_i32_i64(static_cast<const int32_t*>(sp.data) + sp.offset, n,
-                                                   reinterpret_cast<int64_t*>(out_values->mutable_address()), st)));
-    }
-    std::shared_ptr<Buffer> validity;
-    int64_t null_count = 0;
-    if (sp.validity != nullptr && n > 0) {
-      if (in.offset == 0) {
-        validity = in.buffers[0];
-      } else {
-        ARROW_ASSIGN_OR_RAISE(validity, AllocDevice(((n + 63) / 64) * 8));
-        ARROW_RETURN_NOT_OK(FromArx(arx_bitmap_copy(sp.validity, sp.offset, n,
-                                                    reinterpret_cast<void*>(validity->mutable_address()), st)));
-      }
-      null_count = in.null_count.load();
-      if (null_count < 0 || in.offset != 0) {
-        ARROW_ASSIGN_OR_RAISE(null_count, DeviceNullCount(*validity, n, st));
-      }
-    }
-    HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
-    CountGpu(kFnCast);
-    auto type = to == Type::INT32 ? arrow::int32() : (to == Type::DOUBLE ? arrow::float64() : arrow::int64());
-    return arrow::Datum(ArrayData::Make(std::move(type), n, {std::move(validity), std::move(out_values)}, null_count));
-  }
-
-  // device-resident input: output values (and a re-based validity bitmap if offset != 0) in HBM
-  static arrow::Result<arrow::Datum> CastF64F32Device(const ArrayData& in) {
-    const int64_t n = in.length;
-    hipStream_t st;
-    ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
-    ARROW_ASSIGN_OR_RAISE(auto out_values, AllocDevice(n * 4));
-    const double* src = reinterpret_cast<const double*>(in.buffers[1]->address()) + in.offset;
-    ARROW_RETURN_NOT_OK(FromArx(arx_cast_f64_f32(src, n, reinterpret_cast<float*>(out_values->mutable_address()), st)));
-    std::shared_ptr<Buffer> validity;
-    if (in.buffers[0] != nullptr && in.null_count != 0) {
-      if (in.offset == 0) {
-        validity = in.buffers[0];
-      } else {
-        ARROW_ASSIGN_OR_RAISE(validity, AllocDevice(((n + 63) / 64) * 8));
-        ARROW_RETURN_NOT_OK(FromArx(arx_bitmap_copy(reinterpret_cast<const void*>(in.buffers[0]->address()), in.offset,
-                                                    n, reinterpret_cast<void*>(validity->mutable_address()), st)));
-      }
-    }
-    int64_t null_count = 0;
-    if (validity) {
-      null_count = in.null_count.load();
-      if (null_count < 0) {
-        ARROW_ASSIGN_OR_RAISE(null_count, DeviceNullCount(*validity, n, st));
-      }
-    }
-    HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
-    CountGpu(kFnCast);
-    return arrow::Datum(ArrayData::Make(arrow::float32(), n, {std::move(validity), std::move(out_values)}, null_count));
-  }
-
   static arrow::Result<arrow::Datum> CastF64F32(const ArrayData& in, cp::ExecContext* ctx) {
     const int64_t n = in.length;
     hipStream_t st;
@@ -199,8 +116,8 @@ class RocmCastMetaFunction : public cp::MetaFunction {
                           arrow::AllocateBuffer(n * 4, ctx->memory_pool()));
     HIP_RETURN_NOT_OK(hipMemcpyAsync(din, in.GetValues<double>(1), static_cast<size_t>(n) * 8,
                                      hipMemcpyHostToDevice, st));
-    ARROW_RETURN_NOT_OK(FromArx(arx_cast_f64_f32(static_cast<const double*>(din), n,
-                                                 static_cast<float*>(dout), st)));
+    const ArxSpan staged{nullptr, din, 0, n, 0};   // (every slot is converted; validity stays on the host)
+    ARROW_RETURN_NOT_OK(FromArx(arx_cast_numeric(&staged, ARX_NUM_FLOAT64, ARX_NUM_FLOAT32, 0, 0, nullptr, 0, dout, st)));
     HIP_RETURN_NOT_OK(hipMemcpyAsync(out_values->mutable_data(), dout, static_cast<size_t>(n) * 4,
                                      hipMemcpyDeviceToHost, st));
     std::shared_ptr<Buffer> validity;

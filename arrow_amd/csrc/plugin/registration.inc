@@ -147,70 +147,34 @@ Status RegisterAll() {
   ARX_REGISTER_SORT(kSortSlotLargeBinary, arrow::large_binary());
   ARX_REGISTER_SORT(kSortSlotStruct, ValueType(arrow::struct_({arrow::field("a", arrow::int64())}), Type::STRUCT));
 #undef ARX_REGISTER_SORT
-  {
-    ARROW_ASSIGN_OR_RAISE(auto fn, reg->GetFunction("greater"));
-    auto* sfn = static_cast<cp::ScalarFunction*>(fn.get());
-    ARROW_ASSIGN_OR_RAISE(const cp::Kernel* k0, sfn->DispatchExact({arrow::float64(), arrow::float64()}));
-    cp::ScalarKernel copy = *static_cast<const cp::ScalarKernel*>(k0);
-    g_stock_greater.exec = copy.exec;
-    g_stock_greater.init = copy.init;
-    copy.exec = GreaterExecNP;
-    copy.null_handling = cp::NullHandling::COMPUTED_NO_PREALLOCATE;
-    copy.mem_allocation = cp::MemAllocation::NO_PREALLOCATE;
-    ARROW_RETURN_NOT_OK(sfn->AddKernel(std::move(copy)));
-  }
-  ARROW_RETURN_NOT_OK(RegisterScalarBinaryNP<OpGreaterI64>(reg, "greater", arrow::int64()));
-  ARROW_RETURN_NOT_OK(RegisterScalarBinaryNP<OpAddI64>(reg, "add", arrow::int64()));
-  ARROW_RETURN_NOT_OK(RegisterScalarBinaryNP<OpAddF64>(reg, "add", arrow::float64()));
-#define ARX_REGISTER_COMPARE(NAME, CMP, SLOT)                                                                          \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompare<int64_t, arrow::Int64Scalar, CMP, SLOT>>(reg, NAME,          \
-                                                                                               arrow::int64())));    \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompare<double, arrow::DoubleScalar, CMP, SLOT + 1>>(reg, NAME,      \
-                                                                                                  arrow::float64())))
-  ARX_REGISTER_COMPARE("equal", ARX_CMP_EQUAL, 0);
-  ARX_REGISTER_COMPARE("not_equal", ARX_CMP_NOT_EQUAL, 2);
-  ARX_REGISTER_COMPARE("greater_equal", ARX_CMP_GREATER_EQUAL, 4);
-  ARX_REGISTER_COMPARE("less", ARX_CMP_LESS, 6);
-  ARX_REGISTER_COMPARE("less_equal", ARX_CMP_LESS_EQUAL, 8);
-#undef ARX_REGISTER_COMPARE
-#define ARX_REGISTER_ARITH(NAME, OP, CHECKED, SLOT)                                                                     \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpArith<int64_t, arrow::Int64Scalar, OP, CHECKED, SLOT>>(reg, NAME,     \
-                                                                                                     arrow::int64()))); \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpArith<double, arrow::DoubleScalar, OP, CHECKED, SLOT + 1>>(            \
-      reg, NAME, arrow::float64())))
-  ARX_REGISTER_ARITH("subtract", ARX_ARITH_SUBTRACT, false, 0);
-  ARX_REGISTER_ARITH("multiply", ARX_ARITH_MULTIPLY, false, 2);
-  ARX_REGISTER_ARITH("add_checked", ARX_ARITH_ADD, true, 4);
-  ARX_REGISTER_ARITH("subtract_checked", ARX_ARITH_SUBTRACT, true, 6);
-  ARX_REGISTER_ARITH("multiply_checked", ARX_ARITH_MULTIPLY, true, 8);
-#undef ARX_REGISTER_ARITH
-  // the same functions for the other numeric element types (8 types x 6 functions each)
+  // compare / arithmetic / divide: one kernel per (function, numeric type) (plugin/scalar.inc)
 #define ARX_NUM_TYPES(X)                                                                                                     \
   X(int8_t, arrow::Int8Scalar, ARX_NUM_INT8, arrow::int8(), 0) X(uint8_t, arrow::UInt8Scalar, ARX_NUM_UINT8, arrow::uint8(), 1) \
   X(int16_t, arrow::Int16Scalar, ARX_NUM_INT16, arrow::int16(), 2) X(uint16_t, arrow::UInt16Scalar, ARX_NUM_UINT16, arrow::uint16(), 3) \
   X(int32_t, arrow::Int32Scalar, ARX_NUM_INT32, arrow::int32(), 4) X(uint32_t, arrow::UInt32Scalar, ARX_NUM_UINT32, arrow::uint32(), 5) \
-  X(uint64_t, arrow::UInt64Scalar, ARX_NUM_UINT64, arrow::uint64(), 6) X(float, arrow::FloatScalar, ARX_NUM_FLOAT32, arrow::float32(), 7)
+  X(int64_t, arrow::Int64Scalar, ARX_NUM_INT64, arrow::int64(), 6) X(uint64_t, arrow::UInt64Scalar, ARX_NUM_UINT64, arrow::uint64(), 7) \
+  X(float, arrow::FloatScalar, ARX_NUM_FLOAT32, arrow::float32(), 8) X(double, arrow::DoubleScalar, ARX_NUM_FLOAT64, arrow::float64(), 9)
 #define ARX_REG_CMP_NUM(CT, ST, NUM, TYPE, TI)                                                                                \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareNum<CT, ST, NUM, ARX_CMP_EQUAL, 0 * 8 + TI>>(reg, "equal", TYPE)));              \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareNum<CT, ST, NUM, ARX_CMP_NOT_EQUAL, 1 * 8 + TI>>(reg, "not_equal", TYPE)));      \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareNum<CT, ST, NUM, ARX_CMP_GREATER, 2 * 8 + TI>>(reg, "greater", TYPE)));          \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareNum<CT, ST, NUM, ARX_CMP_GREATER_EQUAL, 3 * 8 + TI>>(reg, "greater_equal", TYPE))); \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareNum<CT, ST, NUM, ARX_CMP_LESS, 4 * 8 + TI>>(reg, "less", TYPE)));                \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareNum<CT, ST, NUM, ARX_CMP_LESS_EQUAL, 5 * 8 + TI>>(reg, "less_equal", TYPE)));
+  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompare<CT, ST, NUM, ARX_CMP_EQUAL, 0 * 10 + TI>>(reg, "equal", TYPE)));              \
+  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompare<CT, ST, NUM, ARX_CMP_NOT_EQUAL, 1 * 10 + TI>>(reg, "not_equal", TYPE)));      \
+  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompare<CT, ST, NUM, ARX_CMP_GREATER, 2 * 10 + TI>>(reg, "greater", TYPE)));          \
+  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompare<CT, ST, NUM, ARX_CMP_GREATER_EQUAL, 3 * 10 + TI>>(reg, "greater_equal", TYPE))); \
+  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompare<CT, ST, NUM, ARX_CMP_LESS, 4 * 10 + TI>>(reg, "less", TYPE)));                \
+  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompare<CT, ST, NUM, ARX_CMP_LESS_EQUAL, 5 * 10 + TI>>(reg, "less_equal", TYPE)));
   ARX_NUM_TYPES(ARX_REG_CMP_NUM)
 #undef ARX_REG_CMP_NUM
 #define ARX_REG_ARITH_NUM(CT, ST, NUM, TYPE, TI)                                                                              \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpArithNum<CT, ST, NUM, ARX_ARITH_ADD, false, 0 * 8 + TI>>(reg, "add", TYPE)));            \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpArithNum<CT, ST, NUM, ARX_ARITH_SUBTRACT, false, 1 * 8 + TI>>(reg, "subtract", TYPE)));  \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpArithNum<CT, ST, NUM, ARX_ARITH_MULTIPLY, false, 2 * 8 + TI>>(reg, "multiply", TYPE)));  \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpArithNum<CT, ST, NUM, ARX_ARITH_ADD, true, 3 * 8 + TI>>(reg, "add_checked", TYPE)));     \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpArithNum<CT, ST, NUM, ARX_ARITH_SUBTRACT, true, 4 * 8 + TI>>(reg, "subtract_checked", TYPE))); \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpArithNum<CT, ST, NUM, ARX_ARITH_MULTIPLY, true, 5 * 8 + TI>>(reg, "multiply_checked", TYPE)));
+  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpArith<CT, ST, NUM, ARX_ARITH_ADD, false, 0 * 10 + TI>>(reg, "add", TYPE)));            \
+  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpArith<CT, ST, NUM, ARX_ARITH_SUBTRACT, false, 1 * 10 + TI>>(reg, "subtract", TYPE)));  \
+  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpArith<CT, ST, NUM, ARX_ARITH_MULTIPLY, false, 2 * 10 + TI>>(reg, "multiply", TYPE)));  \
+  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpArith<CT, ST, NUM, ARX_ARITH_ADD, true, 3 * 10 + TI>>(reg, "add_checked", TYPE)));     \
+  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpArith<CT, ST, NUM, ARX_ARITH_SUBTRACT, true, 4 * 10 + TI>>(reg, "subtract_checked", TYPE))); \
+  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpArith<CT, ST, NUM, ARX_ARITH_MULTIPLY, true, 5 * 10 + TI>>(reg, "multiply_checked", TYPE)));
   ARX_NUM_TYPES(ARX_REG_ARITH_NUM)
 #undef ARX_REG_ARITH_NUM
 #define ARX_REG_DIVIDE_NUM(CT, ST, NUM, TYPE, TI)                                                                             \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpDivideNum<CT, ST, NUM, false, 0 * 8 + TI>>(reg, "divide", TYPE)));             \
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpDivideNum<CT, ST, NUM, true, 1 * 8 + TI>>(reg, "divide_checked", TYPE)));
+  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpDivide<CT, ST, NUM, false, 0 * 10 + TI>>(reg, "divide", TYPE)));             \
+  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpDivide<CT, ST, NUM, true, 1 * 10 + TI>>(reg, "divide_checked", TYPE)));
   ARX_NUM_TYPES(ARX_REG_DIVIDE_NUM)
 #undef ARX_REG_DIVIDE_NUM
 #undef ARX_NUM_TYPES
@@ -244,10 +208,6 @@ Status RegisterAll() {
     ARX_REG_CMP_TEMPORAL(int64_t, arrow::Date64Scalar, ARX_NUM_INT64, arrow::date64(), cp::InputType(arrow::date64()), 13)
 #undef ARX_REG_CMP_TEMPORAL
   }
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpDivide<int64_t, arrow::Int64Scalar, false, 0>>(reg, "divide", arrow::int64())));
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpDivide<double, arrow::DoubleScalar, false, 1>>(reg, "divide", arrow::float64())));
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpDivide<int64_t, arrow::Int64Scalar, true, 2>>(reg, "divide_checked", arrow::int64())));
-  ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpDivide<double, arrow::DoubleScalar, true, 3>>(reg, "divide_checked", arrow::float64())));
   ARROW_RETURN_NOT_OK(RegisterBooleanNP(reg, "and_kleene", 2, KleeneExecNP<ARX_AND_KLEENE>, &g_stock_and_kleene));
   ARROW_RETURN_NOT_OK(RegisterBooleanNP(reg, "or_kleene", 2, KleeneExecNP<ARX_OR_KLEENE>, &g_stock_or_kleene));
   ARROW_RETURN_NOT_OK(RegisterBooleanNP(reg, "invert", 1, InvertExecNP, &g_stock_invert));

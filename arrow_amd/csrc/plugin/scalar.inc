@@ -1,264 +1,36 @@
 // Element-wise shims: compare family, arithmetic (+checked), Kleene logic.
 // Part of the Arrow registration shim: included by ../arrow_plugin.cc inside its anonymous
 // namespace (one translation unit; the split is for reading, not for linkage).
-// ---------------------------------------------------------------- greater(double, double)
-StockKernel g_stock_greater;
-
-// ComparePrimitiveArrayArray<DoubleType, Greater> (scalar_compare.cc:165-190); validity is
-// handled by the ScalarExecutor (NullHandling::INTERSECTION), the output bitmap is preallocated.
-Status GreaterExec(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecResult* out) {
-  if (!batch[0].is_array() || !batch[1].is_array() || !out->is_array_span() ||
-      out->array_span()->offset != 0 || batch.length < g_min_rows_streaming.load() ||
-      !IsHost(batch[0].array) || !IsHost(batch[1].array)) {
-    CountStock(kFnGreater);
-    return g_stock_greater.exec(ctx, batch, out);
-  }
-  const ArraySpan& l = batch[0].array;
-  const ArraySpan& r = batch[1].array;
-  const int64_t n = batch.length;
-  hipStream_t st;
-  ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
-  void *dl = nullptr, *dr = nullptr, *dout = nullptr;
-  ARROW_RETURN_NOT_OK(t_scratch.Get(kValues, static_cast<size_t>(n) * 8, &dl));
-  ARROW_RETURN_NOT_OK(t_scratch.Get(kArg2, static_cast<size_t>(n) * 8, &dr));
-  ARROW_RETURN_NOT_OK(t_scratch.Get(kOutData, static_cast<size_t>((n + 63) / 64) * 8, &dout));
-  HIP_RETURN_NOT_OK(hipMemcpyAsync(dl, l.GetValues<double>(1), static_cast<size_t>(n) * 8, hipMemcpyHostToDevice, st));
-  HIP_RETURN_NOT_OK(hipMemcpyAsync(dr, r.GetValues<double>(1), static_cast<size_t>(n) * 8, hipMemcpyHostToDevice, st));
-  ARROW_RETURN_NOT_OK(FromArx(arx_greater_f64(static_cast<const double*>(dl), static_cast<const double*>(dr), n,
-                                              static_cast<uint64_t*>(dout), st)));
-  ArraySpan* o = out->array_span_mutable();
-  HIP_RETURN_NOT_OK(hipMemcpyAsync(o->buffers[1].data, dout, static_cast<size_t>(arrow::bit_util::BytesForBits(n)),
-                                   hipMemcpyDeviceToHost, st));
-  HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
-  CountGpu(kFnGreater);
-  return Status::OK();
-}
-
-// The kernel actually registered for greater(double, double): NullHandling::COMPUTED_NO_PREALLOCATE +
-// MemAllocation::NO_PREALLOCATE, because the ScalarExecutor's own preallocation and null
+// ---------------------------------------------------------------- compare / arithmetic / divide on the numeric types
+// One Op per (function, element type) describes a NO_PREALLOCATE kernel (ScalarBinaryNP below): NullHandling::
+// COMPUTED_NO_PREALLOCATE + MemAllocation::NO_PREALLOCATE, because the ScalarExecutor's own preallocation and null
 // propagation (exec.cc:846-861,1222-1281) run on the CPU and cannot touch device buffers.
-//  * device-resident inputs: compare, validity intersection and null count all on the MI355X,
-//    output bitmap + validity stay in HBM (so compare -> filter chains never leave the device);
-//  * host inputs: allocate what the executor would have preallocated, propagate nulls with Arrow's
-//    own bitmap utilities, then run the preallocated-style exec above (HIP staging path for large
-//    arrays, Arrow's stock kernel for scalars / small inputs).
-Status GreaterExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecResult* out) {
-  const int64_t n = batch.length;
-  ArrayData* out_arr = out->array_data().get();
-  out_arr->buffers.resize(2);
-  const bool dev0 = batch[0].is_array() && OnRocm(batch[0].array);
-  const bool dev1 = batch[1].is_array() && OnRocm(batch[1].array);
-  if (dev0 || dev1) {
-    for (int i = 0; i < 2; ++i) {
-      if (batch[i].is_array() ? !OnRocm(batch[i].array) : !batch[i].scalar->is_valid) {
-        return Status::NotImplemented("arrow_amd: greater on device-resident arrays needs device arrays or "
-                                      "valid scalars on both sides");
-      }
-    }
-    hipStream_t st;
-    ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
-    ARROW_ASSIGN_OR_RAISE(out_arr->buffers[1], AllocDevice(((n + 63) / 64) * 8));
-    uint64_t* dout = reinterpret_cast<uint64_t*>(out_arr->buffers[1]->mutable_address());
-    ArxSpan sp[2] = {};
-    const double* ptr[2] = {nullptr, nullptr};
-    double sc[2] = {0.0, 0.0};
-    for (int i = 0; i < 2; ++i) {
-      if (batch[i].is_array()) {
-        ARROW_RETURN_NOT_OK(DeviceSpan(batch[i].array, &sp[i]));
-        ptr[i] = static_cast<const double*>(sp[i].data) + sp[i].offset;
-      } else {
-        sc[i] = static_cast<const arrow::DoubleScalar&>(*batch[i].scalar).value;
-      }
-    }
-    int rc;
-    if (ptr[0] && ptr[1]) rc = arx_greater_f64(ptr[0], ptr[1], n, dout, st);
-    else if (ptr[0]) rc = arx_greater_f64_array_scalar(ptr[0], sc[1], n, dout, st);
-    else rc = arx_greater_f64_scalar_array(sc[0], ptr[1], n, dout, st);
-    ARROW_RETURN_NOT_OK(FromArx(rc));
-    // validity = intersection of the inputs' validity bitmaps, re-based to offset 0
-    const ArxSpan* with_nulls[2];
-    int nv = 0;
-    for (int i = 0; i < 2; ++i) {
-      if (ptr[i] && sp[i].validity != nullptr) with_nulls[nv++] = &sp[i];
-    }
-    out_arr->buffers[0] = nullptr;
-    out_arr->null_count = 0;
-    if (nv > 0 && n > 0) {
-      ARROW_ASSIGN_OR_RAISE(out_arr->buffers[0], AllocDevice(((n + 63) / 64) * 8));
-      void* dv = reinterpret_cast<void*>(out_arr->buffers[0]->mutable_address());
-      if (nv == 1) {
-        ARROW_RETURN_NOT_OK(FromArx(arx_bitmap_copy(with_nulls[0]->validity, with_nulls[0]->offset, n, dv, st)));
-      } else {
-        ARROW_RETURN_NOT_OK(FromArx(arx_bitmap_and(with_nulls[0]->validity, with_nulls[0]->offset,
-                                                   with_nulls[1]->validity, with_nulls[1]->offset, n, dv, st)));
-      }
-      ARROW_ASSIGN_OR_RAISE(out_arr->null_count, DeviceNullCount(*out_arr->buffers[0], n, st));
-    }
-    HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
-    CountGpu(kFnGreater);
-    return Status::OK();
-  }
+//  * device-resident operands (arrays, or one scalar): the operation, the validity intersection and the null count all
+//    run on the MI355X and the result stays in HBM (so compare -> filter chains never leave the device);
+//  * host operands get exactly the buffers the ScalarExecutor would have preallocated and then go to Arrow's stock
+//    kernel (these element-wise ops are PCIe-bound for host data).
+// NUM = ARX_NUM_*: the library picks the device kernel for the type.  SLOT: one stock-kernel slot per (function, type).
+// FN: the arrow_amd_plugin_calls counter the Op reports under.
+StockKernel g_stock_compare[6 * 10];
+StockKernel g_stock_arith[6 * 10];
+StockKernel g_stock_divide[2 * 10];
 
-  // ---- host inputs: what ScalarExecutor::PrepareOutput + PropagateNulls would have done
-  arrow::MemoryPool* pool = ctx->memory_pool();
-  ARROW_ASSIGN_OR_RAISE(std::shared_ptr<Buffer> data, ctx->AllocateBitmap(n));
-  std::shared_ptr<Buffer> validity;
-  int64_t null_count = 0;
-  bool null_scalar = false;
-  const ArraySpan* with_nulls[2];
-  int nv = 0;
-  for (int i = 0; i < 2; ++i) {
-    if (batch[i].is_scalar()) {
-      null_scalar = null_scalar || !batch[i].scalar->is_valid;
-    } else if (batch[i].array.MayHaveNulls()) {
-      with_nulls[nv++] = &batch[i].array;
-    }
-  }
-  if (null_scalar) {
-    ARROW_ASSIGN_OR_RAISE(validity, ctx->AllocateBitmap(n));  // zero-initialised: every slot null
-    null_count = n;
-  } else if (nv == 1) {
-    ARROW_ASSIGN_OR_RAISE(validity, arrow::internal::CopyBitmap(pool, with_nulls[0]->buffers[0].data,
-                                                                with_nulls[0]->offset, n));
-    null_count = with_nulls[0]->null_count;  // may be kUnknownNullCount
-  } else if (nv == 2) {
-    ARROW_ASSIGN_OR_RAISE(validity, arrow::internal::BitmapAnd(pool, with_nulls[0]->buffers[0].data,
-                                                               with_nulls[0]->offset, with_nulls[1]->buffers[0].data,
-                                                               with_nulls[1]->offset, n, 0));
-    null_count = arrow::kUnknownNullCount;
-  }
-  cp::ExecResult tmp;
-  ArraySpan span;
-  span.type = out_arr->type.get();
-  span.length = n;
-  span.offset = 0;
-  span.null_count = null_count;
-  if (validity) {
-    span.buffers[0].data = validity->mutable_data();
-    span.buffers[0].size = validity->size();
-  }
-  span.buffers[1].data = data->mutable_data();
-  span.buffers[1].size = data->size();
-  tmp.value = std::move(span);
-  ARROW_RETURN_NOT_OK(GreaterExec(ctx, batch, &tmp));
-  out_arr->buffers[0] = std::move(validity);
-  out_arr->buffers[1] = std::move(data);
-  out_arr->null_count = null_count;
-  return Status::OK();
-}
+// "greater" on int64 / double has a counter of its own (it predates the family; the benchmark's greater leg reads it),
+// every other comparison reports under "compare"
+template <typename CT, int CMP>
+constexpr Fn kCompareFn = CMP == ARX_CMP_GREATER && (std::is_same<CT, int64_t>::value || std::is_same<CT, double>::value)
+                              ? kFnGreater : kFnCompare;
 
-// ---------------------------------------------------------------- greater(int64), add(int64|double)
-// The same NO_PREALLOCATE twin as GreaterExecNP, generic over the operation: device-resident
-// operands (arrays, or one valid scalar) run on the MI355X and the result stays in HBM; host
-// operands get exactly the buffers the ScalarExecutor would have preallocated and then go to
-// Arrow's stock kernel (these element-wise ops are PCIe-bound for host data).
-StockKernel g_stock_greater_i64, g_stock_add_i64, g_stock_add_f64;
-
-struct OpGreaterI64 {
-  static constexpr bool kChecked = false;
-  using T = int64_t;
-  using ScalarT = arrow::Int64Scalar;
-  static constexpr bool kBitmapOut = true;
-  static constexpr Fn kFn = kFnGreater;
-  static StockKernel& stock() { return g_stock_greater_i64; }
-  static int aa(const T* l, const T* r, int64_t n, void* o, hipStream_t st) { return arx_greater_i64(l, r, n, static_cast<uint64_t*>(o), st); }
-  static int as(const T* l, T r, int64_t n, void* o, hipStream_t st) { return arx_greater_i64_array_scalar(l, r, n, static_cast<uint64_t*>(o), st); }
-  static int sa(T l, const T* r, int64_t n, void* o, hipStream_t st) { return arx_greater_i64_scalar_array(l, r, n, static_cast<uint64_t*>(o), st); }
-};
-struct OpAddI64 {
-  static constexpr bool kChecked = false;
-  using T = int64_t;
-  using ScalarT = arrow::Int64Scalar;
-  static constexpr bool kBitmapOut = false;
-  static constexpr Fn kFn = kFnAdd;
-  static StockKernel& stock() { return g_stock_add_i64; }
-  static int aa(const T* l, const T* r, int64_t n, void* o, hipStream_t st) { return arx_add_i64(l, r, n, static_cast<T*>(o), st); }
-  static int as(const T* l, T r, int64_t n, void* o, hipStream_t st) { return arx_add_i64_array_scalar(l, r, n, static_cast<T*>(o), st); }
-  static int sa(T l, const T* r, int64_t n, void* o, hipStream_t st) { return arx_add_i64_array_scalar(r, l, n, static_cast<T*>(o), st); }
-};
-struct OpAddF64 {
-  static constexpr bool kChecked = false;
-  using T = double;
-  using ScalarT = arrow::DoubleScalar;
-  static constexpr bool kBitmapOut = false;
-  static constexpr Fn kFn = kFnAdd;
-  static StockKernel& stock() { return g_stock_add_f64; }
-  static int aa(const T* l, const T* r, int64_t n, void* o, hipStream_t st) { return arx_add_f64(l, r, n, static_cast<T*>(o), st); }
-  static int as(const T* l, T r, int64_t n, void* o, hipStream_t st) { return arx_add_f64_array_scalar(l, r, n, static_cast<T*>(o), st); }
-  static int sa(T l, const T* r, int64_t n, void* o, hipStream_t st) { return arx_add_f64_array_scalar(r, l, n, static_cast<T*>(o), st); }
-};
-
-// equal / not_equal / greater_equal / less / less_equal for int64 and double (greater has its own
-// entries above): one stock-kernel slot per (function, type)
-StockKernel g_stock_compare[12];
-
-template <typename CT, typename ScalarType, int CMP, int SLOT>
+template <typename CT, typename ScalarType, int NUM, int CMP, int SLOT, Fn FN = kCompareFn<CT, CMP>>
 struct OpCompare {
   using T = CT;
   using ScalarT = ScalarType;
   static constexpr bool kBitmapOut = true;
   static constexpr bool kChecked = false;
-  static constexpr Fn kFn = kFnCompare;
+  static constexpr Fn kFn = FN;
+  // greater(double, double) on large HOST arrays is staged through HBM (StagedHostCompare) instead of going to the stock kernel
+  static constexpr bool kStageHostArrays = CMP == ARX_CMP_GREATER && std::is_same<CT, double>::value;
   static StockKernel& stock() { return g_stock_compare[SLOT]; }
-  static int run(const T* l, T ls, const T* r, T rs, int64_t n, void* o, hipStream_t st) {
-    if constexpr (std::is_same<T, double>::value) {
-      return arx_compare_f64(CMP, l, ls, r, rs, n, static_cast<uint64_t*>(o), st);
-    } else {
-      return arx_compare_i64(CMP, l, ls, r, rs, n, static_cast<uint64_t*>(o), st);
-    }
-  }
-  static int aa(const T* l, const T* r, int64_t n, void* o, hipStream_t st) { return run(l, T(0), r, T(0), n, o, st); }
-  static int as(const T* l, T r, int64_t n, void* o, hipStream_t st) { return run(l, T(0), nullptr, r, n, o, st); }
-  static int sa(T l, const T* r, int64_t n, void* o, hipStream_t st) { return run(nullptr, l, r, T(0), n, o, st); }
-};
-
-// subtract / multiply and add_checked / subtract_checked / multiply_checked (int64, double): what
-// `+`, `-`, `*` on pyarrow / Acero expressions mean.  The checked int64 forms read an overflow flag
-// back after the kernel and fail with the reference's Status::Invalid("overflow").
-StockKernel g_stock_arith[10];
-
-template <typename CT, typename ScalarType, int OP, bool CHECKED, int SLOT>
-struct OpArith {
-  using T = CT;
-  using ScalarT = ScalarType;
-  static constexpr bool kBitmapOut = false;
-  static constexpr bool kChecked = CHECKED && std::is_same<CT, int64_t>::value;
-  static constexpr Fn kFn = kFnAdd;
-  static StockKernel& stock() { return g_stock_arith[SLOT]; }
-  static int run(const T* l, T ls, const T* r, T rs, int64_t n, void* o, hipStream_t st) {
-    if constexpr (std::is_same<T, double>::value) {
-      return arx_arith_f64(OP, l, ls, r, rs, n, static_cast<double*>(o), st);
-    } else {
-      return arx_arith_i64(OP, l, ls, r, rs, n, static_cast<int64_t*>(o), st);
-    }
-  }
-  static int aa(const T* l, const T* r, int64_t n, void* o, hipStream_t st) { return run(l, T(0), r, T(0), n, o, st); }
-  static int as(const T* l, T r, int64_t n, void* o, hipStream_t st) { return run(l, T(0), nullptr, r, n, o, st); }
-  static int sa(T l, const T* r, int64_t n, void* o, hipStream_t st) { return run(nullptr, l, r, T(0), n, o, st); }
-  static int checked(const T* l, T ls, const ArxSpan& lsp, const T* r, T rs, const ArxSpan& rsp, int64_t n, void* o,
-                     unsigned int* flag, hipStream_t st) {
-    if constexpr (std::is_same<T, int64_t>::value) {
-      return arx_arith_checked_i64(OP, l, ls, l ? lsp.validity : nullptr, lsp.offset, r, rs,
-                                   r ? rsp.validity : nullptr, rsp.offset, n, static_cast<int64_t*>(o), flag, st);
-    } else {
-      return ARX_NOT_IMPLEMENTED;
-    }
-  }
-};
-
-// The same two families for the other numeric element types (int8 ... uint32, uint64, float): arx_compare_numeric /
-// arx_arith_numeric (one kernel template per type).  NUM = ARX_NUM_*; one stock-kernel slot per (function, type).
-StockKernel g_stock_compare_num[6 * 8];
-StockKernel g_stock_arith_num[6 * 8];
-
-template <typename CT, typename ScalarType, int NUM, int CMP, int SLOT>
-struct OpCompareNum {
-  using T = CT;
-  using ScalarT = ScalarType;
-  static constexpr bool kBitmapOut = true;
-  static constexpr bool kChecked = false;
-  static constexpr Fn kFn = kFnCompare;
-  static StockKernel& stock() { return g_stock_compare_num[SLOT]; }
   static int run(const T* l, T ls, const T* r, T rs, int64_t n, void* o, hipStream_t st) {
     return arx_compare_numeric(CMP, NUM, l, &ls, r, &rs, n, static_cast<uint64_t*>(o), st);
   }
@@ -267,14 +39,17 @@ struct OpCompareNum {
   static int sa(T l, const T* r, int64_t n, void* o, hipStream_t st) { return run(nullptr, l, r, T(0), n, o, st); }
 };
 
+// add / subtract / multiply and add_checked / subtract_checked / multiply_checked: what `+`, `-`, `*` on pyarrow /
+// Acero expressions mean.  The checked integer forms read an overflow flag back after the kernel and fail with the
+// reference's Status::Invalid("overflow").
 template <typename CT, typename ScalarType, int NUM, int OP, bool CHECKED, int SLOT>
-struct OpArithNum {
+struct OpArith {
   using T = CT;
   using ScalarT = ScalarType;
   static constexpr bool kBitmapOut = false;
   static constexpr bool kChecked = CHECKED && std::is_integral<CT>::value;
   static constexpr Fn kFn = kFnAdd;
-  static StockKernel& stock() { return g_stock_arith_num[SLOT]; }
+  static StockKernel& stock() { return g_stock_arith[SLOT]; }
   static int run(const T* l, T ls, const T* r, T rs, int64_t n, void* o, hipStream_t st) {
     return arx_arith_numeric(OP, 0, NUM, l, &ls, nullptr, 0, r, &rs, nullptr, 0, n, o, nullptr, st);
   }
@@ -295,7 +70,7 @@ struct OpArithNum {
 StockKernel g_stock_compare_temporal[6 * 14];
 
 template <typename CT, typename ScalarType, int NUM, int CMP, int SLOT>
-struct OpCompareTemporal : OpCompareNum<CT, ScalarType, NUM, CMP, SLOT> {
+struct OpCompareTemporal : OpCompare<CT, ScalarType, NUM, CMP, SLOT, kFnCompare> {
   static StockKernel& stock() { return g_stock_compare_temporal[SLOT]; }
   static constexpr bool kTemporal = true;
   // less / less_equal are greater / greater_equal with the operands swapped in the reference (scalar_compare.cc:436-445):
@@ -307,12 +82,10 @@ struct IsTemporalOp : std::false_type {};
 template <class Op>
 struct IsTemporalOp<Op, std::void_t<decltype(Op::kTemporal)>> : std::true_type {};
 
-// divide / divide_checked (int64, double): Divide / DivideChecked, base_arithmetic_internal.h:366-424.  Both forms can
-// fail ("divide by zero"; the checked one also "overflow" for INT64_MIN / -1): the kernel leaves the last failing row
-// of each kind in two device words, the larger one names the Status (the reference overwrites it slot by slot).
-StockKernel g_stock_divide[4];
-
-template <typename CT, typename ScalarType, bool CHECKED, int SLOT>
+// divide / divide_checked: Divide / DivideChecked, base_arithmetic_internal.h:366-424.  Both forms can fail ("divide by
+// zero"; the checked one also "overflow" for min / -1 of a signed type): the kernel leaves the last failing row of each
+// kind in two device words, the larger one names the Status (the reference overwrites it slot by slot).
+template <typename CT, typename ScalarType, int NUM, bool CHECKED, int SLOT>
 struct OpDivide {
   using T = CT;
   using ScalarT = ScalarType;
@@ -326,32 +99,6 @@ struct OpDivide {
   static int sa(T, const T*, int64_t, void*, hipStream_t) { return ARX_NOT_IMPLEMENTED; }
   static int divide(const T* l, T ls, const ArxSpan& lsp, const T* r, T rs, const ArxSpan& rsp, int64_t n, void* o,
                     uint64_t* errors, hipStream_t st) {
-    if constexpr (std::is_same<T, int64_t>::value) {
-      return arx_divide_i64(l, ls, l ? lsp.validity : nullptr, lsp.offset, r, rs, r ? rsp.validity : nullptr, rsp.offset, n,
-                            CHECKED ? 1 : 0, static_cast<int64_t*>(o), errors, st);
-    } else {
-      return arx_divide_f64(l, ls, l ? lsp.validity : nullptr, lsp.offset, r, rs, r ? rsp.validity : nullptr, rsp.offset, n,
-                            CHECKED ? 1 : 0, static_cast<double*>(o), errors, st);
-    }
-  }
-};
-// divide / divide_checked for the other numeric element types (int8 ... uint32, uint64, float): arx_divide_numeric
-StockKernel g_stock_divide_num[2 * 8];
-
-template <typename CT, typename ScalarType, int NUM, bool CHECKED, int SLOT>
-struct OpDivideNum {
-  using T = CT;
-  using ScalarT = ScalarType;
-  static constexpr bool kBitmapOut = false;
-  static constexpr bool kChecked = false;
-  static constexpr bool kDivideChecked = CHECKED;
-  static constexpr Fn kFn = kFnAdd;
-  static StockKernel& stock() { return g_stock_divide_num[SLOT]; }
-  static int aa(const T*, const T*, int64_t, void*, hipStream_t) { return ARX_NOT_IMPLEMENTED; }
-  static int as(const T*, T, int64_t, void*, hipStream_t) { return ARX_NOT_IMPLEMENTED; }
-  static int sa(T, const T*, int64_t, void*, hipStream_t) { return ARX_NOT_IMPLEMENTED; }
-  static int divide(const T* l, T ls, const ArxSpan& lsp, const T* r, T rs, const ArxSpan& rsp, int64_t n, void* o,
-                    uint64_t* errors, hipStream_t st) {
     return arx_divide_numeric(CHECKED ? 1 : 0, NUM, l, &ls, l ? lsp.validity : nullptr, lsp.offset, r, &rs,
                               r ? rsp.validity : nullptr, rsp.offset, n, o, errors, st);
   }
@@ -360,6 +107,44 @@ template <class Op, class = void>
 struct IsDivideOp : std::false_type {};
 template <class Op>
 struct IsDivideOp<Op, std::void_t<decltype(Op::kDivideChecked)>> : std::true_type {};
+
+template <class Op, class = void>
+struct StagesHostArrays : std::false_type {};
+template <class Op>
+struct StagesHostArrays<Op, std::void_t<decltype(Op::kStageHostArrays)>> : std::bool_constant<Op::kStageHostArrays> {};
+
+// The host half of an Op with kStageHostArrays: two host arrays of at least g_min_rows_streaming rows are copied to HBM,
+// compared there and the bitmap copied back into the preallocated output (counted as a GPU call); scalars and small
+// inputs go to Arrow's stock kernel.  Validity has been propagated by the caller.
+template <class Op>
+Status StagedHostCompare(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecResult* out) {
+  using T = typename Op::T;
+  if (!batch[0].is_array() || !batch[1].is_array() || !out->is_array_span() ||
+      out->array_span()->offset != 0 || batch.length < g_min_rows_streaming.load() ||
+      !IsHost(batch[0].array) || !IsHost(batch[1].array)) {
+    CountStock(Op::kFn);
+    return Op::stock().exec(ctx, batch, out);
+  }
+  const ArraySpan& l = batch[0].array;
+  const ArraySpan& r = batch[1].array;
+  const int64_t n = batch.length;
+  const size_t bytes = static_cast<size_t>(n) * sizeof(T);
+  hipStream_t st;
+  ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
+  void *dl = nullptr, *dr = nullptr, *dout = nullptr;
+  ARROW_RETURN_NOT_OK(t_scratch.Get(kValues, bytes, &dl));
+  ARROW_RETURN_NOT_OK(t_scratch.Get(kArg2, bytes, &dr));
+  ARROW_RETURN_NOT_OK(t_scratch.Get(kOutData, static_cast<size_t>((n + 63) / 64) * 8, &dout));
+  HIP_RETURN_NOT_OK(hipMemcpyAsync(dl, l.GetValues<T>(1), bytes, hipMemcpyHostToDevice, st));
+  HIP_RETURN_NOT_OK(hipMemcpyAsync(dr, r.GetValues<T>(1), bytes, hipMemcpyHostToDevice, st));
+  ARROW_RETURN_NOT_OK(FromArx(Op::aa(static_cast<const T*>(dl), static_cast<const T*>(dr), n, dout, st)));
+  ArraySpan* o = out->array_span_mutable();
+  HIP_RETURN_NOT_OK(hipMemcpyAsync(o->buffers[1].data, dout, static_cast<size_t>(arrow::bit_util::BytesForBits(n)),
+                                   hipMemcpyDeviceToHost, st));
+  HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
+  CountGpu(Op::kFn);
+  return Status::OK();
+}
 
 template <class Op>
 Status ScalarBinaryNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecResult* out) {
@@ -473,7 +258,7 @@ Status ScalarBinaryNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::Exe
     return Status::OK();
   }
 
-  // ---- host operands: ScalarExecutor::PrepareOutput + PropagateNulls, then Arrow's stock kernel
+  // ---- host operands: ScalarExecutor::PrepareOutput + PropagateNulls, then Arrow's stock kernel (or the Op's staging)
   arrow::MemoryPool* pool = ctx->memory_pool();
   std::shared_ptr<Buffer> data;
   if (Op::kBitmapOut) {
@@ -519,8 +304,12 @@ Status ScalarBinaryNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::Exe
   span.buffers[1].data = data->mutable_data();
   span.buffers[1].size = data->size();
   tmp.value = std::move(span);
-  CountStock(Op::kFn);
-  ARROW_RETURN_NOT_OK(Op::stock().exec(ctx, batch, &tmp));
+  if constexpr (StagesHostArrays<Op>::value) {
+    ARROW_RETURN_NOT_OK(StagedHostCompare<Op>(ctx, batch, &tmp));
+  } else {
+    CountStock(Op::kFn);
+    ARROW_RETURN_NOT_OK(Op::stock().exec(ctx, batch, &tmp));
+  }
   out_arr->buffers[0] = std::move(validity);
   out_arr->buffers[1] = std::move(data);
   out_arr->null_count = null_count;

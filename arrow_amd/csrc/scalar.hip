@@ -636,6 +636,14 @@ __global__ __launch_bounds__(kBlock) void popcount_kernel(Bits a, int64_t nwords
   }
 }
 
+// ------------------------------------------------------------------ host-side launchers
+// The element types with kernels of their own: greater_kernel / add_kernel load 16-byte pairs of 64-bit values, and the
+// casts double -> float, int64 -> int32 | double, int32 -> int64 have dedicated kernels.  Which kernel a call of the
+// arx_*_numeric entry points gets is decided in this file, at compile time per element type (`if constexpr`), so the
+// generic kernels are not even instantiated for the types that never reach them.
+template <typename T>
+constexpr bool kPairKernels = std::is_same<T, int64_t>::value || std::is_same<T, double>::value;
+
 template <typename T, int LK, int RK, int CMP = ARX_CMP_GREATER>
 static int launch_greater(const T* left, T ls, const T* right, T rs, int64_t n, uint64_t* out,
                           hipStream_t st) {
@@ -738,7 +746,17 @@ static int arith_any(int op, const T* left, T ls, const T* right, T rs, const Bi
   }
   if (n == 0) return ARX_OK;
   switch (op) {
-    case ARX_ARITH_ADD: return arith_shapes<T, ARX_ARITH_ADD, CHECKED>(left, ls, right, rs, lv, rv, n, out, overflow, st);
+    case ARX_ARITH_ADD:
+      if constexpr (!CHECKED && kPairKernels<T>) {
+        // the pair-loading add_kernel; scalar + array is array + scalar with the operands swapped (add commutes)
+        if (left != nullptr && right != nullptr) return launch_add<T, false>(left, right, T(0), n, out, st);
+        if (left != nullptr) return launch_add<T, true>(left, nullptr, rs, n, out, st);
+        if (right != nullptr) return launch_add<T, true>(right, nullptr, ls, n, out, st);
+        set_error("arithmetic: at least one operand must be an array");
+        return ARX_INVALID;
+      } else {
+        return arith_shapes<T, ARX_ARITH_ADD, CHECKED>(left, ls, right, rs, lv, rv, n, out, overflow, st);
+      }
     case ARX_ARITH_SUBTRACT: return arith_shapes<T, ARX_ARITH_SUBTRACT, CHECKED>(left, ls, right, rs, lv, rv, n, out, overflow, st);
     case ARX_ARITH_MULTIPLY: return arith_shapes<T, ARX_ARITH_MULTIPLY, CHECKED>(left, ls, right, rs, lv, rv, n, out, overflow, st);
     default:
@@ -831,11 +849,12 @@ __global__ __launch_bounds__(kBlock) void bitmap_copy_segments_kernel(const ArxB
 }
 
 // ------------------------------------------------------------------ compare / arithmetic on every numeric type
-// The comparison family and add / subtract / multiply (+ _checked) for the element types the 64-bit kernels above do
-// not take (int8 ... uint32, uint64, float): the same Call bodies (scalar_compare.cc:38-64,
-// base_arithmetic_internal.h:45-150,290-364) instantiated per type — unchecked integer results wrap in the type's
-// width, the checked forms report an overflow of THAT type (only where both operands are valid).
-// One lane per row and step, U steps in flight: a wave reads 64 * sizeof(T) contiguous bytes per load.
+// The comparison family and add / subtract / multiply (+ _checked) for every numeric element type: the same Call bodies
+// (scalar_compare.cc:38-64, base_arithmetic_internal.h:45-150,290-364) instantiated per type — unchecked integer results
+// wrap in the type's width, the checked forms report an overflow of THAT type (only where both operands are valid).
+// int64 and double run the pair-loading kernels (kPairKernels: greater_kernel, add_kernel, the 64-bit casts), the other
+// eight types the one-lane-per-row kernels below (a wave reads 64 * sizeof(T) contiguous bytes per load, U steps in
+// flight).
 template <typename T, int LK, int RK, int CMP>
 __global__ __launch_bounds__(kBlock) void compare_rows_kernel(const T* __restrict__ left, T lscalar,
                                                               const T* __restrict__ right, T rscalar, int64_t n,
@@ -884,23 +903,27 @@ static int compare_rows_shapes(const T* left, T ls, const T* right, T rs, int64_
 }
 
 template <typename T>
-static int compare_rows_any(int op, const void* left, const void* lsp, const void* right, const void* rsp, int64_t n,
-                            uint64_t* out, hipStream_t st) {
+static int compare_numeric_any(int op, const void* left, const void* lsp, const void* right, const void* rsp, int64_t n,
+                               uint64_t* out, hipStream_t st) {
   const T* l = static_cast<const T*>(left);
   const T* r = static_cast<const T*>(right);
   T ls = T(0), rs = T(0);
   if (l == nullptr && lsp != nullptr) memcpy(&ls, lsp, sizeof(T));
   if (r == nullptr && rsp != nullptr) memcpy(&rs, rsp, sizeof(T));
-  switch (op) {
-    case ARX_CMP_EQUAL: return compare_rows_shapes<T, ARX_CMP_EQUAL>(l, ls, r, rs, n, out, st);
-    case ARX_CMP_NOT_EQUAL: return compare_rows_shapes<T, ARX_CMP_NOT_EQUAL>(l, ls, r, rs, n, out, st);
-    case ARX_CMP_GREATER: return compare_rows_shapes<T, ARX_CMP_GREATER>(l, ls, r, rs, n, out, st);
-    case ARX_CMP_GREATER_EQUAL: return compare_rows_shapes<T, ARX_CMP_GREATER_EQUAL>(l, ls, r, rs, n, out, st);
-    case ARX_CMP_LESS: return compare_rows_shapes<T, ARX_CMP_GREATER>(r, rs, l, ls, n, out, st);
-    case ARX_CMP_LESS_EQUAL: return compare_rows_shapes<T, ARX_CMP_GREATER_EQUAL>(r, rs, l, ls, n, out, st);
-    default:
-      set_error("unknown compare op %d", op);
-      return ARX_INVALID;
+  if constexpr (kPairKernels<T>) {
+    return compare_any<T>(op, l, ls, r, rs, n, out, st);
+  } else {
+    switch (op) {
+      case ARX_CMP_EQUAL: return compare_rows_shapes<T, ARX_CMP_EQUAL>(l, ls, r, rs, n, out, st);
+      case ARX_CMP_NOT_EQUAL: return compare_rows_shapes<T, ARX_CMP_NOT_EQUAL>(l, ls, r, rs, n, out, st);
+      case ARX_CMP_GREATER: return compare_rows_shapes<T, ARX_CMP_GREATER>(l, ls, r, rs, n, out, st);
+      case ARX_CMP_GREATER_EQUAL: return compare_rows_shapes<T, ARX_CMP_GREATER_EQUAL>(l, ls, r, rs, n, out, st);
+      case ARX_CMP_LESS: return compare_rows_shapes<T, ARX_CMP_GREATER>(r, rs, l, ls, n, out, st);
+      case ARX_CMP_LESS_EQUAL: return compare_rows_shapes<T, ARX_CMP_GREATER_EQUAL>(r, rs, l, ls, n, out, st);
+      default:
+        set_error("unknown compare op %d", op);
+        return ARX_INVALID;
+    }
   }
 }
 
@@ -918,20 +941,16 @@ static int arith_numeric_any(int op, int checked, const void* left, const void* 
   return arith_any<T, false>(op, l, ls, r, rs, lv, rv, n, static_cast<T*>(out), nullptr, st);
 }
 
+// int64 -> int32 | double with the range [lo, hi] checked on the valid slots unless `unchecked` (an unchecked call needs
+// no workspace); arx_cast_numeric has validated the span and `out`
 template <typename OutT>
-static int cast_i64_checked(const char* what, const ArxSpan* values, int unchecked, int64_t lo, int64_t hi, void* ws,
-                            size_t ws_bytes, OutT* out, void* stream) {
-  if (values == nullptr || values->length < 0) {
-    set_error("bad arguments to %s", what);
-    return ARX_INVALID;
-  }
+static int cast_i64_checked(const ArxSpan* values, int unchecked, int64_t lo, int64_t hi, void* ws, size_t ws_bytes,
+                            OutT* out, hipStream_t st) {
   const int64_t n = values->length;
-  if (n == 0) return ARX_OK;
-  if (values->data == nullptr || out == nullptr || (!unchecked && (ws == nullptr || ws_bytes < 8))) {
-    set_error("NULL buffer / workspace passed to %s", what);
+  if (!unchecked && (ws == nullptr || ws_bytes < 8)) {
+    set_error("arx_cast_numeric: a checked cast needs >= 8 bytes of device workspace");
     return ARX_INVALID;
   }
-  hipStream_t st = as_stream(stream);
   const int64_t* in = static_cast<const int64_t*>(values->data) + values->offset;
   const Bits valid = make_bits(values->null_count != 0 ? values->validity : nullptr, values->offset, n);
   unsigned long long* first_bad = static_cast<unsigned long long*>(ws);
@@ -974,7 +993,7 @@ static void format_num(char* buf, size_t cap, T v) {
 }
 
 template <typename InT, typename OutT>
-static int cast_numeric_pair(const ArxSpan* values, int allow_int_overflow, int allow_float_truncate, void* ws,
+static int cast_generic_pair(const ArxSpan* values, int allow_int_overflow, int allow_float_truncate, void* ws,
                              size_t ws_bytes, void* out_v, hipStream_t st) {
   const int64_t n = values->length;
   const InT* in = static_cast<const InT*>(values->data) + values->offset;
@@ -1052,6 +1071,39 @@ static int cast_numeric_pair(const ArxSpan* values, int allow_int_overflow, int 
   return ARX_INVALID;
 }
 
+// One (input, output) pair: the four pairs with kernels of their own, else cast_numeric_kernel.
+template <typename InT, typename OutT>
+static int cast_numeric_pair(const ArxSpan* values, int allow_int_overflow, int allow_float_truncate, void* ws,
+                             size_t ws_bytes, void* out_v, hipStream_t st) {
+  const int64_t n = values->length;
+  const InT* in = static_cast<const InT*>(values->data) + values->offset;
+  OutT* out = static_cast<OutT*>(out_v);
+  if constexpr (std::is_same<InT, double>::value && std::is_same<OutT, float>::value) {
+    // CastFloatingToFloating (scalar_cast_numeric.cc:56-60): neither option applies, every slot is converted
+    const bool aligned = (reinterpret_cast<uint64_t>(in) & 15) == 0 && (reinterpret_cast<uint64_t>(out) & 7) == 0;
+    const unsigned grid = stream_grid(kBlock * 2 * 2, n);
+    if (aligned) {
+      hipLaunchKernelGGL((cast_f64_f32_kernel<true>), dim3(grid), dim3(kBlock), 0, st, in, n, out);
+    } else {
+      hipLaunchKernelGGL((cast_f64_f32_kernel<false>), dim3(grid), dim3(kBlock), 0, st, in, n, out);
+    }
+    ARX_CHECK_LAUNCH("cast_f64_f32_kernel");
+    return ARX_OK;
+  } else if constexpr (std::is_same<InT, int64_t>::value && std::is_same<OutT, int32_t>::value) {
+    return cast_i64_checked<int32_t>(values, allow_int_overflow, INT32_MIN, INT32_MAX, ws, ws_bytes, out, st);
+  } else if constexpr (std::is_same<InT, int64_t>::value && std::is_same<OutT, double>::value) {
+    // whole numbers are exact in a double up to 2^53 (FloatingIntegerBound<double>, scalar_cast_numeric.cc:213-215)
+    return cast_i64_checked<double>(values, allow_float_truncate, -(int64_t(1) << 53), int64_t(1) << 53, ws, ws_bytes, out,
+                                    st);
+  } else if constexpr (std::is_same<InT, int32_t>::value && std::is_same<OutT, int64_t>::value) {
+    hipLaunchKernelGGL(cast_i32_i64_kernel, dim3(stream_grid(kBlock, n)), dim3(kBlock), 0, st, in, n, out);
+    ARX_CHECK_LAUNCH("cast_i32_i64_kernel");
+    return ARX_OK;
+  } else {
+    return cast_generic_pair<InT, OutT>(values, allow_int_overflow, allow_float_truncate, ws, ws_bytes, out_v, st);
+  }
+}
+
 template <typename InT>
 static int cast_numeric_from(int out_type, const ArxSpan* values, int aio, int aft, void* ws, size_t ws_bytes, void* out,
                              hipStream_t st) {
@@ -1104,106 +1156,6 @@ int arx_cast_numeric(const ArxSpan* values, int in_type, int out_type, int allow
   }
 }
 
-int arx_cast_f64_f32(const double* in, int64_t length, float* out, void* stream) {
-  if (length < 0 || (length > 0 && (in == nullptr || out == nullptr))) {
-    set_error("bad arguments to arx_cast_f64_f32");
-    return ARX_INVALID;
-  }
-  if (length == 0) return ARX_OK;
-  hipStream_t st = as_stream(stream);
-  const bool aligned =
-      (reinterpret_cast<uint64_t>(in) & 15) == 0 && (reinterpret_cast<uint64_t>(out) & 7) == 0;
-  const unsigned grid = stream_grid(kBlock * 2 * 2, length);
-  if (aligned) {
-    hipLaunchKernelGGL((cast_f64_f32_kernel<true>), dim3(grid), dim3(kBlock), 0, st, in, length, out);
-  } else {
-    hipLaunchKernelGGL((cast_f64_f32_kernel<false>), dim3(grid), dim3(kBlock), 0, st, in, length, out);
-  }
-  ARX_CHECK_LAUNCH("cast_f64_f32_kernel");
-  return ARX_OK;
-}
-
-int arx_cast_i64_i32(const ArxSpan* values, int allow_int_overflow, void* ws, size_t ws_bytes, int32_t* out,
-                     void* stream) {
-  return cast_i64_checked<int32_t>("arx_cast_i64_i32", values, allow_int_overflow, INT32_MIN, INT32_MAX, ws, ws_bytes,
-                                   out, stream);
-}
-
-int arx_cast_i64_f64(const ArxSpan* values, int allow_float_truncate, void* ws, size_t ws_bytes, double* out,
-                     void* stream) {
-  // whole numbers are exact in a double up to 2^53 (FloatingIntegerBound<double>, scalar_cast_numeric.cc:213-215)
-  return cast_i64_checked<double>("arx_cast_i64_f64", values, allow_float_truncate, -(int64_t(1) << 53),
-                                  int64_t(1) << 53, ws, ws_bytes, out, stream);
-}
-
-int arx_cast_i32_i64(const int32_t* values, int64_t length, int64_t* out, void* stream) {
-  if (length < 0 || (length > 0 && (values == nullptr || out == nullptr))) {
-    set_error("bad arguments to arx_cast_i32_i64");
-    return ARX_INVALID;
-  }
-  if (length == 0) return ARX_OK;
-  hipLaunchKernelGGL(cast_i32_i64_kernel, dim3(stream_grid(kBlock, length)), dim3(kBlock), 0, as_stream(stream), values,
-                     length, out);
-  ARX_CHECK_LAUNCH("cast_i32_i64_kernel");
-  return ARX_OK;
-}
-
-int arx_greater_f64(const double* left, const double* right, int64_t length, uint64_t* out_bits,
-                    void* stream) {
-  return launch_greater<double, kArray, kArray>(left, 0.0, right, 0.0, length, out_bits,
-                                                as_stream(stream));
-}
-int arx_greater_f64_array_scalar(const double* left, double right, int64_t length,
-                                 uint64_t* out_bits, void* stream) {
-  return launch_greater<double, kArray, kScalar>(left, 0.0, nullptr, right, length, out_bits,
-                                                 as_stream(stream));
-}
-int arx_greater_f64_scalar_array(double left, const double* right, int64_t length,
-                                 uint64_t* out_bits, void* stream) {
-  return launch_greater<double, kScalar, kArray>(nullptr, left, right, 0.0, length, out_bits,
-                                                 as_stream(stream));
-}
-int arx_greater_i64(const int64_t* left, const int64_t* right, int64_t length, uint64_t* out_bits,
-                    void* stream) {
-  return launch_greater<int64_t, kArray, kArray>(left, 0, right, 0, length, out_bits,
-                                                 as_stream(stream));
-}
-
-int arx_compare_f64(int op, const double* left, double left_scalar, const double* right, double right_scalar,
-                    int64_t length, uint64_t* out_bits, void* stream) {
-  return compare_any<double>(op, left, left_scalar, right, right_scalar, length, out_bits, as_stream(stream));
-}
-int arx_compare_i64(int op, const int64_t* left, int64_t left_scalar, const int64_t* right, int64_t right_scalar,
-                    int64_t length, uint64_t* out_bits, void* stream) {
-  return compare_any<int64_t>(op, left, left_scalar, right, right_scalar, length, out_bits, as_stream(stream));
-}
-
-int arx_arith_i64(int op, const int64_t* left, int64_t left_scalar, const int64_t* right, int64_t right_scalar,
-                  int64_t length, int64_t* out, void* stream) {
-  const Bits none = make_bits(nullptr, 0, length);
-  return arith_any<int64_t, false>(op, left, left_scalar, right, right_scalar, none, none, length, out, nullptr,
-                                   as_stream(stream));
-}
-int arx_arith_f64(int op, const double* left, double left_scalar, const double* right, double right_scalar,
-                  int64_t length, double* out, void* stream) {
-  const Bits none = make_bits(nullptr, 0, length);
-  return arith_any<double, false>(op, left, left_scalar, right, right_scalar, none, none, length, out, nullptr,
-                                  as_stream(stream));
-}
-int arx_arith_checked_i64(int op, const int64_t* left, int64_t left_scalar, const void* left_validity,
-                          int64_t left_offset, const int64_t* right, int64_t right_scalar,
-                          const void* right_validity, int64_t right_offset, int64_t length, int64_t* out,
-                          unsigned int* overflow_flag, void* stream) {
-  if (overflow_flag == nullptr) {
-    set_error("arx_arith_checked_i64: overflow_flag is NULL");
-    return ARX_INVALID;
-  }
-  const Bits lv = make_bits(left_validity, left_offset, length);
-  const Bits rv = make_bits(right_validity, right_offset, length);
-  return arith_any<int64_t, true>(op, left, left_scalar, right, right_scalar, lv, rv, length, out, overflow_flag,
-                                  as_stream(stream));
-}
-
 int arx_copy_segments(const ArxCopySeg* segments, int64_t num_segments, uint64_t max_segment_bytes, void* stream) {
   if (num_segments < 0 || (num_segments > 0 && segments == nullptr)) {
     set_error("bad arguments to arx_copy_segments");
@@ -1252,16 +1204,16 @@ int arx_compare_numeric(int op, int num_type, const void* left, const void* left
   }
   hipStream_t st = as_stream(stream);
   switch (num_type) {
-    case ARX_NUM_INT8: return compare_rows_any<int8_t>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
-    case ARX_NUM_UINT8: return compare_rows_any<uint8_t>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
-    case ARX_NUM_INT16: return compare_rows_any<int16_t>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
-    case ARX_NUM_UINT16: return compare_rows_any<uint16_t>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
-    case ARX_NUM_INT32: return compare_rows_any<int32_t>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
-    case ARX_NUM_UINT32: return compare_rows_any<uint32_t>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
-    case ARX_NUM_INT64: return compare_rows_any<int64_t>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
-    case ARX_NUM_UINT64: return compare_rows_any<uint64_t>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
-    case ARX_NUM_FLOAT32: return compare_rows_any<float>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
-    case ARX_NUM_FLOAT64: return compare_rows_any<double>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
+    case ARX_NUM_INT8: return compare_numeric_any<int8_t>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
+    case ARX_NUM_UINT8: return compare_numeric_any<uint8_t>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
+    case ARX_NUM_INT16: return compare_numeric_any<int16_t>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
+    case ARX_NUM_UINT16: return compare_numeric_any<uint16_t>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
+    case ARX_NUM_INT32: return compare_numeric_any<int32_t>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
+    case ARX_NUM_UINT32: return compare_numeric_any<uint32_t>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
+    case ARX_NUM_INT64: return compare_numeric_any<int64_t>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
+    case ARX_NUM_UINT64: return compare_numeric_any<uint64_t>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
+    case ARX_NUM_FLOAT32: return compare_numeric_any<float>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
+    case ARX_NUM_FLOAT64: return compare_numeric_any<double>(op, left, left_scalar, right, right_scalar, length, out_bits, st);
     default:
       set_error("compare: unknown numeric type %d", num_type);
       return ARX_NOT_IMPLEMENTED;
@@ -1305,19 +1257,6 @@ int arx_arith_numeric(int op, int checked, int num_type, const void* left, const
 #undef ARX_ARITH_T
 }
 
-int arx_divide_i64(const int64_t* left, int64_t left_scalar, const void* left_validity, int64_t left_offset,
-                   const int64_t* right, int64_t right_scalar, const void* right_validity, int64_t right_offset,
-                   int64_t length, int checked, int64_t* out, uint64_t* errors, void* stream) {
-  return divide_any<int64_t>(left, left_scalar, left_validity, left_offset, right, right_scalar, right_validity,
-                             right_offset, length, checked, out, errors, as_stream(stream));
-}
-int arx_divide_f64(const double* left, double left_scalar, const void* left_validity, int64_t left_offset,
-                   const double* right, double right_scalar, const void* right_validity, int64_t right_offset,
-                   int64_t length, int checked, double* out, uint64_t* errors, void* stream) {
-  return divide_any<double>(left, left_scalar, left_validity, left_offset, right, right_scalar, right_validity,
-                            right_offset, length, checked, out, errors, as_stream(stream));
-}
-
 int arx_divide_numeric(int checked, int num_type, const void* left, const void* left_scalar, const void* left_validity,
                        int64_t left_offset, const void* right, const void* right_scalar, const void* right_validity,
                        int64_t right_offset, int64_t length, void* out, uint64_t* errors, void* stream) {
@@ -1346,30 +1285,6 @@ int arx_divide_numeric(int checked, int num_type, const void* left, const void* 
       return ARX_NOT_IMPLEMENTED;
   }
 #undef ARX_DIVIDE_T
-}
-
-int arx_add_i64(const int64_t* left, const int64_t* right, int64_t length, int64_t* out,
-                void* stream) {
-  return launch_add<int64_t, false>(left, right, 0, length, out, as_stream(stream));
-}
-int arx_add_f64(const double* left, const double* right, int64_t length, double* out,
-                void* stream) {
-  return launch_add<double, false>(left, right, 0.0, length, out, as_stream(stream));
-}
-
-int arx_add_i64_array_scalar(const int64_t* left, int64_t right, int64_t length, int64_t* out, void* stream) {
-  return launch_add<int64_t, true>(left, nullptr, right, length, out, as_stream(stream));
-}
-int arx_add_f64_array_scalar(const double* left, double right, int64_t length, double* out, void* stream) {
-  return launch_add<double, true>(left, nullptr, right, length, out, as_stream(stream));
-}
-int arx_greater_i64_array_scalar(const int64_t* left, int64_t right, int64_t length, uint64_t* out_bits,
-                                 void* stream) {
-  return launch_greater<int64_t, kArray, kScalar>(left, 0, nullptr, right, length, out_bits, as_stream(stream));
-}
-int arx_greater_i64_scalar_array(int64_t left, const int64_t* right, int64_t length, uint64_t* out_bits,
-                                 void* stream) {
-  return launch_greater<int64_t, kScalar, kArray>(nullptr, left, right, 0, length, out_bits, as_stream(stream));
 }
 
 int arx_buffer_copy(const void* src, void* dst, int64_t nbytes, void* stream) {

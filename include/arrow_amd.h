@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define ARX_ABI_VERSION 3
+#define ARX_ABI_VERSION 4
 
 /* arrow::StatusCode twins (cpp/src/arrow/status.h:83-107). */
 typedef enum ArxStatus {
@@ -245,153 +245,79 @@ int arx_large_list_take_data(const ArxBinarySpan* values, int elem_shift, int64_
                              void* stream);
 
 /* ---------------------------------------------------------------------------
- * Cast float64 -> float32 — replaces CastPrimitive<FloatType,DoubleType>::Exec
- * (cpp/src/arrow/compute/kernels/scalar_cast_internal.cc:41-53): every slot is
- * converted (null slots included), IEEE round-to-nearest-even.
- * `in` is pre-offset (points at element 0).
+ * Element-wise kernels on the ten numeric types: cast, the comparison family, add / subtract / multiply
+ * (+ _checked), divide (+ _checked).  One entry point per family; the element type is an argument (ARX_NUM_*).
+ * The library picks the kernel: int64 / double compares, unchecked int64 / double add and the casts
+ * double -> float, int64 -> int32 | double, int32 -> int64 run kernels of their own (16-byte pair loads), every
+ * other (function, type) the per-type generic ones.
  * ------------------------------------------------------------------------- */
-int arx_cast_f64_f32(const double* in, int64_t length, float* out, void* stream);
+enum {
+  ARX_NUM_INT8 = 0, ARX_NUM_UINT8 = 1, ARX_NUM_INT16 = 2, ARX_NUM_UINT16 = 3, ARX_NUM_INT32 = 4, ARX_NUM_UINT32 = 5,
+  ARX_NUM_INT64 = 6, ARX_NUM_UINT64 = 7, ARX_NUM_FLOAT32 = 8, ARX_NUM_FLOAT64 = 9
+};
 
-/* Integer casts — CastIntegerToInteger (cpp/src/arrow/compute/kernels/scalar_cast_numeric.cc:46-54).
- * int64 -> int32: unless allow_int_overflow, the first valid slot (row order) whose value does not fit
- * fails with the reference's text "Integer value V not in range: -2147483648 to 2147483647"
- * (IntegersInRange, util/int_util.cc:594-665; ARX_INVALID, synchronous; ws: >= 8 device bytes);
- * every slot is converted with static_cast either way.  int32 -> int64 widens (asynchronous). */
-int arx_cast_i64_i32(const ArxSpan* values, int allow_int_overflow, void* ws, size_t ws_bytes, int32_t* out,
-                     void* stream);
-int arx_cast_i32_i64(const int32_t* values, int64_t length, int64_t* out, void* stream);
-/* int64 -> float64 — CastIntegerToFloating (scalar_cast_numeric.cc:270-279): unless
- * allow_float_truncate, CheckIntegerFloatTruncateImpl (:218-227) applies the same range check with
- * the bounds -2^53 .. 2^53 ("Integer value V not in range: -9007199254740992 to 9007199254740992"). */
-int arx_cast_i64_f64(const ArxSpan* values, int allow_float_truncate, void* ws, size_t ws_bytes, double* out,
-                     void* stream);
-
-/* Every numeric pair — CastIntegerToInteger / CastFloatingToInteger / CastIntegerToFloating / CastFloatingToFloating
- * (scalar_cast_numeric.cc:46-60, 190-207, 270-279; registration :797-858): all slots go through static_cast
- * (CastNumberToNumberUnsafe), and on the VALID slots
+/* Cast, every numeric pair — CastIntegerToInteger / CastFloatingToInteger / CastIntegerToFloating /
+ * CastFloatingToFloating (scalar_cast_numeric.cc:46-60, 190-207, 270-279; registration :797-858): all slots go through
+ * static_cast (CastNumberToNumberUnsafe, scalar_cast_internal.cc:41-53; null slots included; floating -> floating is
+ * IEEE round-to-nearest-even), and on the VALID slots
  *   integer -> integer, unless allow_int_overflow: IntegersCanFit (util/int_util.cc:795-900) —
- *       "Integer value V not in range: LO to HI" with the bounds GetSafeMinMax derives for the pair;
+ *       "Integer value V not in range: LO to HI" with the bounds GetSafeMinMax derives for the pair
+ *       (int64 -> int32: -2147483648 to 2147483647);
  *   integer -> floating, unless allow_float_truncate: |V| <= 2^24 (float) / 2^53 (double) for the 32/64-bit inputs
- *       the reference checks (:229-268), same message;
+ *       the reference checks (:229-268), same message (int64 -> double: -9007199254740992 to 9007199254740992);
  *   floating -> integer, unless allow_float_truncate: static_cast<In>(out) == in, else
  *       "Float value V was truncated converting to TYPE" (out-of-range values and NaN fail it too).  With
  *       allow_float_truncate an out-of-range value converts to an unspecified integer (undefined behaviour in the
  *       reference as well).
  * The first offender in row order names the error (ARX_INVALID; synchronous when a check applies, ws >= 8 device
- * bytes).  in_type / out_type: ARX_NUM_*. */
-enum {
-  ARX_NUM_INT8 = 0, ARX_NUM_UINT8 = 1, ARX_NUM_INT16 = 2, ARX_NUM_UINT16 = 3, ARX_NUM_INT32 = 4, ARX_NUM_UINT32 = 5,
-  ARX_NUM_INT64 = 6, ARX_NUM_UINT64 = 7, ARX_NUM_FLOAT32 = 8, ARX_NUM_FLOAT64 = 9
-};
+ * bytes; a cast no check applies to is asynchronous and needs no workspace).  in_type / out_type: ARX_NUM_*. */
 int arx_cast_numeric(const ArxSpan* values, int in_type, int out_type, int allow_int_overflow, int allow_float_truncate,
                      void* ws, size_t ws_bytes, void* out, void* stream);
 
-/* ---------------------------------------------------------------------------
- * Compare — replaces ComparePrimitiveArrayArray/ArrayScalar/ScalarArray<DoubleType,
- * Greater> (cpp/src/arrow/compute/kernels/scalar_compare.cc:165-247): bit i =
- * left[i] > right[i] (any NaN -> 0), LSB-first, computed on all slots.
- * Pointers are pre-offset.  out_bits: ceil(length/64) 64-bit words.
- * ------------------------------------------------------------------------- */
-int arx_greater_f64(const double* left, const double* right, int64_t length,
-                    uint64_t* out_bits, void* stream);
-int arx_greater_f64_array_scalar(const double* left, double right, int64_t length,
-                                 uint64_t* out_bits, void* stream);
-int arx_greater_f64_scalar_array(double left, const double* right, int64_t length,
-                                 uint64_t* out_bits, void* stream);
-int arx_greater_i64(const int64_t* left, const int64_t* right, int64_t length,
-                    uint64_t* out_bits, void* stream);
-int arx_greater_i64_array_scalar(const int64_t* left, int64_t right, int64_t length,
-                                 uint64_t* out_bits, void* stream);
-int arx_greater_i64_scalar_array(int64_t left, const int64_t* right, int64_t length,
-                                 uint64_t* out_bits, void* stream);
-
-/* The whole comparison family — equal, not_equal, greater, greater_equal, less, less_equal
- * (Equal ... LessEqual, cpp/src/arrow/compute/kernels/scalar_compare.cc:38-64; less / less_equal
- * are registered there as the flipped greater / greater_equal, :436-445, and run here the same
- * way).  left / right: pre-offset arrays, or NULL for "this side is the scalar" (then *_scalar is
- * its value).  Floats: IEEE — NaN makes every ordered comparison and equal false, not_equal true. */
+/* The comparison family — equal, not_equal, greater, greater_equal, less, less_equal (Equal ... LessEqual,
+ * cpp/src/arrow/compute/kernels/scalar_compare.cc:38-64, ComparePrimitiveArrayArray / ArrayScalar / ScalarArray
+ * :165-247; less / less_equal are registered there as the flipped greater / greater_equal, :436-445, and run here the
+ * same way) for every numeric element type (:398-446).  Bit i of out_bits = left[i] OP right[i], LSB-first, computed on
+ * all slots; out_bits: ceil(length/64) 64-bit words.  Floats: IEEE — NaN makes every ordered comparison and equal false,
+ * not_equal true.
+ * left / right: pre-offset arrays of num_type, or NULL for "this side is the scalar" *left_scalar / *right_scalar (host
+ * pointer to one value of the type); at least one side is an array.  Asynchronous. */
 #define ARX_CMP_EQUAL 0
 #define ARX_CMP_NOT_EQUAL 1
 #define ARX_CMP_GREATER 2
 #define ARX_CMP_GREATER_EQUAL 3
 #define ARX_CMP_LESS 4
 #define ARX_CMP_LESS_EQUAL 5
-int arx_compare_f64(int op, const double* left, double left_scalar, const double* right, double right_scalar,
-                    int64_t length, uint64_t* out_bits, void* stream);
-int arx_compare_i64(int op, const int64_t* left, int64_t left_scalar, const int64_t* right, int64_t right_scalar,
-                    int64_t length, uint64_t* out_bits, void* stream);
+int arx_compare_numeric(int op, int num_type, const void* left, const void* left_scalar, const void* right,
+                        const void* right_scalar, int64_t length, uint64_t* out_bits, void* stream);
 
-/* ---------------------------------------------------------------------------
- * Arithmetic — replaces ScalarBinary<Int64,Int64,Int64,Add> / <Double,...>
- * (cpp/src/arrow/compute/kernels/base_arithmetic_internal.h:45-80,
- * codegen_internal.h:814): unchecked integer add wraps around.
- * ------------------------------------------------------------------------- */
-int arx_add_i64(const int64_t* left, const int64_t* right, int64_t length, int64_t* out,
-                void* stream);
-int arx_add_f64(const double* left, const double* right, int64_t length, double* out,
-                void* stream);
-/* add / subtract / multiply in one entry point (Add, Subtract, Multiply,
- * base_arithmetic_internal.h:45-120,290-330): left / right are pre-offset arrays or NULL for
- * "this side is the scalar".  Integer results wrap. */
+/* add / subtract / multiply and their _checked forms (Add, Subtract, Multiply, AddChecked ...,
+ * base_arithmetic_internal.h:45-120,290-364; ScalarBinary, codegen_internal.h:814) for every numeric element type, as
+ * the reference registers them for all of NumericTypes() (scalar_arithmetic.cc AddArithmeticFunctions); both operands
+ * and the result have num_type.  Unchecked integer results wrap in the type's width (the reference computes them in
+ * the unsigned type, :45-68; int16 / uint16 multiply through uint32, :303-325 — the same bits).
+ * checked != 0 (integer types): the wrapped results are written all the same and *overflow_flag (device uint32,
+ * caller-zeroed) is set if a slot where BOTH operands are valid overflowed the type — the reference visits only those
+ * slots (ScalarBinaryNotNull) and then fails with Status::Invalid("overflow"); the caller reads the flag after the
+ * stream has drained.  left/right_validity: bitmaps (bit offsets) or NULL = all valid.  float / double: IEEE, the
+ * checked functions are the plain ones.  Operands as for arx_compare_numeric.  Asynchronous. */
 #define ARX_ARITH_ADD 0
 #define ARX_ARITH_SUBTRACT 1
 #define ARX_ARITH_MULTIPLY 2
-int arx_arith_i64(int op, const int64_t* left, int64_t left_scalar, const int64_t* right, int64_t right_scalar,
-                  int64_t length, int64_t* out, void* stream);
-int arx_arith_f64(int op, const double* left, double left_scalar, const double* right, double right_scalar,
-                  int64_t length, double* out, void* stream);
-/* add_checked / subtract_checked / multiply_checked(int64) (AddChecked ..., :70-120,341-364): the
- * wrapped results are written like above and *overflow_flag (device uint32, caller-zeroed) is set
- * if a slot where BOTH operands are valid overflowed — the reference visits only those slots
- * (ScalarBinaryNotNull) and then fails with Status::Invalid("overflow"); the caller reads the flag
- * after the stream has drained.  left/right_validity: bitmaps (bit offsets) or NULL = all valid.
- * For doubles the checked functions are the plain ones. */
-int arx_arith_checked_i64(int op, const int64_t* left, int64_t left_scalar, const void* left_validity,
-                          int64_t left_offset, const int64_t* right, int64_t right_scalar,
-                          const void* right_validity, int64_t right_offset, int64_t length, int64_t* out,
-                          unsigned int* overflow_flag, void* stream);
-
-/* The comparison family and add / subtract / multiply (+ _checked) for EVERY numeric element type (num_type:
- * ARX_NUM_*; both operands and, for arithmetic, the result have that type): the same Call bodies as above
- * instantiated per type, as the reference registers them for all of NumericTypes() (scalar_compare.cc:398-446,
- * scalar_arithmetic.cc AddArithmeticFunctions).  Unchecked integer results wrap in the type's width (the reference
- * computes them in the unsigned type, base_arithmetic_internal.h:45-68; int16 / uint16 multiply through uint32,
- * :303-325 — the same bits); the checked forms report an overflow of that type.  float / double: IEEE.
- * left / right == NULL: that operand is the scalar *left_scalar / *right_scalar (host pointer to one value of the type).
- * out_bits / out / overflow_flag / validity as for the 64-bit entry points above.  Asynchronous. */
-int arx_compare_numeric(int op, int num_type, const void* left, const void* left_scalar, const void* right,
-                        const void* right_scalar, int64_t length, uint64_t* out_bits, void* stream);
 int arx_arith_numeric(int op, int checked, int num_type, const void* left, const void* left_scalar,
                       const void* left_validity, int64_t left_offset, const void* right, const void* right_scalar,
                       const void* right_validity, int64_t right_offset, int64_t length, void* out,
                       uint32_t* overflow_flag, void* stream);
-/* divide / divide_checked (Divide, DivideChecked, base_arithmetic_internal.h:366-424), visited only where both
- * operands are valid.  int64: truncating division; a zero divisor fails with "divide by zero" in both forms;
- * INT64_MIN / -1 is 0 unchecked and "overflow" checked.  double: IEEE division, the checked form fails on a zero
- * divisor.  errors: two device uint64 zeroed by the caller; after the stream has drained errors[0] / errors[1] hold
- * 1 + the LAST failing row of the overflow / zero-divisor kind (the reference overwrites its Status on every
- * failing slot, so the larger of the two names the message).  A NULL operand pointer broadcasts its scalar. */
-int arx_divide_i64(const int64_t* left, int64_t left_scalar, const void* left_validity, int64_t left_offset,
-                   const int64_t* right, int64_t right_scalar, const void* right_validity,
-                   int64_t right_offset, int64_t length, int checked, int64_t* out, uint64_t* errors,
-                   void* stream);
-int arx_divide_f64(const double* left, double left_scalar, const void* left_validity, int64_t left_offset,
-                   const double* right, double right_scalar, const void* right_validity,
-                   int64_t right_offset, int64_t length, int checked, double* out, uint64_t* errors,
-                   void* stream);
-/* The same for EVERY numeric element type (num_type: ARX_NUM_*; the reference registers divide / divide_checked for all
- * of NumericTypes(), scalar_arithmetic.cc): the signed integer types fail / give 0 on min / -1 of their own width, the
- * unsigned ones only on a zero divisor (DivideWithOverflowGeneric, util/int_util_overflow.h:124-138), float like double.
- * left / right == NULL: that operand is the scalar *left_scalar / *right_scalar (host pointer to one value of the type). */
+/* divide / divide_checked (Divide, DivideChecked, base_arithmetic_internal.h:366-424) for every numeric element type,
+ * visited only where both operands are valid.  Integers: truncating division; a zero divisor fails with "divide by
+ * zero" in both forms; for the signed types min / -1 of their own width is 0 unchecked and "overflow" checked
+ * (DivideWithOverflowGeneric, util/int_util_overflow.h:124-138).  float / double: IEEE division, the checked form fails
+ * on a zero divisor.  errors: two device uint64 zeroed by the caller; after the stream has drained errors[0] /
+ * errors[1] hold 1 + the LAST failing row of the overflow / zero-divisor kind (the reference overwrites its Status on
+ * every failing slot, so the larger of the two names the message).  Operands as for arx_compare_numeric. */
 int arx_divide_numeric(int checked, int num_type, const void* left, const void* left_scalar, const void* left_validity,
                        int64_t left_offset, const void* right, const void* right_scalar, const void* right_validity,
                        int64_t right_offset, int64_t length, void* out, uint64_t* errors, void* stream);
-/* array + valid scalar (ScalarBinary::ArrayScalar, codegen_internal.h; add commutes, so
- * scalar + array is the same call) */
-int arx_add_i64_array_scalar(const int64_t* left, int64_t right, int64_t length, int64_t* out,
-                             void* stream);
-int arx_add_f64_array_scalar(const double* left, double right, int64_t length, double* out,
-                             void* stream);
 
 /* ---------------------------------------------------------------------------
  * Validity plumbing — what ScalarExecutor's null propagation does on the host

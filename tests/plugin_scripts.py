@@ -4661,6 +4661,52 @@ PARQUET_LISTS_SCRIPT = textwrap.dedent(r"""
     print("PARQUET_LISTS_OK")
 """)
 
+NULL_SCALAR_COMPARE_SCRIPT = textwrap.dedent(r'''
+    import ctypes, os, sys, faulthandler
+    faulthandler.enable()
+    import numpy as np
+    import pyarrow as pa, pyarrow.compute as pc
+    sys.path.insert(0, ROOT)
+    SC = lambda x: max(64, int(x * float(os.environ.get("ARROW_AMD_TEST_SCALE", "1"))))   # sizes shrink for the emulated run
+    if os.environ.get("ARROW_AMD_PLUGIN_EMULATED") == "1":      # CPU tier: the shim on the emulated kernels (tests/emu)
+        from tests.emu.build_plugin_emu import build_plugin
+    else:
+        from arrow_amd.plugin_build import build_plugin
+    lib = ctypes.CDLL(build_plugin())
+    lib.arrow_amd_plugin_last_error.restype = ctypes.c_char_p
+    lib.arrow_amd_plugin_calls.restype = ctypes.c_int64
+    lib.arrow_amd_plugin_calls.argtypes = [ctypes.c_char_p, ctypes.c_int]
+    assert lib.arrow_amd_register() == 0, lib.arrow_amd_plugin_last_error()
+
+    def to_device(arr):
+        c_arr, c_schema, c_dev = (ctypes.create_string_buffer(n) for n in (80, 72, 128))
+        arr._export_to_c(ctypes.addressof(c_arr), ctypes.addressof(c_schema))
+        assert lib.arrow_amd_copy_to_device(c_arr, c_schema, c_dev) == 0, lib.arrow_amd_plugin_last_error()
+        return pa.Array._import_from_c_device(ctypes.addressof(c_dev), arr.type)
+
+    def to_host(darr):
+        c_dev, c_schema, c_arr, c_schema2 = (ctypes.create_string_buffer(n) for n in (128, 72, 80, 72))
+        darr._export_to_c_device(ctypes.addressof(c_dev), ctypes.addressof(c_schema))
+        assert lib.arrow_amd_copy_to_host(c_dev, c_schema, c_arr, c_schema2) == 0, lib.arrow_amd_plugin_last_error()
+        return pa.Array._import_from_c(ctypes.addressof(c_arr), ctypes.addressof(c_schema2))
+
+    rng = np.random.default_rng(47)
+    n = SC(1_000_003)
+    f64 = pa.array(rng.standard_normal(n), mask=rng.random(n) < 0.1)
+    d_f64 = to_device(f64)
+    null = pa.scalar(None, pa.float64())
+    g0 = lib.arrow_amd_plugin_calls(b"greater", 1)
+    for dev_out, host_out in ((pc.greater(d_f64, null), pc.greater(f64, null)), (pc.greater(null, d_f64), pc.greater(null, f64)),
+                              (pc.greater(d_f64.slice(7, n - 13), null), pc.greater(f64.slice(7, n - 13), null))):
+        assert not dev_out.is_cpu                    # the all-null answer stays in HBM like every other result
+        ho = to_host(dev_out)
+        assert ho.type == pa.bool_() and len(ho) == len(host_out) and ho.null_count == len(ho)
+        assert ho.equals(host_out) and ho.null_count == host_out.null_count
+    assert lib.arrow_amd_plugin_calls(b"greater", 1) - g0 == 3      # counted where greater(double) on the device always was
+    print("NULL_SCALAR_COMPARE_OK")
+''')
+
+
 CASES = [
     ('pyarrow_compute_dispatches_to_the_hip_kernels', SCRIPT, 'PLUGIN_OK', 0.04,
      ''),
@@ -4744,4 +4790,6 @@ CASES = [
      "pyarrow.compute's generated wrappers (pc.rank, pc.select_k_unstable, pc.sort_indices, ...) keep the Function objects they find when the module is imported: with arrow_amd_register() called BEFORE `import pyarrow.compute` they bind the replaced MetaFunctions and device-resident arrays go through them by their ordinary spelling; registered later, the replaced functions are reached by name (CallFunction / pc.call_function) — INTEGRATION.md 'Load order'."),
     ('hash_variance_stddev_skew_kurtosis_in_aggregate_rocm', MOMENTS_SCRIPT, 'MOMENTS_OK', 0.004,
      "SURVEY.md 8 (f3): the grouped moments (GroupedStatisticImpl) as two passes over all rows of the node — null exactly where the reference's Finalize leaves a group null (ddof, unbiased skew / kurtosis of too few values, min_count, skip_nulls), values within 1e-11 relative of the reference's per-batch moments merged batch by batch (its own tests compare approximately)."),
+    ('greater_of_a_device_double_array_and_a_null_scalar_is_all_null', NULL_SCALAR_COMPARE_SCRIPT, 'NULL_SCALAR_COMPARE_OK', 0.02,
+     "greater(double, double) on device-resident arrays goes through the same ScalarBinaryNP as every other (function, type): a null scalar operand on either side yields the reference's answer — an all-null boolean array, in HBM — instead of a refusal; equal to pyarrow's result on the host copy."),
 ]

@@ -125,15 +125,21 @@ def test_scalar_kernel_argument_checks(emu_ctx):
     L = emu_ctx._lib
     lib = L.get_lib()
     a, b, out = _buf(800), _buf(800), _buf(800)
-    assert lib.arx_compare_f64(2, None, 0.0, None, 0.0, 100, out.data_ptr(), None) == INVALID          # scalar x scalar
-    assert lib.arx_compare_i64(77, a.data_ptr(), 0, b.data_ptr(), 0, 100, out.data_ptr(), None) == INVALID   # unknown op
-    assert lib.arx_compare_i64(2, a.data_ptr(), 0, b.data_ptr(), 0, 0, None, None) == OK
-    assert lib.arx_arith_i64(9, a.data_ptr(), 0, b.data_ptr(), 0, 100, out.data_ptr(), None) == INVALID
-    assert lib.arx_arith_checked_i64(0, a.data_ptr(), 0, None, 0, b.data_ptr(), 0, None, 0, 100, out.data_ptr(), None, None) == INVALID  # no flag
-    assert lib.arx_cast_f64_f32(None, 10, out.data_ptr(), None) == INVALID
+    I64, F64, F32, I32 = 6, 9, 8, 4                                                                      # ARX_NUM_*
+    zf, zi = C.c_double(0.0), C.c_int64(0)
+    zfp, zip_ = C.addressof(zf), C.addressof(zi)
+    assert lib.arx_compare_numeric(2, F64, None, zfp, None, zfp, 100, out.data_ptr(), None) == INVALID  # scalar x scalar
+    assert lib.arx_compare_numeric(77, I64, a.data_ptr(), zip_, b.data_ptr(), zip_, 100, out.data_ptr(), None) == INVALID   # unknown op
+    assert lib.arx_compare_numeric(2, I64, a.data_ptr(), zip_, b.data_ptr(), zip_, 0, None, None) == OK
+    assert lib.arx_arith_numeric(9, 0, I64, a.data_ptr(), zip_, None, 0, b.data_ptr(), zip_, None, 0, 100, out.data_ptr(), None,
+                                 None) == INVALID                                                       # unknown op
+    assert lib.arx_arith_numeric(0, 1, I64, a.data_ptr(), zip_, None, 0, b.data_ptr(), zip_, None, 0, 100, out.data_ptr(), None,
+                                 None) == INVALID                                                       # checked int64, no flag
+    nodata = L.ArxSpan(None, None, 0, 10, 0)
+    assert lib.arx_cast_numeric(C.byref(nodata), F64, F32, 0, 0, None, 0, out.data_ptr(), None) == INVALID   # NULL input
     sp = _span(L, a, length=100)
-    assert lib.arx_cast_i64_i32(C.byref(sp), 0, None, 0, out.data_ptr(), None) == INVALID               # checked cast needs a workspace
-    assert lib.arx_cast_i64_i32(C.byref(sp), 1, None, 0, out.data_ptr(), None) == OK                    # unchecked does not
+    assert lib.arx_cast_numeric(C.byref(sp), I64, I32, 0, 0, None, 0, out.data_ptr(), None) == INVALID   # checked cast needs a workspace
+    assert lib.arx_cast_numeric(C.byref(sp), I64, I32, 1, 0, None, 0, out.data_ptr(), None) == OK        # unchecked does not
     lm, rm = _span(L, a, length=100), _span(L, b, length=90)
     assert lib.arx_boolean_kleene(0, C.byref(lm), C.byref(rm), out.data_ptr(), None, None) == INVALID   # length mismatch
     rm = _span(L, b, validity=a, length=100, null_count=-1)
