@@ -22,7 +22,7 @@ ARX_INDEX_ERROR = -7
 ARX_NOT_IMPLEMENTED = -10
 ARX_DEVICE_ERROR = -100
 
-ABI_VERSION = 4  # ARX_ABI_VERSION of include/arrow_amd.h
+ABI_VERSION = 5  # ARX_ABI_VERSION of include/arrow_amd.h
 
 FILTER_DROP, FILTER_EMIT_NULL = 0, 1
 SORT_ASCENDING, SORT_DESCENDING = 0, 1
@@ -115,6 +115,7 @@ SIGNATURES = {
     "arx_abi_version": (_int, []),
     "arx_device_count": (_int, []),
     "arx_set_option": (_int, [C.c_char_p, _i64]),
+    "arx_get_option": (_int, [C.c_char_p, C.POINTER(_i64)]),
     "arx_get_counter": (_i64, [C.c_char_p]),
     "arx_filter_workspace_bytes": (_sz, [_i64]),
     "arx_filter_count": (_int, [_span, _int, _p, _sz, C.POINTER(_i64), _p]),

@@ -33,15 +33,56 @@ constexpr int kTilesPerGroup = 64;      // count-kernel workgroup = 64 wave tile
 // ---------------------------------------------------------------------------
 void set_error(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
-// Per-file tuning-knob hooks used by arx_set_option (return 1 if the name was recognised).
-int set_selection_option(const char* name, int64_t value);
-int set_sort_option(const char* name, int64_t value);
-int set_groupby_option(const char* name, int64_t value);
-int set_parquet_option(const char* name, int64_t value);
-// Per-file diagnostic counters read by arx_get_counter (return 1 if the name was recognised).
-int get_groupby_counter(const char* name, int64_t* out);
-int get_sort_counter(const char* name, int64_t* out);
-int get_set_lookup_counter(const char* name, int64_t* out);
+// One row per knob, in a table next to the knobs' definitions in each file (sort.hip, groupby.hip, groupby_lines.h,
+// selection.hip, parquet.hip): the name, the knob and how a given value is normalised before it is stored.  These tables
+// are the authoritative list of names, defaults and ranges; capi.hip walks them for arx_set_option / arx_get_option.
+struct KnobRow {
+  const char* name;
+  Knob<int>* k32;               // exactly one of k32 / k64 (a 32-bit knob stores the normalised value truncated to int)
+  Knob<int64_t>* k64;
+  int64_t (*rule)(int64_t);     // nullptr: clamp to [lo, hi]
+  int64_t lo, hi;
+  constexpr KnobRow(const char* n, Knob<int>& k, int64_t (*r)(int64_t)) : name(n), k32(&k), k64(nullptr), rule(r), lo(0), hi(0) {}
+  constexpr KnobRow(const char* n, Knob<int>& k, int64_t l, int64_t h) : name(n), k32(&k), k64(nullptr), rule(nullptr), lo(l), hi(h) {}
+  constexpr KnobRow(const char* n, Knob<int64_t>& k, int64_t (*r)(int64_t)) : name(n), k32(nullptr), k64(&k), rule(r), lo(0), hi(0) {}
+  constexpr KnobRow(const char* n, Knob<int64_t>& k, int64_t l, int64_t h) : name(n), k32(nullptr), k64(&k), rule(nullptr), lo(l), hi(h) {}
+};
+inline int64_t knob_bool(int64_t v) { return v != 0; }
+inline int64_t knob_tri(int64_t v) { return v < 0 ? -1 : (v != 0); }   // -1 = auto, 0 = off, 1 = on
+inline int64_t knob_any(int64_t v) { return v; }
+// the largest of `hi` / `mid` that the value reaches, else `lo`
+template <int LO, int MID, int HI = MID>
+inline int64_t knob_snap_down(int64_t v) { return v >= HI ? HI : v >= MID ? MID : LO; }
+constexpr int64_t kKnobNoMax = INT64_MAX;   // `hi` of a knob with a lower bound only
+
+// A diagnostic counter (arx_get_counter), one row each in a table of the file that counts.
+struct CounterRow {
+  const char* name;
+  const std::atomic<int64_t>* v;
+};
+
+struct KnobTable {
+  const KnobRow* rows;
+  size_t n;
+};
+struct CounterTable {
+  const CounterRow* rows;
+  size_t n;
+};
+template <size_t N>
+constexpr KnobTable knob_table(const KnobRow (&rows)[N]) { return {rows, N}; }
+template <size_t N>
+constexpr CounterTable counter_table(const CounterRow (&rows)[N]) { return {rows, N}; }
+// Each file's tables, for capi.hip.
+KnobTable selection_knobs();
+KnobTable sort_knobs();
+KnobTable groupby_knobs();
+KnobTable groupby_lines_knobs();
+KnobTable parquet_knobs();
+CounterTable groupby_counters();
+CounterTable groupby_lines_counters();
+CounterTable sort_counters();
+CounterTable set_lookup_counters();
 
 #define ARX_HIP(call)                                          \
   do {                                                         \
@@ -71,26 +112,8 @@ struct Bits {
   int shift;             // position of logical bit 0 inside base[0]
 };
 
-static inline Bits make_bits(const void* bitmap, int64_t bit_offset, int64_t length) {
-  Bits b;
-  b.length = length;
-  if (bitmap == nullptr) {
-    b.base = nullptr;
-    b.nphys = 0;
-    b.shift = 0;
-    return b;
-  }
-  const uint64_t byte_addr = reinterpret_cast<uint64_t>(bitmap) + static_cast<uint64_t>(bit_offset >> 3);
-  const int bit_in_byte = static_cast<int>(bit_offset & 7);
-  const uint64_t aligned = byte_addr & ~uint64_t(7);
-  b.base = reinterpret_cast<const uint64_t*>(aligned);
-  b.shift = static_cast<int>((byte_addr - aligned) * 8) + bit_in_byte;
-  b.nphys = (static_cast<int64_t>(b.shift) + length + 63) >> 6;
-  return b;
-}
-
-// make_bits on the device (the bitmap's address comes out of a device-side table)
-__device__ __forceinline__ Bits make_bits_device(const void* bitmap, int64_t bit_offset, int64_t length) {
+// (host, and device where the bitmap's address comes out of a device-side table)
+__host__ __device__ __forceinline__ Bits make_bits(const void* bitmap, int64_t bit_offset, int64_t length) {
   Bits b;
   b.length = length;
   if (bitmap == nullptr) {

@@ -2008,7 +2008,8 @@ static Knob<int64_t> g_gbp_probe_rows{int64_t(1) << 25};   // rows of the probe 
 static Knob<int> g_gbp_l1_global{1};       // level 1 with global cursors (one tile per workgroup; +3 % at 4e9 rows) instead of chunked exact offsets
 
 static int gbp_bits_for(int64_t capacity) {
-  if (g_gbp_bits >= 0) return std::min(int(g_gbp_bits), kGbMaxBits);
+  const int forced = g_gbp_bits;
+  if (forced >= 0) return std::min(forced, kGbMaxBits);
   // capacity = slots of the HBM table ~ 2x the distinct keys expected; aim at <= 2048 groups
   // per 4096-slot LDS table.  bits == 0: everything fits one table, no partitioning at all.
   const int64_t groups = std::max<int64_t>(1, capacity / 2);
@@ -2023,12 +2024,47 @@ constexpr int64_t kGbHardMaxSlice = (int64_t(1) << 32) - (int64_t(1) << 26);   /
 static Knob<int64_t> g_gbp_wide_max_slice{kGbHardMaxSlice};   // A/B knob groupby_wide_max_slice_rows
 static Knob<int> g_gbp_agg_chunk{1 << 18};             // A/B knob groupby_agg_chunk_rows (2^16: every group of a partition is flushed 2-8x per slice; 2^18: +4 %)
 
+// the next power of two within 2^LO .. 2^HI
+template <int LO, int HI>
+static int64_t gbp_knob_pow2(int64_t value) {
+  int lg = LO;
+  while (lg < HI && (int64_t(1) << lg) < value) ++lg;
+  return int64_t(1) << lg;
+}
+// whole tiles within kGbTile .. kGbHardMaxSlice
+static int64_t gbp_knob_slice_rows(int64_t value) {
+  return std::max<int64_t>(kGbTile, std::min<int64_t>(value, kGbHardMaxSlice)) / kGbTile * kGbTile;
+}
+// name, knob, rule (arx_common.h: KnobRow) — the defaults are the initialisers above
+static const KnobRow kGroupbyKnobs[] = {
+    {"groupby_partition_min_rows", g_gbp_min_rows, 0, INT32_MAX},
+    {"groupby_partition_bits", g_gbp_bits, knob_any},
+    {"groupby_agg_pipe", g_gbp_agg_pipe, knob_bool},
+    {"groupby_xcd_map", g_gbp_xcd_map, 0, 7},
+    {"groupby_b1", g_gbp_b1, knob_any},
+    {"groupby_chunks", g_gbp_chunks, 1, kGbMaxChunks},
+    {"groupby_wide_max_bits", g_gbp_wide_max_bits, 1, kGbWideMaxBits},
+    {"groupby_wide_room_min_mean", g_gbp_room_min_mean, 1, INT32_MAX},
+    {"groupby_sketch", g_gbp_sketch, knob_bool},
+    {"groupby_stripe", g_gbp_stripe, [](int64_t v) -> int64_t { return v <= 0 ? 0 : std::max<int64_t>(4, std::min<int64_t>(v & ~int64_t(3), 1 << 20)); }},
+    {"groupby_wide_rooms", g_gbp_wide_rooms, knob_bool},
+    {"groupby_wide", g_gbp_wide, 0, 2},
+    {"groupby_wide_agg_chunk_rows", g_gbp_wide_agg_chunk, gbp_knob_pow2<14, 26>},
+    {"groupby_probe_rows", g_gbp_probe_rows, kGbTile, kKnobNoMax},
+    {"groupby_l1_global", g_gbp_l1_global, knob_bool},
+    {"groupby_max_slice_rows", g_gbp_max_slice, gbp_knob_slice_rows},
+    {"groupby_wide_max_slice_rows", g_gbp_wide_max_slice, gbp_knob_slice_rows},
+    {"groupby_agg_chunk_rows", g_gbp_agg_chunk, gbp_knob_pow2<12, 24>},
+};
+KnobTable groupby_knobs() { return knob_table(kGroupbyKnobs); }
+
 // Partition bits of the wide form for `groups` distinct keys (<= kGbWideMaxGroups per 8192-slot LDS table), or -1 when
 // the flat level would need more than 2048 bins.
 static int gbp_wide_bits_for(int64_t groups) {
   int bits = 1;
-  while (bits <= g_gbp_wide_max_bits && ((groups + (int64_t(1) << bits) - 1) >> bits) > kGbWideMaxGroups) ++bits;
-  return bits <= g_gbp_wide_max_bits ? bits : -1;
+  const int max_bits = g_gbp_wide_max_bits;
+  while (bits <= max_bits && ((groups + (int64_t(1) << bits) - 1) >> bits) > kGbWideMaxGroups) ++bits;
+  return bits <= max_bits ? bits : -1;
 }
 
 // Records a partition's room holds when the wide form runs without a histogram: the mean + 6 sigma of the binomial a
@@ -2058,15 +2094,17 @@ static GbpPlan gbp_plan(int64_t slice_rows, int64_t capacity, int64_t groups_hin
     // (32 bins: ~128-record runs), level 2 works inside a partition whose short runs meet in one L2 (xcd_contiguous) —
     // 4e9 rows / 1e7 keys: 7 + 6 bits 61.6 ms, 5 + 8 bits 54.4 ms; 1e6 keys: 5 + 4 bits 60.8 ms, 3 + 6 bits 54.0 ms
     p.b1 = std::max(p.bits - 8, std::min(3, p.bits - 1));
-    if (g_gbp_b1 > 0) p.b1 = std::max(p.bits - 8, std::min(int(g_gbp_b1), std::min(8, p.bits - 1)));
+    const int b1 = g_gbp_b1;
+    if (b1 > 0) p.b1 = std::max(p.bits - 8, std::min(b1, std::min(8, p.bits - 1)));
     p.b2 = p.bits - p.b1;
   }
   // the wide one-level plan replaces a two-level plan when its tables are known to be enough; groupby_wide = 2 forces
   // it (tests / A-B) with groupby_partition_bits as its bin count
   int wb = -1;
-  if (g_gbp_wide == 2) {
-    wb = int(g_gbp_bits) >= 1 ? std::min(int(g_gbp_bits), kGbWideMaxBits) : kGbWideMaxBits;
-  } else if (g_gbp_wide && p.bits > 8 && g_gbp_bits < 0) {
+  const int wide = g_gbp_wide, forced_bits = g_gbp_bits;
+  if (wide == 2) {
+    wb = forced_bits >= 1 ? std::min(forced_bits, kGbWideMaxBits) : kGbWideMaxBits;
+  } else if (wide && p.bits > 8 && forced_bits < 0) {
     wb = gbp_wide_bits_for(groups_hint >= 0 ? groups_hint : std::max<int64_t>(1, capacity / 2));
     if (dense_idbits > 0) {
       // dense ids: id << (32 - idbits) is the bijection, a partition's ids are consecutive and map to distinct slots
@@ -2176,19 +2214,16 @@ static std::atomic<int64_t> g_gbp_slices_direct{0}, g_gbp_slices_one_level{0}, g
     g_gbp_slices_wide{0}, g_gbp_slices_probe{0}, g_gbp_slices_rooms{0}, g_gbp_rooms_overflows{0};
 constexpr int kGbpRoomsOverflow = -1000;   // gbp_run_slice: a partition outgrew its room, nothing consumed yet
 
-static int get_groupby_lines_counter(const char* name, int64_t* out);   // groupby_lines.h
-
-int get_groupby_counter(const char* name, int64_t* out) {
-  if (strcmp(name, "groupby_slices_direct") == 0) *out = g_gbp_slices_direct.load();
-  else if (strcmp(name, "groupby_slices_one_level") == 0) *out = g_gbp_slices_one_level.load();
-  else if (strcmp(name, "groupby_slices_two_level") == 0) *out = g_gbp_slices_two_level.load();
-  else if (strcmp(name, "groupby_slices_wide") == 0) *out = g_gbp_slices_wide.load();
-  else if (strcmp(name, "groupby_slices_probe") == 0) *out = g_gbp_slices_probe.load();
-  else if (strcmp(name, "groupby_slices_rooms") == 0) *out = g_gbp_slices_rooms.load();
-  else if (strcmp(name, "groupby_rooms_overflows") == 0) *out = g_gbp_rooms_overflows.load();
-  else return get_groupby_lines_counter(name, out);
-  return 1;
-}
+static const CounterRow kGroupbyCounters[] = {
+    {"groupby_slices_direct", &g_gbp_slices_direct},
+    {"groupby_slices_one_level", &g_gbp_slices_one_level},
+    {"groupby_slices_two_level", &g_gbp_slices_two_level},
+    {"groupby_slices_wide", &g_gbp_slices_wide},
+    {"groupby_slices_probe", &g_gbp_slices_probe},
+    {"groupby_slices_rooms", &g_gbp_slices_rooms},
+    {"groupby_rooms_overflows", &g_gbp_rooms_overflows},
+};
+CounterTable groupby_counters() { return counter_table(kGroupbyCounters); }
 
 template <bool HAS_NULLS>
 static int gbp_run_slice(const GroupbyView& v, GbpArgs a, const GbpPlan& plan, hipStream_t st, bool redo = false) {
@@ -2336,89 +2371,6 @@ static int read_header(void* state, GroupbyHeader* h, hipStream_t st) {
   return ARX_OK;
 }
 
-static int set_groupby_lines_option(const char* name, int64_t value);   // groupby_lines.h
-
-int set_groupby_option(const char* name, int64_t value) {
-  if (set_groupby_lines_option(name, value)) return 1;
-  if (strcmp(name, "groupby_partition_min_rows") == 0) {
-    g_gbp_min_rows = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(value, INT32_MAX)));
-    return 1;
-  }
-  if (strcmp(name, "groupby_chunks") == 0) {
-    g_gbp_chunks = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(value, kGbMaxChunks)));
-    return 1;
-  }
-  if (strcmp(name, "groupby_max_slice_rows") == 0) {
-    g_gbp_max_slice = std::max<int64_t>(kGbTile, std::min<int64_t>(value, kGbHardMaxSlice)) / kGbTile * kGbTile;
-    return 1;
-  }
-  if (strcmp(name, "groupby_agg_chunk_rows") == 0) {
-    int lg = 12;
-    while (lg < 24 && (int64_t(1) << lg) < value) ++lg;
-    g_gbp_agg_chunk = 1 << lg;
-    return 1;
-  }
-  if (strcmp(name, "groupby_wide") == 0) {
-    g_gbp_wide = value < 0 ? 0 : static_cast<int>(std::min<int64_t>(value, 2));
-    return 1;
-  }
-  if (strcmp(name, "groupby_wide_agg_chunk_rows") == 0) {
-    int lg = 14;
-    while (lg < 26 && (int64_t(1) << lg) < value) ++lg;
-    g_gbp_wide_agg_chunk = 1 << lg;
-    return 1;
-  }
-  if (strcmp(name, "groupby_wide_room_min_mean") == 0) {
-    g_gbp_room_min_mean = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(value, INT32_MAX)));
-    return 1;
-  }
-  if (strcmp(name, "groupby_sketch") == 0) {
-    g_gbp_sketch = value != 0;
-    return 1;
-  }
-  if (strcmp(name, "groupby_stripe") == 0) {
-    g_gbp_stripe = value <= 0 ? 0 : static_cast<int>(std::max<int64_t>(4, std::min<int64_t>(value & ~int64_t(3), 1 << 20)));
-    return 1;
-  }
-  if (strcmp(name, "groupby_wide_rooms") == 0) {
-    g_gbp_wide_rooms = value != 0;
-    return 1;
-  }
-  if (strcmp(name, "groupby_wide_max_slice_rows") == 0) {
-    g_gbp_wide_max_slice = std::max<int64_t>(kGbTile, std::min<int64_t>(value, kGbHardMaxSlice)) / kGbTile * kGbTile;
-    return 1;
-  }
-  if (strcmp(name, "groupby_wide_max_bits") == 0) {
-    g_gbp_wide_max_bits = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(value, kGbWideMaxBits)));
-    return 1;
-  }
-  if (strcmp(name, "groupby_probe_rows") == 0) {
-    g_gbp_probe_rows = std::max<int64_t>(kGbTile, value);
-    return 1;
-  }
-  if (strcmp(name, "groupby_l1_global") == 0) {
-    g_gbp_l1_global = value != 0;
-    return 1;
-  }
-  if (strcmp(name, "groupby_b1") == 0) {
-    g_gbp_b1 = static_cast<int>(value);
-    return 1;
-  }
-  if (strcmp(name, "groupby_xcd_map") == 0) {
-    g_gbp_xcd_map = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(value, 7)));
-    return 1;
-  }
-  if (strcmp(name, "groupby_agg_pipe") == 0) {
-    g_gbp_agg_pipe = value != 0;
-    return 1;
-  }
-  if (strcmp(name, "groupby_partition_bits") == 0) {
-    g_gbp_bits = static_cast<int>(value);
-    return 1;
-  }
-  return 0;
-}
-
 // hash_any / hash_all Finalize (GroupedBooleanAggregator::Finalize, kernels/hash_aggregate.cc:1321-1350) from three dense
 // counts per group — valid rows, null rows, valid rows whose value is true: a wave packs 64 groups per ballot.
 //   value    any: a true was seen          all: no false was seen
@@ -2545,7 +2497,8 @@ size_t arx_groupby_consume_workspace_bytes(int64_t length, int64_t capacity) {
   if (length < g_gbp_min_rows || length <= 0) return 0;
   // the plan the capacity alone selects, in its slices — and, where a measured group count may select the wide plan
   // later (arx_groupby_sum_i64_consume's probe slice), room for that plan's larger slices
-  size_t need = gbp_plan(std::min<int64_t>(length, gbp_plan(kGbTile, capacity).wide ? int64_t(g_gbp_wide_max_slice) : int64_t(g_gbp_max_slice)),
+  const int64_t wide_max_slice = g_gbp_wide_max_slice;
+  size_t need = gbp_plan(std::min<int64_t>(length, gbp_plan(kGbTile, capacity).wide ? wide_max_slice : int64_t(g_gbp_max_slice)),
                          capacity).total;
   if (g_gbp_wide && g_gbp_bits < 0 && !gbp_plan(kGbTile, capacity).wide && gbp_plan(kGbTile, capacity).b2 > 0) {
     // (the rooms' slack grows with the partition count: size for the fewest and for the most partitions a hint can select,
@@ -2553,7 +2506,7 @@ size_t arx_groupby_consume_workspace_bytes(int64_t length, int64_t capacity) {
     //  the probe slice had taken 2^25 rows first)
     const int64_t few = int64_t(kGbWideMaxGroups) << 1;
     const int64_t many = int64_t(kGbWideMaxGroups) << std::min<int>(int(g_gbp_wide_max_bits), kGbWideMaxBits);
-    const int64_t rows = std::min<int64_t>(length, int64_t(g_gbp_wide_max_slice));
+    const int64_t rows = std::min<int64_t>(length, wide_max_slice);
     need = std::max({need, gbp_plan(rows, capacity, few).total, gbp_plan(rows, capacity, many).total});
   }
   return std::max(need, length >= g_gbl_min_rows ? gbl_workspace_bytes(length, true) : size_t(0));
@@ -2663,8 +2616,9 @@ static int gb_sum_i64_consume(void* state, int64_t capacity, const ArxSpan* keys
     // never exactness (rows that find no room in an LDS table go to the HBM table).
     const GbpPlan unhinted = gbp_plan(slice, capacity);
     const int64_t probe_rows = std::max<int64_t>(kGbTile, int64_t(g_gbp_probe_rows) / kGbTile * kGbTile);
-    const bool sketch = g_gbp_sketch != 0 && g_gbp_wide && g_gbp_bits < 0 && unhinted.b2 > 0 && !unhinted.wide && n >= 2 * probe_rows;
-    const bool probe = emit == nullptr && !sketch && g_gbp_wide && g_gbp_bits < 0 && unhinted.b2 > 0 && !unhinted.wide && n >= 4 * probe_rows;   // (the probe reads the table's group count: the emit form leaves the table empty)
+    const bool wide_in_reach = g_gbp_wide && g_gbp_bits < 0 && unhinted.b2 > 0 && !unhinted.wide;
+    const bool sketch = g_gbp_sketch != 0 && wide_in_reach && n >= 2 * probe_rows;
+    const bool probe = emit == nullptr && !sketch && wide_in_reach && n >= 4 * probe_rows;   // (the probe reads the table's group count: the emit form leaves the table empty)
     int64_t groups_hint = -1;
     bool rooms_ok = true;
     unsigned long long groups_before = 0;

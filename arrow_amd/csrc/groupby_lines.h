@@ -803,7 +803,24 @@ static Knob<int64_t> g_gbl_sample_rows{int64_t(1) << 24};   // rows the histogra
 static Knob<int64_t> g_gbl_range_sample_rows{int64_t(1) << 20};   // rows the key-range sample reads (knob groupby_lines_range_sample_rows)
 static Knob<int> g_gbl_unit_rows{1 << 21};         // rows per aggregate work unit (knob groupby_lines_unit_rows)
 static Knob<int> g_gbl_wgs{0};                     // workgroups of the scatter (0: one per CU; knob groupby_lines_wgs — tests)
+static const KnobRow kGroupbyLinesKnobs[] = {
+    {"groupby_lines", g_gbl, knob_bool},
+    {"groupby_lines_min_rows", g_gbl_min_rows, 1, kKnobNoMax},
+    {"groupby_lines_sample_rows", g_gbl_sample_rows, kGblUnitRows, kKnobNoMax},
+    {"groupby_lines_range_sample_rows", g_gbl_range_sample_rows, kGblUnitRows, kKnobNoMax},
+    {"groupby_lines_unit_rows", g_gbl_unit_rows, 768, 1 << 30},
+    {"groupby_lines_wgs", g_gbl_wgs, 0, 4096},
+};
+// (defined here, in a header: groupby.hip is its only includer)
+KnobTable groupby_lines_knobs() { return knob_table(kGroupbyLinesKnobs); }
 static std::atomic<int64_t> g_gbl_slices{0}, g_gbl_fallbacks{0}, g_gbl_outlier_rows{0}, g_gbl_declined{0};
+static const CounterRow kGroupbyLinesCounters[] = {
+    {"groupby_slices_lines", &g_gbl_slices},
+    {"groupby_lines_fallbacks", &g_gbl_fallbacks},
+    {"groupby_lines_declined", &g_gbl_declined},
+    {"groupby_lines_outlier_rows", &g_gbl_outlier_rows},
+};
+CounterTable groupby_lines_counters() { return counter_table(kGroupbyLinesCounters); }
 
 struct GblPlan {
   int64_t kmin;
@@ -867,7 +884,8 @@ static bool gbl_plan(int64_t n, int64_t kmin, int width, int wshift, int bins, b
   p->wshift = wshift;
   p->bins = bins;
   const int64_t batch = int64_t(kGblR) * kGblThreads;
-  int wgs = g_gbl_wgs > 0 ? int(g_gbl_wgs) : gbl_cus();
+  const int knob_wgs = g_gbl_wgs;
+  int wgs = knob_wgs > 0 ? knob_wgs : gbl_cus();
   wgs = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(wgs, n / (int64_t(1) << 18))));   // >= 2^18 rows per workgroup: chunk tails stay small
   p->wgs = wgs;
   p->rows_per_wg = ceil_div(ceil_div(n, wgs), batch) * batch;
@@ -893,7 +911,8 @@ static bool gbl_plan(int64_t n, int64_t kmin, int width, int wshift, int bins, b
 // scratch the lines plan may ask for at most for `n` rows (any key range it accepts; with_dense: + the dense state)
 static size_t gbl_workspace_bytes(int64_t n, bool with_dense) {
   if (!g_gbl || n < 1) return 0;
-  const int wgs = g_gbl_wgs > 0 ? int(g_gbl_wgs) : gbl_cus();
+  const int knob_wgs = g_gbl_wgs;
+  const int wgs = knob_wgs > 0 ? knob_wgs : gbl_cus();
   const int64_t lines = gbl_lines_for(n, kGblMaxBins, wgs, gbl_stride_for(n, g_gbl_sample_rows));
   return static_cast<size_t>(lines) * 128 + (size_t(kGblMaxBins) * kGblCursorStride * 4 + 4 * (kGblMaxBins + 1) * 4 + 4096) +
          (with_dense ? static_cast<size_t>(kGblMaxBins) * kGblMaxWidth * 16 + 256 : 0);
@@ -966,14 +985,15 @@ static int gbl_try(const GroupbyView& v, const int32_t* k, const int64_t* val, B
   int32_t* range = reinterpret_cast<int32_t*>(w);
   const int32_t init[2] = {INT32_MAX, INT32_MIN};
   ARX_HIP(hipMemcpyAsync(range, init, 8, hipMemcpyHostToDevice, st));
-  const int rrc = gbl_sample_range(k, n, g_gbl_range_sample_rows, range, st);
+  const int64_t range_sample_rows = g_gbl_range_sample_rows;
+  const int rrc = gbl_sample_range(k, n, range_sample_rows, range, st);
   if (rrc != ARX_OK) return rrc;
   int32_t mm[2];
   ARX_HIP(hipMemcpyAsync(mm, range, 8, hipMemcpyDeviceToHost, st));
   ARX_HIP(hipStreamSynchronize(st));
   if (mm[0] > mm[1]) return kGblDeclined;
   // (a sample misses a few keys at both ends of a range: 1/64 of the range on either side)
-  const bool sampled = gbl_stride_for(n, g_gbl_range_sample_rows) > 1;
+  const bool sampled = gbl_stride_for(n, range_sample_rows) > 1;
   const int64_t pad = sampled ? (static_cast<int64_t>(mm[1]) - mm[0] + 1) / 64 + 1 : 0;
   const int64_t kmin = std::max<int64_t>(INT32_MIN, static_cast<int64_t>(mm[0]) - pad);
   const int64_t kmax = std::min<int64_t>(INT32_MAX, static_cast<int64_t>(mm[1]) + pad);
@@ -1022,24 +1042,4 @@ static int gbl_try(const GroupbyView& v, const int32_t* k, const int64_t* val, B
   hipLaunchKernelGGL(gbl_table_insert_kernel, dim3(gb_grid(static_cast<int64_t>(plan.bins) * plan.width)), dim3(kBlock), 0, st, v, a);
   ARX_CHECK_LAUNCH("gbl_table_insert_kernel");
   return ARX_OK;
-}
-
-static int get_groupby_lines_counter(const char* name, int64_t* out) {
-  if (strcmp(name, "groupby_slices_lines") == 0) *out = g_gbl_slices.load();
-  else if (strcmp(name, "groupby_lines_fallbacks") == 0) *out = g_gbl_fallbacks.load();
-  else if (strcmp(name, "groupby_lines_declined") == 0) *out = g_gbl_declined.load();
-  else if (strcmp(name, "groupby_lines_outlier_rows") == 0) *out = g_gbl_outlier_rows.load();
-  else return 0;
-  return 1;
-}
-
-static int set_groupby_lines_option(const char* name, int64_t value) {
-  if (strcmp(name, "groupby_lines") == 0) g_gbl = value != 0 ? 1 : 0;
-  else if (strcmp(name, "groupby_lines_min_rows") == 0) g_gbl_min_rows = std::max<int64_t>(1, value);
-  else if (strcmp(name, "groupby_lines_sample_rows") == 0) g_gbl_sample_rows = std::max<int64_t>(kGblUnitRows, value);
-  else if (strcmp(name, "groupby_lines_range_sample_rows") == 0) g_gbl_range_sample_rows = std::max<int64_t>(kGblUnitRows, value);
-  else if (strcmp(name, "groupby_lines_unit_rows") == 0) g_gbl_unit_rows = static_cast<int>(std::max<int64_t>(768, std::min<int64_t>(value, 1 << 30)));
-  else if (strcmp(name, "groupby_lines_wgs") == 0) g_gbl_wgs = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(value, 4096)));
-  else return 0;
-  return 1;
 }

@@ -307,13 +307,10 @@ __global__ __launch_bounds__(kBlock) void byte_stream_split_kernel(const uint8_t
 // by the page count: the LDS form is 8-25 % faster on pages of >= 160 KB (profiles/r02_aq) but its 70 KB of LDS per
 // workgroup halves the waves per CU, which costs 40-65 % when there are thousands of small pages to overlap
 static Knob<int> g_snappy_lds{-1};
-int set_parquet_option(const char* name, int64_t value) {
-  if (strcmp(name, "snappy_lds") == 0) {
-    g_snappy_lds = value < 0 ? -1 : (value != 0);
-    return 1;
-  }
-  return 0;
-}
+static const KnobRow kParquetKnobs[] = {
+    {"snappy_lds", g_snappy_lds, knob_tri},
+};
+KnobTable parquet_knobs() { return knob_table(kParquetKnobs); }
 
 // ------------------------------------------------------------------ Snappy page decompression
 // What SnappyCodec::Decompress -> snappy::RawUncompress does per page (cpp/src/arrow/util/compression_snappy.cc:42-62;
@@ -1977,7 +1974,8 @@ int arx_snappy_decompress_pages(const void* compressed, const ArxSnappyPage* pag
     return ARX_INVALID;
   }
   const unsigned grid = static_cast<unsigned>(ceil_div(num_pages, kWavesPerBlock));
-  if (g_snappy_lds == 1 || (g_snappy_lds < 0 && num_pages < 4096)) {
+  const int lds = g_snappy_lds;
+  if (lds == 1 || (lds < 0 && num_pages < 4096)) {
     hipLaunchKernelGGL(snappy_decode_lds_kernel, dim3(grid), dim3(kBlock), 0, as_stream(stream),
                        static_cast<const uint8_t*>(compressed), pages, num_pages, static_cast<uint8_t*>(out), status);
   } else {

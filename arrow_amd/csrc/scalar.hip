@@ -835,7 +835,7 @@ __global__ __launch_bounds__(kBlock) void bitmap_copy_segments_kernel(const ArxB
   const unsigned part = blockIdx.x % per_seg;
   if (sg >= nsegs) return;
   const ArxBitSeg seg = segs[sg];
-  const Bits src = make_bits_device(seg.src, seg.src_bit_offset, seg.nbits);
+  const Bits src = make_bits(seg.src, seg.src_bit_offset, seg.nbits);
   unsigned long long* dst = static_cast<unsigned long long*>(seg.dst);
   const int64_t nwords = (seg.nbits + 63) >> 6;
   for (int64_t w = static_cast<int64_t>(part) * kBlock + threadIdx.x; w < nwords; w += static_cast<int64_t>(per_seg) * kBlock) {

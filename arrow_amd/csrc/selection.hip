@@ -1216,6 +1216,12 @@ static int launch_count(const ArxSpan* mask, int null_selection, void* ws, size_
 static Knob<int> g_filter_batch{4};
 static Knob<int> g_filter_pipe{1};
 static Knob<int> g_filter_sparse{-1};  // -1 = auto (see launch_compact), 0 = never, 1 = always
+static const KnobRow kSelectionKnobs[] = {
+    {"filter_batch", g_filter_batch, knob_snap_down<1, 4>},
+    {"filter_pipe", g_filter_pipe, knob_bool},
+    {"filter_sparse", g_filter_sparse, knob_tri},
+};
+KnobTable selection_knobs() { return knob_table(kSelectionKnobs); }
 
 template <int W, bool IOTA, bool EMIT, bool ALIGNED>
 static void launch_compact_e(const CompactArgs& a, unsigned grid, hipStream_t st) {
@@ -1260,13 +1266,14 @@ static int launch_compact(bool iota, int W, const CompactArgs& a, hipStream_t st
   // gather form wins at EVERY selectivity (1.94 vs 2.46 ms at 25 %, 2.38 vs 2.84 ms at 50 %, equal
   // at 100 %); narrower values keep the sweeping form above 25 % (its 16-byte granules carry
   // 4-16 rows per lane, the gather form would issue 1-4 byte accesses).
+  const int filter_sparse = g_filter_sparse;
   const bool sparse = !iota && !a.invert &&
-                      (g_filter_sparse == 1 ||
-                       (g_filter_sparse < 0 &&
+                      (filter_sparse == 1 ||
+                       (filter_sparse < 0 &&
                         (W >= 8 || (out_length >= 0 && out_length * 4 <= a.length))));
   // GetTakeIndices: the gather form (row numbers instead of gathered values) unless the bitmap is
   // being inverted for the sort's null partition
-  if (iota && !a.invert && g_filter_sparse != 0 && (W == 2 || W == 4 || W == 8)) {
+  if (iota && !a.invert && filter_sparse != 0 && (W == 2 || W == 4 || W == 8)) {
     if (W == 2) launch_sparse_w<2, true>(a, grid, st);
     else if (W == 4) launch_sparse_w<4, true>(a, grid, st);
     else launch_sparse_w<8, true>(a, grid, st);
@@ -1311,22 +1318,6 @@ static int launch_compact(bool iota, int W, const CompactArgs& a, hipStream_t st
   }
   ARX_CHECK_LAUNCH("compact_kernel");
   return ARX_OK;
-}
-
-int set_selection_option(const char* name, int64_t value) {
-  if (strcmp(name, "filter_batch") == 0) {
-    g_filter_batch = value >= 4 ? 4 : 1;
-    return 1;
-  }
-  if (strcmp(name, "filter_pipe") == 0) {
-    g_filter_pipe = value != 0;
-    return 1;
-  }
-  if (strcmp(name, "filter_sparse") == 0) {
-    g_filter_sparse = value < 0 ? -1 : (value != 0);
-    return 1;
-  }
-  return 0;
 }
 
 // Zero the ceil(S/64) words of an output bitmap (tile-boundary words are OR-ed in).

@@ -569,12 +569,11 @@ int probe_binary_any(const void* state, const ArxBinarySpan* set, int set_offset
 
 }  // namespace
 
-int get_set_lookup_counter(const char* name, int64_t* out) {
-  if (strcmp(name, "set_lookup_lds_probes") == 0) *out = g_set_lookup_lds_probes.load();
-  else if (strcmp(name, "set_lookup_global_probes") == 0) *out = g_set_lookup_global_probes.load();
-  else return 0;
-  return 1;
-}
+static const CounterRow kSetLookupCounters[] = {
+    {"set_lookup_lds_probes", &g_set_lookup_lds_probes},
+    {"set_lookup_global_probes", &g_set_lookup_global_probes},
+};
+CounterTable set_lookup_counters() { return counter_table(kSetLookupCounters); }
 
 }  // namespace arx
 

@@ -33,6 +33,8 @@ constexpr int kSortItems = 16;
 constexpr int kSortTile = kBlock * kSortItems;  // 4096 keys
 constexpr int kDigits = 256;
 constexpr int kMaxChunks = 16384;  // upper bound (sizes the histogram table)
+constexpr int kMsdMaxBits = 14;    // partition bits of the MSD forms' two global levels
+constexpr int kMsdwMaxBits = 20;   // ... of the wide two-level form
 static Knob<int> g_sort_msd{-1};            // -1 = auto (n >= g_sort_msd_min_rows), 0 = never, 1 = whenever possible
 static Knob<int> g_sort_msd_min_rows{1 << 22};
 static Knob<int> g_sort_msd_sampled{1};     // skewed keys: bucket boundaries from a sorted sample
@@ -69,6 +71,46 @@ static Knob<int> g_sort_msd_seg_min_bits{1};  // floor of the segment level's bi
 static Knob<int> g_sort_msd_global_bits{14};  // (= kMsdMaxBits) cap of the two global levels (tests lower it to reach level 3)
 static Knob<int> g_sort_fuse_prep{1};    // first pass reads the caller's column directly (no prep pass)
 static Knob<int> g_sort_chunks{2048};    // chunks actually used (arx_set_option "sort_chunks")
+
+// name, knob, rule (arx_common.h: KnobRow) — the defaults are the initialisers above
+static const KnobRow kSortKnobs[] = {
+    {"sort_msd", g_sort_msd, knob_tri},
+    {"sort_msd_min_rows", g_sort_msd_min_rows, 256, INT32_MAX},
+    {"sort_msd_sampled", g_sort_msd_sampled, 0, 2},
+    {"sort_msd_fused", g_sort_msd_fused, knob_bool},
+    {"sort_msd_segment_rows", g_sort_msd_segment_rows, 1024, kKnobNoMax},
+    {"sort_msd_final_rows_log2", g_sort_msd_final_rows_log2, 1, 8},
+    {"sort_msd_small_bucket", g_sort_msd_small_bucket, knob_bool},
+    {"sort_msd_wide_sample_shift", g_sort_msd_wide_sample_shift, 0, 8},
+    {"sort_xcd_map", g_sort_xcd_map, 0, 7},
+    {"sort_msd_wide_bits", g_sort_msd_wide_bits, 0, kMsdwMaxBits},
+    {"sort_msd_wide_b2max", g_sort_msd_wide_b2max, 0, 12},
+    {"sort_msd_wide_rpt1", g_sort_msd_wide_rpt1, knob_snap_down<8, 16, 24>},
+    {"sort_msd_wide_rpt2", g_sort_msd_wide_rpt2, knob_snap_down<8, 16, 24>},
+    {"sort_msd_tiny_bucket", g_sort_msd_tiny_bucket, 0, 2},   // 2: also the 9-rows-per-thread form
+    {"sort_msd_bucket_cpt", g_sort_msd_bucket_cpt, knob_snap_down<4, 8>},
+    {"sort_msd_prefix", g_sort_msd_prefix, knob_bool},
+    {"sort_msd_wide_gap2", g_sort_msd_wide_gap2, knob_bool},
+    {"sort_msd_wide_rec8", g_sort_msd_wide_rec8, knob_bool},
+    {"sort_msd_wide_rec8_tie_shift", g_sort_msd_wide_rec8_tie_shift, 0, 40},
+    {"sort_msd_wide_wc", g_sort_msd_wide_wc, 0, 4096},
+    {"sort_records_in_place", g_sort_records_in_place, knob_bool},
+    {"sort_vary_sample_shift", g_sort_vary_sample_shift, 1, 8},
+    {"sort_msd_wide_wc_typed", g_sort_msd_wide_wc_typed, [](int64_t v) -> int64_t { return v == 2 ? 2 : (v != 0); }},
+    {"sort_msd_wide_wc_form", g_sort_msd_wide_wc_form, [](int64_t v) -> int64_t { return v == 1 ? 1 : 2; }},
+    {"sort_msd_wide_wc_rows", g_sort_msd_wide_wc_rows, [](int64_t v) -> int64_t { return v == 8 ? 8 : v == 6 ? 6 : 4; }},
+    {"sort_msd_wide_wc_min_rows", g_sort_msd_wide_wc_min_rows, 1, 1 << 30},
+    {"sort_msd_wide_wc_prefetch", g_sort_msd_wide_wc_prefetch, knob_bool},
+    {"sort_msd_wide_l2w", g_sort_msd_wide_l2w, 0, 3},
+    {"sort_msd_wide_sample_strict", g_sort_msd_wide_sample_strict, knob_bool},
+    {"sort_msd_wide", g_sort_msd_wide, knob_bool},
+    {"sort_msd_bucket_v2", g_sort_msd_bucket_v2, knob_bool},
+    {"sort_msd_seg_min_bits", g_sort_msd_seg_min_bits, 1, 7},
+    {"sort_msd_global_bits", g_sort_msd_global_bits, 2, kMsdMaxBits},
+    {"sort_fuse_prep", g_sort_fuse_prep, knob_bool},
+    {"sort_chunks", g_sort_chunks, 1, kMaxChunks},
+};
+KnobTable sort_knobs() { return knob_table(kSortKnobs); }
 
 // Provided by selection.hip: ascending row numbers of the set (or clear) bits of a bitmap.
 int selection_bit_positions(const void* bitmap, int64_t bit_offset, int64_t length, bool invert,
@@ -726,7 +768,6 @@ __global__ void widen_counts_kernel(const uint32_t* __restrict__ in, int n, int6
 constexpr int kMsdThreads = 512;
 constexpr int kMsdTile = 4096;
 constexpr int kMsdRows = kMsdTile / kMsdThreads;  // 8 per thread
-constexpr int kMsdMaxBits = 14;
 constexpr int kMsdMaxChunks = 2048;
 constexpr int kMsdCore = 2048;   // rows finalised per workgroup of msd_final
 constexpr int kMsdHalo = 256;    // a bucket must fit in the halo on either side
@@ -1719,7 +1760,6 @@ constexpr size_t kMsdTableBytes = (3 * kMsdTableWords + size_t(128) * kMsdMaxChu
 // tables of the wide two-level form (run_msd_sort_wide): 3 arrays of 2^20 buckets + 10 of 1024 level-1 entries
 constexpr int kMsdwMaxBins = 1024;    // level 1 (one thread per bin in the one-workgroup scans)
 constexpr int kMsdwMaxBins2 = 4096;   // level 2 (inside a level-1 bucket: short runs are fine there, xcd_contiguous)
-constexpr int kMsdwMaxBits = 20;
 constexpr size_t kMsdwTableBytes = (3 * ((size_t(1) << kMsdwMaxBits) + 64) + 10 * (kMsdwMaxBins + 64) + kMsdwMaxBins * 32) * 4;   // (+ the write-combined level 1's cursors, a 128-byte line each)
 
 // The wide form lays its buckets out with room to spare instead of counting them exactly first: level-1 buckets
@@ -1766,157 +1806,15 @@ static SortPlan make_plan(int64_t length) {
 static std::atomic<int64_t> g_sort_wide_runs{0}, g_sort_wide_rec8_runs{0}, g_sort_wide_rec8_ties{0}, g_sort_wide_rec8_given_up{0},
     g_sort_wide_wc_runs{0}, g_sort_wide_wc_given_up{0};
 
-int get_sort_counter(const char* name, int64_t* out) {
-  if (strcmp(name, "sort_wide_runs") == 0) *out = g_sort_wide_runs.load();
-  else if (strcmp(name, "sort_wide_rec8_runs") == 0) *out = g_sort_wide_rec8_runs.load();
-  else if (strcmp(name, "sort_wide_rec8_ties") == 0) *out = g_sort_wide_rec8_ties.load();
-  else if (strcmp(name, "sort_wide_rec8_given_up") == 0) *out = g_sort_wide_rec8_given_up.load();
-  else if (strcmp(name, "sort_wide_wc_runs") == 0) *out = g_sort_wide_wc_runs.load();
-  else if (strcmp(name, "sort_wide_wc_given_up") == 0) *out = g_sort_wide_wc_given_up.load();
-  else return 0;
-  return 1;
-}
-
-int set_sort_option(const char* name, int64_t value) {
-  if (strcmp(name, "sort_msd") == 0) {
-    g_sort_msd = value < 0 ? -1 : (value != 0);
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_sampled") == 0) {
-    g_sort_msd_sampled = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(value, 2)));
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_fused") == 0) {
-    g_sort_msd_fused = value != 0;
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_final_rows_log2") == 0) {
-    g_sort_msd_final_rows_log2 = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(value, 8)));
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_wide_sample_shift") == 0) {
-    g_sort_msd_wide_sample_shift = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(value, 8)));
-    return 1;
-  }
-  if (strcmp(name, "sort_xcd_map") == 0) {
-    g_sort_xcd_map = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(value, 7)));
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_wide_bits") == 0) {
-    g_sort_msd_wide_bits = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(value, kMsdwMaxBits)));
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_wide_b2max") == 0) {
-    g_sort_msd_wide_b2max = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(value, 12)));
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_wide_rpt1") == 0 || strcmp(name, "sort_msd_wide_rpt2") == 0) {
-    const int rpt = value >= 24 ? 24 : value >= 16 ? 16 : 8;
-    (name[17] == '1' ? g_sort_msd_wide_rpt1 : g_sort_msd_wide_rpt2) = rpt;
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_bucket_cpt") == 0) {
-    g_sort_msd_bucket_cpt = value >= 8 ? 8 : 4;
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_tiny_bucket") == 0) {
-    g_sort_msd_tiny_bucket = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(value, 2)));   // 2: also the 9-rows-per-thread form
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_prefix") == 0) {
-    g_sort_msd_prefix = value != 0;
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_wide_gap2") == 0) {
-    g_sort_msd_wide_gap2 = value != 0;
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_wide_rec8") == 0) {
-    g_sort_msd_wide_rec8 = value != 0;
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_wide_wc") == 0) {
-    g_sort_msd_wide_wc = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(value, 4096)));
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_wide_l2w") == 0) {
-    g_sort_msd_wide_l2w = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(value, 3)));
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_wide_wc_prefetch") == 0) {
-    g_sort_msd_wide_wc_prefetch = value != 0;
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_wide_wc_rows") == 0) {
-    g_sort_msd_wide_wc_rows = value == 8 ? 8 : value == 6 ? 6 : 4;
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_wide_wc_min_rows") == 0) {
-    g_sort_msd_wide_wc_min_rows = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(value, 1 << 30)));
-    return 1;
-  }
-  if (strcmp(name, "sort_records_in_place") == 0) {
-    g_sort_records_in_place = value != 0 ? 1 : 0;
-    return 1;
-  }
-  if (strcmp(name, "sort_vary_sample_shift") == 0) {
-    g_sort_vary_sample_shift = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(value, 8)));
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_wide_wc_typed") == 0) {
-    g_sort_msd_wide_wc_typed = value == 2 ? 2 : (value != 0 ? 1 : 0);
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_wide_wc_form") == 0) {
-    g_sort_msd_wide_wc_form = value == 1 ? 1 : 2;
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_wide_rec8_tie_shift") == 0) {
-    g_sort_msd_wide_rec8_tie_shift = static_cast<int>(std::max<int64_t>(0, std::min<int64_t>(value, 40)));
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_wide_sample_strict") == 0) {
-    g_sort_msd_wide_sample_strict = value != 0;
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_wide") == 0) {
-    g_sort_msd_wide = value != 0;
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_bucket_v2") == 0) {
-    g_sort_msd_bucket_v2 = value != 0;
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_small_bucket") == 0) {
-    g_sort_msd_small_bucket = value != 0;
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_seg_min_bits") == 0) {
-    g_sort_msd_seg_min_bits = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(value, 7)));
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_segment_rows") == 0) {
-    g_sort_msd_segment_rows = std::max<int64_t>(1024, value);
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_global_bits") == 0) {
-    g_sort_msd_global_bits = static_cast<int>(std::max<int64_t>(2, std::min<int64_t>(value, kMsdMaxBits)));
-    return 1;
-  }
-  if (strcmp(name, "sort_msd_min_rows") == 0) {
-    g_sort_msd_min_rows = static_cast<int>(std::max<int64_t>(256, std::min<int64_t>(value, INT32_MAX)));
-    return 1;
-  }
-  if (strcmp(name, "sort_fuse_prep") == 0) {
-    g_sort_fuse_prep = value != 0;
-    return 1;
-  }
-  if (strcmp(name, "sort_chunks") == 0) {
-    g_sort_chunks = static_cast<int>(std::max<int64_t>(1, std::min<int64_t>(value, kMaxChunks)));
-    return 1;
-  }
-  return 0;
-}
+static const CounterRow kSortCounters[] = {
+    {"sort_wide_runs", &g_sort_wide_runs},
+    {"sort_wide_rec8_runs", &g_sort_wide_rec8_runs},
+    {"sort_wide_rec8_ties", &g_sort_wide_rec8_ties},
+    {"sort_wide_rec8_given_up", &g_sort_wide_rec8_given_up},
+    {"sort_wide_wc_runs", &g_sort_wide_wc_runs},
+    {"sort_wide_wc_given_up", &g_sort_wide_wc_given_up},
+};
+CounterTable sort_counters() { return counter_table(kSortCounters); }
 
 // Runs the MSD-hybrid path.  *overflowed = 1 if a bucket did not fit the final window (the caller
 // then falls back to the LSD path).  Synchronous (reads the flag back).
@@ -2001,7 +1899,8 @@ static int run_msd_sort(const uint64_t* src_keys, const uint32_t* src_idx, int r
   a.n = n;
   int lg = 0;
   while ((int64_t(1) << (lg + 1)) <= n) ++lg;
-  int total = lg - g_sort_msd_final_rows_log2;  // default 3: ~8-16 rows per final bucket
+  const int final_rows_log2 = g_sort_msd_final_rows_log2;
+  int total = lg - final_rows_log2;  // default 3: ~8-16 rows per final bucket
   total = std::max(2, std::min(total, std::min(kMsdMaxBits + 9, 64 - kshift)));
   a.bits = std::max(2, std::min(total, int(g_sort_msd_global_bits)));
   total = std::min(total, a.bits + 9);
@@ -2063,7 +1962,7 @@ static int run_msd_sort(const uint64_t* src_keys, const uint32_t* src_idx, int r
   // level-2 buckets that fit LDS: finish each one in a single workgroup (b3 may use 10 bits there)
   if (fused) {
     const bool small = g_sort_msd_small_bucket != 0 && max_part <= static_cast<unsigned int>(kBktCapSmall);
-    const int want_b3 = lg - (g_sort_msd_final_rows_log2 - 1) - a.bits;   // default: ~4 rows per sub-bucket
+    const int want_b3 = lg - (final_rows_log2 - 1) - a.bits;   // default: ~4 rows per sub-bucket
     if (g_sort_msd_bucket_v2) {
       a.b3 = std::max(0, std::min(std::min(want_b3, small ? 11 : 12), 64 - kshift - a.bits));
       if (small) {
@@ -3699,17 +3598,19 @@ static int run_msd_sort_wide_form(const uint64_t* src_keys, const uint32_t* src_
   a.raw = raw;
   a.n = n;
   a.kshift = kshift;
-  a.xcd_map = (g_sort_xcd_map & 1) != 0;
-  a.xcd_map1 = (g_sort_xcd_map & 4) != 0;
+  const int xcd_map = g_sort_xcd_map;
+  a.xcd_map = (xcd_map & 1) != 0;
+  a.xcd_map1 = (xcd_map & 4) != 0;
   // 1024 < average bucket <= 2048 rows (up to 2^31 rows): the 256-thread finish holds them, four or five per CU.
   // 2e9 rows: 2^20 buckets 31.5 ms, 2^19 buckets (512-thread finish) 32.9 ms (profiles/r03_k_sort_ab.txt)
   a.bits = std::max(2, std::min(std::min(lg - 11, kMsdwMaxBits), 64 - kshift));
-  if (g_sort_msd_wide_bits > 0) a.bits = std::max(2, std::min(int(g_sort_msd_wide_bits), 64 - kshift));
+  const int wide_bits = g_sort_msd_wide_bits;
+  if (wide_bits > 0) a.bits = std::max(2, std::min(wide_bits, 64 - kshift));
   // level 2 takes up to b2max bits (<= 4096 bins, default 1024): level 1 scatters over the whole array, where fewer
   // bins and longer runs pay; level 2 works inside a bucket whose short runs meet in one L2 (xcd_contiguous) — but a
   // 4096-bin level 2 loses more there than level 1 gains (profiles/r02_ah)
-  a.b2 = int(g_sort_msd_wide_b2max) > 0 ? std::min(std::min(int(g_sort_msd_wide_b2max), 12), a.bits - 1)
-                                   : a.bits - a.bits / 2;   // 0: the even split
+  const int b2max = g_sort_msd_wide_b2max;
+  a.b2 = b2max > 0 ? std::min(std::min(b2max, 12), a.bits - 1) : a.bits - a.bits / 2;   // 0: the even split
   a.b1 = a.bits - a.b2;
   if (a.b1 > 10) {   // (level 1 has at most 1024 bins)
     a.b1 = 10;
@@ -3762,11 +3663,12 @@ static int run_msd_sort_wide_form(const uint64_t* src_keys, const uint32_t* src_
   // (form 2: contiguous shares of >= 2^17 rows per workgroup keep the chunk tails small; its pads — two chunks per bucket and
   //  workgroup at most, + the rooms rounded up to chunks — must fit a third of the buffers' slack: the sampled rooms take up
   //  to n / 32 + n / 8 of the n / 4)
-  int64_t wc_groups = std::min<int64_t>(int(g_sort_msd_wide_wc), grid1);
+  const int wide_wc = g_sort_msd_wide_wc;
+  int64_t wc_groups = std::min<int64_t>(wide_wc, grid1);
   int64_t wc_slack = int64_t(16) * wc_groups * nb1;
   a.wc_k = 0;
   if (a.wc_form == 2) {
-    const int64_t groups2 = std::max<int64_t>(1, std::min<int64_t>(int(g_sort_msd_wide_wc), n / std::max<int64_t>(1, int64_t(g_sort_msd_wide_wc_min_rows))));
+    const int64_t groups2 = std::max<int64_t>(1, std::min<int64_t>(wide_wc, n / std::max<int64_t>(1, int64_t(g_sort_msd_wide_wc_min_rows))));
     for (int k : {kMsdwWcK, 2, 1}) {
       const int64_t slack2 = int64_t(16) * k * 2 * groups2 * nb1 + int64_t(16) * k * nb1;
       if ((sample_shift > 0 ? 3 : 1) * slack2 <= a.capacity - n) {
@@ -3778,9 +3680,12 @@ static int run_msd_sort_wide_form(const uint64_t* src_keys, const uint32_t* src_
     }
     if (a.wc_k == 0) a.wc_form = 1;   // (its pads do not fit this input's slack: round 5's kernel pads one line per bin and workgroup)
   }
-  a.wc1 = (a.rec8 && roomy && int(g_sort_msd_wide_wc) > 0 && wc_groups > 0 &&
+  a.wc1 = (a.rec8 && roomy && wide_wc > 0 && wc_groups > 0 &&
            (a.wc_form == 2 ? nb1 <= kMsdwMaxBins : nb1 <= kMsdwWcBins && 2 * wc_slack <= a.capacity - n)) ? static_cast<int>(wc_groups) : 0;
-  const int wc_r = g_sort_msd_wide_wc_rows == 8 ? 8 : g_sort_msd_wide_wc_rows == 6 ? 6 : 4;   // (read once: the grid's shares and the kernel must agree)
+  const int wc_rows = g_sort_msd_wide_wc_rows;
+  const int wc_r = wc_rows == 8 ? 8 : wc_rows == 6 ? 6 : 4;   // (read once: the grid's shares and the kernel must agree)
+  const int wc_typed = g_sort_msd_wide_wc_typed;
+  const bool sample_strict = g_sort_msd_wide_sample_strict != 0;
   if (a.wc1 > 0 && a.wc_form == 2) {
     const int64_t batch = int64_t(wc_r) * kMsdwThreads;
     a.wc_rows_per_wg = ceil_div(ceil_div(n, a.wc1), batch) * batch;
@@ -3822,29 +3727,30 @@ static int run_msd_sort_wide_form(const uint64_t* src_keys, const uint32_t* src_
         hipLaunchKernelGGL((msdw_scatter1wc2_kernel<8, -1>), dim3(a.wc1), dim3(kMsdwThreads), 0, st, a);
       } else if (wc_r == 6) {
         hipLaunchKernelGGL((msdw_scatter1wc2_kernel<6, -1>), dim3(a.wc1), dim3(kMsdwThreads), 0, st, a);
-      } else if (kt == 0 && g_sort_msd_wide_wc_typed == 2) {   // (A/B: the queue of full lines)
+      } else if (kt == 0 && wc_typed == 2) {   // (A/B: the queue of full lines)
         hipLaunchKernelGGL((msdw_scatter1wc2_kernel<4, 0, true>), dim3(a.wc1), dim3(kMsdwThreads), 0, st, a);
-      } else if (kt == 0 && g_sort_msd_wide_wc_typed) {
+      } else if (kt == 0 && wc_typed) {
         hipLaunchKernelGGL((msdw_scatter1wc2_kernel<4, 0>), dim3(a.wc1), dim3(kMsdwThreads), 0, st, a);
-      } else if (kt == 1 && g_sort_msd_wide_wc_typed) {
+      } else if (kt == 1 && wc_typed) {
         hipLaunchKernelGGL((msdw_scatter1wc2_kernel<4, 1>), dim3(a.wc1), dim3(kMsdwThreads), 0, st, a);
-      } else if (kt == 4 && g_sort_msd_wide_wc_typed) {
+      } else if (kt == 4 && wc_typed) {
         hipLaunchKernelGGL((msdw_scatter1wc2_kernel<4, 4>), dim3(a.wc1), dim3(kMsdwThreads), 0, st, a);
-      } else if (kt == 2 && g_sort_msd_wide_wc_typed) {
+      } else if (kt == 2 && wc_typed) {
         hipLaunchKernelGGL((msdw_scatter1wc2_kernel<4, 2>), dim3(a.wc1), dim3(kMsdwThreads), 0, st, a);
-      } else if (kt == 3 && g_sort_msd_wide_wc_typed) {
+      } else if (kt == 3 && wc_typed) {
         hipLaunchKernelGGL((msdw_scatter1wc2_kernel<4, 3>), dim3(a.wc1), dim3(kMsdwThreads), 0, st, a);
-      } else if (kt == 5 && g_sort_msd_wide_wc_typed) {
+      } else if (kt == 5 && wc_typed) {
         hipLaunchKernelGGL((msdw_scatter1wc2_kernel<4, 5>), dim3(a.wc1), dim3(kMsdwThreads), 0, st, a);
       } else {
         hipLaunchKernelGGL((msdw_scatter1wc2_kernel<4, -1>), dim3(a.wc1), dim3(kMsdwThreads), 0, st, a);
       }
     } else if (a.wc1 > 0) {
       // tiles of 16 rows per thread with the next tile's keys prefetched (sort_msd_wide_wc_prefetch), or rpt1 rows without
-      const int wc_rpt = g_sort_msd_wide_wc_prefetch ? (rpt1 >= 16 ? 16 : 8) : rpt1;
-      if (g_sort_msd_wide_wc_prefetch && wc_rpt == 16) {
+      const bool wc_prefetch = g_sort_msd_wide_wc_prefetch != 0;
+      const int wc_rpt = wc_prefetch ? (rpt1 >= 16 ? 16 : 8) : rpt1;
+      if (wc_prefetch && wc_rpt == 16) {
         hipLaunchKernelGGL((msdw_scatter1wc_kernel<16, true>), dim3(a.wc1), dim3(kMsdwThreads), 0, st, a);
-      } else if (g_sort_msd_wide_wc_prefetch) {
+      } else if (wc_prefetch) {
         hipLaunchKernelGGL((msdw_scatter1wc_kernel<8, true>), dim3(a.wc1), dim3(kMsdwThreads), 0, st, a);
       } else if (wc_rpt == 24) {
         hipLaunchKernelGGL((msdw_scatter1wc_kernel<24, false>), dim3(a.wc1), dim3(kMsdwThreads), 0, st, a);
@@ -3886,7 +3792,7 @@ static int run_msd_sort_wide_form(const uint64_t* src_keys, const uint32_t* src_
         set_error("array_sort_indices: internal error (exact level-1 histogram disagrees with the scatter)");
         return ARX_INVALID;
       }
-      if (g_sort_msd_wide_sample_strict) {
+      if (sample_strict) {
         set_error("array_sort_indices: sampled level-1 histogram underestimated a bucket (sort_msd_wide_sample_strict)");
         return ARX_INVALID;
       }
@@ -3957,19 +3863,20 @@ static int run_msd_sort_wide_form(const uint64_t* src_keys, const uint32_t* src_
   f.n = n;
   f.bits = a.bits;
   f.kshift = kshift;
-  f.xcd_map = g_sort_xcd_map & 2;
+  f.xcd_map = xcd_map & 2;
   f.part_start = a.part_start;
   f.part_in = a.count2;
   f.overflow = a.flags;
   f.out_final = out_final;
   const bool small_bkt = max_part <= static_cast<unsigned int>(kBktCapSmall);
-  const bool tiny_bkt = g_sort_msd_tiny_bucket != 0 && max_part <= static_cast<unsigned int>(kBktCapTiny);
+  const int tiny_bucket = g_sort_msd_tiny_bucket;
+  const bool tiny_bkt = tiny_bucket != 0 && max_part <= static_cast<unsigned int>(kBktCapTiny);
   const int cpt_bits = g_sort_msd_bucket_cpt == 8 && (tiny_bkt || small_bkt) ? 1 : 0;   // twice the sub-buckets
   f.b3 = std::max(0, std::min(std::min(lg - (g_sort_msd_final_rows_log2 - 1) - a.bits,
                                        (tiny_bkt ? 10 : small_bkt ? 11 : 12) + cpt_bits),
                               64 - kshift - a.bits));
   const uint64_t* recs = reinterpret_cast<const uint64_t*>(rec_y);
-  const bool tiny9 = tiny_bkt && g_sort_msd_tiny_bucket >= 2 && max_part <= static_cast<unsigned int>(kBktCapTiny9);
+  const bool tiny9 = tiny_bkt && tiny_bucket >= 2 && max_part <= static_cast<unsigned int>(kBktCapTiny9);
   if (a.rec8) {
     f.src_keys = src_keys;
     f.raw = raw;
@@ -4034,7 +3941,7 @@ static int run_msd_sort_wide_form(const uint64_t* src_keys, const uint32_t* src_
     g_sort_wide_rec8_given_up.fetch_add(1, std::memory_order_relaxed);
     *overflowed = 3;
   } else if ((flag & 16u) != 0) {
-    if (g_sort_msd_wide_sample_strict) {
+    if (sample_strict) {
       set_error("array_sort_indices: a level-2 room underestimated its bucket (sort_msd_wide_sample_strict)");
       return ARX_INVALID;
     }
@@ -4253,11 +4160,12 @@ int arx_sort_indices(const ArxSpan* values, int key_type, int order, int null_pl
 
   // ---- large inputs: MSD-hybrid path; falls through to the LSD passes if a bucket overflowed
   // auto: from 4M rows up; beyond 2^27 rows an extra level on the top bits cuts ~2^27-row segments
-  const bool try_msd = g_sort_msd != 0 && n_valid < (int64_t(1) << 32) - kMsdTile &&
-                       (g_sort_msd == 1 ? n_valid >= 256 : n_valid >= g_sort_msd_min_rows);
+  const int msd = g_sort_msd, msd_sampled = g_sort_msd_sampled, wide_gap2 = g_sort_msd_wide_gap2;
+  const bool try_msd = msd != 0 && n_valid < (int64_t(1) << 32) - kMsdTile &&
+                       (msd == 1 ? n_valid >= 256 : n_valid >= g_sort_msd_min_rows);
   const bool segmented = n_valid > g_sort_msd_segment_rows;
   const unsigned gprep = static_cast<unsigned>(std::min<int64_t>(ceil_div(n_valid, kBlock), 2048));
-  if (try_msd && g_sort_msd_sampled != 2) {
+  if (try_msd && msd_sampled != 2) {
     uint8_t* tables = w + plan.off_msd;
     int overflowed = 0;
     int rc;
@@ -4273,7 +4181,7 @@ int arx_sort_indices(const ArxSpan* values, int key_type, int order, int null_pl
       rc = ARX_OK;
       if (wide) {
         int rec8 = g_sort_msd_wide_rec8;
-        rc = run_msd_sort_wide(src, nullptr, xf, n_valid, rec_a, rec_b, rec_cap, tables, final_dst, g_sort_msd_wide_gap2, ks, st, &overflowed, &rec8);
+        rc = run_msd_sort_wide(src, nullptr, xf, n_valid, rec_a, rec_b, rec_cap, tables, final_dst, wide_gap2, ks, st, &overflowed, &rec8);
         if (rc == ARX_OK && overflowed == 2) {
           rc = run_msd_sort_wide(src, nullptr, xf, n_valid, rec_a, rec_b, rec_cap, tables, final_dst, 0, ks, st, &overflowed, &rec8);
         }
@@ -4298,7 +4206,7 @@ int arx_sort_indices(const ArxSpan* values, int key_type, int order, int null_pl
       // safe because level 2 only starts after level 1 has consumed the source
       if (wide) {
         int rec8 = 0;   // (a prepped source: row ids are not positions in the column)
-        rc = run_msd_sort_wide(keys_a, idx_a, 0, n_valid, rec_b, rec_a, rec_cap, tables, final_dst, g_sort_msd_wide_gap2, ks, st, &overflowed, &rec8);
+        rc = run_msd_sort_wide(keys_a, idx_a, 0, n_valid, rec_b, rec_a, rec_cap, tables, final_dst, wide_gap2, ks, st, &overflowed, &rec8);
         if (rc == ARX_OK && overflowed == 2) {   // the level-2 records went over the prepped source: rebuild it
           hipLaunchKernelGGL(sort_prep_kernel, dim3(gprep), dim3(kBlock), 0, st, vals, valid_rows, n_valid, xf, 0,
                              keys_a, idx_a);
@@ -4324,11 +4232,11 @@ int arx_sort_indices(const ArxSpan* values, int key_type, int order, int null_pl
   // skewed top bits: bucket boundaries from a sorted sample instead of equal-width prefixes
   // (sort_msd_sampled = 2 forces this form first, for the tests)
   // (32-bit keys: their 4 LSD passes measured faster than this form, 5.2 vs 7.4 ms at 2^27 rows)
-  if ((try_msd || g_sort_msd_sampled == 2) && g_sort_msd_sampled != 0 && (key_width == 8 || g_sort_msd_sampled == 2)) {
+  if ((try_msd || msd_sampled == 2) && msd_sampled != 0 && (key_width == 8 || msd_sampled == 2)) {
     uint8_t* tables = w + plan.off_msd;
     int overflowed = 0;
     int rc = ARX_OK;
-    if (n_valid >= (g_sort_msd_sampled == 2 ? 1024 : (int64_t(1) << 18)) && n_valid <= (int64_t(3) << 26)) {
+    if (n_valid >= (msd_sampled == 2 ? 1024 : (int64_t(1) << 18)) && n_valid <= (int64_t(3) << 26)) {
       if (valid_rows == nullptr) {
         rc = run_msd_sort_sampled(reinterpret_cast<const uint64_t*>(vals), nullptr, xf, n_valid, keys_a, idx_a,
                                   keys_b, idx_b, tables, hist, totals, final_dst, st, &overflowed);
@@ -4736,9 +4644,10 @@ int arx_sort_records(const ArxSortRecord* records, int64_t num_records, void* ws
     return ARX_OK;
   };
   int rc = ARX_OK;
-  const bool try_msd = g_sort_msd != 0 && n < (int64_t(1) << 32) - kMsdTile && (g_sort_msd == 1 ? n >= 256 : n >= g_sort_msd_min_rows);
+  const int msd = g_sort_msd, msd_sampled = g_sort_msd_sampled;
+  const bool try_msd = msd != 0 && n < (int64_t(1) << 32) - kMsdTile && (msd == 1 ? n >= 256 : n >= g_sort_msd_min_rows);
   const bool segmented = n > g_sort_msd_segment_rows;
-  const bool wide = try_msd && g_sort_msd_sampled != 2 && segmented && g_sort_msd_wide != 0;
+  const bool wide = try_msd && msd_sampled != 2 && segmented && g_sort_msd_wide != 0;
   // the wide form reads the records where they lie (level 1 takes 12-byte records as level 2 does): no split into a key
   // and a row array first — every other form starts from the split arrays (knob sort_records_in_place = 0: the split always)
   const MsdRec* in_place = wide && g_sort_records_in_place ? reinterpret_cast<const MsdRec*>(records) : nullptr;
@@ -4746,7 +4655,7 @@ int arx_sort_records(const ArxSortRecord* records, int64_t num_records, void* ws
     rc = prep();
     if (rc != ARX_OK) return rc;
   }
-  if (try_msd && g_sort_msd_sampled != 2) {
+  if (try_msd && msd_sampled != 2) {
     int ks = 0, overflowed = 1;
     rc = sort_shared_prefix_bits(in_place != nullptr ? nullptr : keys_a, 0, n, reinterpret_cast<unsigned long long*>(tables), st, &ks, in_place);
     if (rc != ARX_OK) return rc;
@@ -4770,7 +4679,7 @@ int arx_sort_records(const ArxSortRecord* records, int64_t num_records, void* ws
     rc = prep();
     if (rc != ARX_OK) return rc;
   }
-  if ((try_msd || g_sort_msd_sampled == 2) && g_sort_msd_sampled != 0 && n >= (g_sort_msd_sampled == 2 ? 1024 : (int64_t(1) << 18)) &&
+  if ((try_msd || msd_sampled == 2) && msd_sampled != 0 && n >= (msd_sampled == 2 ? 1024 : (int64_t(1) << 18)) &&
       n <= (int64_t(3) << 26)) {
     int overflowed = 0;
     rc = run_msd_sort_sampled(keys_a, idx_a, 0, n, keys_b, idx_b, keys_a, idx_a, tables, hist, totals, out_rows, st, &overflowed);

@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define ARX_ABI_VERSION 4
+#define ARX_ABI_VERSION 5
 
 /* arrow::StatusCode twins (cpp/src/arrow/status.h:83-107). */
 typedef enum ArxStatus {
@@ -86,11 +86,14 @@ int arx_abi_version(void);
 /* Number of HIP devices visible, or a negative ArxStatus. */
 int arx_device_count(void);
 /* Process-wide tuning knobs for A/B measurements ("filter_sparse", "groupby_partition_bits",
- * "sort_msd", ...; the list is in DESIGN.md 4.8).  Never changes results.  May be called while
- * other threads run kernels: every knob is a relaxed atomic, a call in flight uses the old or the
- * new value of each knob it reads (which of the two is unspecified).  Not part of the reference
- * interface. */
+ * "sort_msd", ...; names, defaults and ranges are the knob tables in arrow_amd/csrc, remarks in
+ * DESIGN.md 4.9).  Never changes results.  May be called while other threads run kernels:
+ * every knob is a relaxed atomic, a call in flight uses the old or the new value of each knob it
+ * reads (which of the two is unspecified).  Not part of the reference interface. */
 int arx_set_option(const char* name, int64_t value);
+/* The value a knob holds now: its default, or what the last arx_set_option stored after normalising it (a value outside
+ * a knob's range is clamped or snapped, not refused).  ARX_INVALID for an unknown or NULL name, as the setter. */
+int arx_get_option(const char* name, int64_t* out_value);
 /* Process-wide diagnostic counters (monotonic): which plan the slices of the partitioned group-by consume ran —
  * "groupby_slices_direct" / "_one_level" / "_two_level" / "_wide" / "_probe" (DESIGN.md 4.6); which record form the wide
  * sorts ran with — "sort_wide_runs", "sort_wide_rec8_runs", "sort_wide_rec8_ties" (rows that read their full key),

@@ -1,6 +1,8 @@
 """End-to-end A/B of arx_set_option knobs on configs[4] (sort 2e9) and configs[3] (group-by 4e9 / 10M keys), one
 process, interleaved.  Usage: exp_knobs.py sort|groupby "k=v k=v" "k=v" ...   (each quoted argument = one configuration;
-"" = defaults).  Every knob named anywhere is reset to its default (given as k=v in DEFAULTS env) between runs."""
+"" = defaults).  Every knob named anywhere is put back between runs to the value the library held at start
+(arx_get_option), or to its k=v in the DEFAULTS env where one is given."""
+import ctypes
 import os
 import sys
 import time
@@ -15,7 +17,12 @@ configs = sys.argv[2:] or [""]
 rows = int(os.environ.get("ROWS", 2_000_000_000 if what == "sort" else 4_000_000_000))
 dev = torch.device("cuda", 0)
 lib = amd._lib.get_lib()
-defaults = dict(kv.split("=") for kv in os.environ.get("DEFAULTS", "").split())
+defaults = {}
+for kv in " ".join(configs).split():
+    value = ctypes.c_int64()
+    assert lib.arx_get_option(kv.split("=")[0].encode(), ctypes.byref(value)) == 0, kv
+    defaults[kv.split("=")[0]] = value.value
+defaults.update(kv.split("=") for kv in os.environ.get("DEFAULTS", "").split())
 
 
 def apply(cfg):
@@ -23,7 +30,6 @@ def apply(cfg):
         assert lib.arx_set_option(k.encode(), int(v)) == 0, k
     for kv in cfg.split():
         k, v = kv.split("=")
-        assert k in defaults, f"give the default of {k} in DEFAULTS"
         assert lib.arx_set_option(k.encode(), int(v)) == 0, kv
 
 

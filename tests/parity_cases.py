@@ -788,9 +788,6 @@ def check_sort_indices(amd, arr: HostArray, order="ascending", null_placement="a
     return out
 
 
-SORT_WIDE_RPT_DEFAULT = (24, 16)   # sort.hip g_sort_msd_wide_rpt1 / rpt2
-
-
 def check_sort_wide_sampled(amd, lib, rng, n, shift, gap2=1, b2max=12, rpt=(24, 16), typed_keys=False):
     """The wide two-level sort with level-1 bucket sizes ESTIMATED from one tile in 2^shift (buckets get room to spare,
     level 2 reads what arrived) and, gap2, level-2 buckets in fixed rooms (mean + 6 sigma) instead of a histogram
@@ -802,12 +799,9 @@ def check_sort_wide_sampled(amd, lib, rng, n, shift, gap2=1, b2max=12, rpt=(24, 
     level-2 scatter tiles (8: LDS-resident tile; 16 / 24: register-staged, moved through LDS in rounds)."""
     opts = {b"sort_msd": 1, b"sort_msd_segment_rows": 4096, b"sort_msd_wide": 1,
             b"sort_msd_wide_sample_shift": shift, b"sort_msd_wide_gap2": gap2, b"sort_msd_wide_b2max": b2max,
-            b"sort_msd_wide_rpt1": rpt[0], b"sort_msd_wide_rpt2": rpt[1]}
-    for k, v in opts.items():
-        assert lib.arx_set_option(k, v) == 0
-    try:
+            b"sort_msd_wide_rpt1": rpt[0], b"sort_msd_wide_rpt2": rpt[1], b"sort_msd_wide_sample_strict": 1}
+    with util.options(lib, opts):
         uniform = util.random_array(rng, np.uint64, n, offset=5)
-        assert lib.arx_set_option(b"sort_msd_wide_sample_strict", 1) == 0
         check_sort_indices(amd, uniform, "ascending", "at_end", use_pyarrow=False)
         signed = util.random_array(rng, np.int64, n, null_p=0.02)
         check_sort_indices(amd, signed, "descending", "at_start", use_pyarrow=False)
@@ -834,15 +828,6 @@ def check_sort_wide_sampled(amd, lib, rng, n, shift, gap2=1, b2max=12, rpt=(24, 
             typed = util.random_array(rng, dtype, min(n, 2_000_000) // 8 + 17, null_p=0.02, offset=1)
             check_sort_indices(amd, typed, "descending" if dtype == np.int32 else "ascending", "at_end", use_pyarrow=False)
         return failed
-    finally:
-        lib.arx_set_option(b"sort_msd_wide_sample_strict", 0)
-        lib.arx_set_option(b"sort_msd_wide_sample_shift", 4)
-        lib.arx_set_option(b"sort_msd_wide_gap2", 1)
-        lib.arx_set_option(b"sort_msd_wide_rpt1", SORT_WIDE_RPT_DEFAULT[0])
-        lib.arx_set_option(b"sort_msd_wide_rpt2", SORT_WIDE_RPT_DEFAULT[1])
-        lib.arx_set_option(b"sort_msd_wide_b2max", 11)
-        lib.arx_set_option(b"sort_msd", -1)
-        lib.arx_set_option(b"sort_msd_segment_rows", 1 << 27)
 
 
 def check_sort_wide_many_bins(amd, lib, rng, n, bits, b2max, combos=((2, 1), (0, 1), (0, 0)), rpt=(24, 16)):
@@ -851,10 +836,9 @@ def check_sort_wide_many_bins(amd, lib, rng, n, bits, b2max, combos=((2, 1), (0,
     scan and in the fixed-room setup.  Exact and sampled sizes, fixed rooms and counted buckets, a skewed input (whole
     partitions empty, one bin holding a third of the rows), nulls, both orders."""
     opts = {b"sort_msd": 1, b"sort_msd_segment_rows": 4096, b"sort_msd_wide": 1, b"sort_msd_wide_bits": bits,
-            b"sort_msd_wide_b2max": b2max, b"sort_msd_wide_rpt1": rpt[0], b"sort_msd_wide_rpt2": rpt[1]}
-    for k, v in opts.items():
-        assert lib.arx_set_option(k, v) == 0
-    try:
+            b"sort_msd_wide_b2max": b2max, b"sort_msd_wide_rpt1": rpt[0], b"sort_msd_wide_rpt2": rpt[1],
+            b"sort_msd_wide_sample_shift": combos[0][0], b"sort_msd_wide_gap2": combos[0][1]}
+    with util.options(lib, opts):
         for shift, gap2 in combos:
             assert lib.arx_set_option(b"sort_msd_wide_sample_shift", shift) == 0
             assert lib.arx_set_option(b"sort_msd_wide_gap2", gap2) == 0
@@ -867,15 +851,6 @@ def check_sort_wide_many_bins(amd, lib, rng, n, bits, b2max, combos=((2, 1), (0,
             v[: n // 3] = (v[: n // 3] & np.uint64((1 << 40) - 1)) | np.uint64(0x5A5A << 48)   # one bin, a third of the rows
             v[n // 3: n // 2] >>= np.uint64(9)                                                  # the lowest partitions only
             check_sort_indices(amd, skew, "ascending", "at_end", use_pyarrow=False)
-    finally:
-        lib.arx_set_option(b"sort_msd_wide_bits", 0)
-        lib.arx_set_option(b"sort_msd_wide_b2max", 11)
-        lib.arx_set_option(b"sort_msd_wide_rpt1", SORT_WIDE_RPT_DEFAULT[0])
-        lib.arx_set_option(b"sort_msd_wide_rpt2", SORT_WIDE_RPT_DEFAULT[1])
-        lib.arx_set_option(b"sort_msd_wide_sample_shift", 4)
-        lib.arx_set_option(b"sort_msd_wide_gap2", 1)
-        lib.arx_set_option(b"sort_msd", -1)
-        lib.arx_set_option(b"sort_msd_segment_rows", 1 << 27)
 
 
 def check_sort_wide_rec8(amd, lib, rng, n, bits=0, gap2=1, shift=0, rpt=(24, 16), b2max=11, wc=256, prefetch=1, l2w=1, wc_form=2,
@@ -898,8 +873,6 @@ def check_sort_wide_rec8(amd, lib, rng, n, bits=0, gap2=1, shift=0, rpt=(24, 16)
             b"sort_msd_wide_rpt2": rpt[1], b"sort_msd_wide_rec8": 1, b"sort_msd_wide_rec8_tie_shift": 0,
             b"sort_msd_wide_b2max": b2max, b"sort_msd_wide_wc": wc, b"sort_msd_wide_wc_prefetch": prefetch,
             b"sort_msd_wide_l2w": l2w, b"sort_msd_wide_wc_form": wc_form, b"sort_msd_wide_wc_min_rows": wc_min_rows}
-    for k, v in opts.items():
-        assert lib.arx_set_option(k, v) == 0
     ctr = lambda name: int(lib.arx_get_counter(name))
 
     def run(arr, order="ascending", placement="at_end"):
@@ -908,7 +881,7 @@ def check_sort_wide_rec8(amd, lib, rng, n, bits=0, gap2=1, shift=0, rpt=(24, 16)
         check_sort_indices(amd, arr, order, placement, use_pyarrow=False)
         return {c.decode()[10:]: ctr(c) - v for c, v in before.items()}
 
-    try:
+    with util.options(lib, opts):
         uniform = util.random_array(rng, np.uint64, n, offset=3)
         d = run(uniform)
         assert d["runs"] == 1 and d["rec8_runs"] == 1 and d["rec8_given_up"] == 0, d
@@ -955,32 +928,15 @@ def check_sort_wide_rec8(amd, lib, rng, n, bits=0, gap2=1, shift=0, rpt=(24, 16)
         assert lib.arx_set_option(b"sort_msd_wide_rec8", 0) == 0
         d = run(below)
         assert d["runs"] == 1 and d["rec8_runs"] == 0, d
-    finally:
-        lib.arx_set_option(b"sort_msd_wide_rec8", 1)
-        lib.arx_set_option(b"sort_msd_wide_rec8_tie_shift", 4)
-        lib.arx_set_option(b"sort_msd_wide_wc", 256)
-        lib.arx_set_option(b"sort_msd_wide_wc_prefetch", 1)
-        lib.arx_set_option(b"sort_msd_wide_wc_form", 2)
-        lib.arx_set_option(b"sort_msd_wide_wc_min_rows", 1 << 17)
-        lib.arx_set_option(b"sort_msd_wide_l2w", 3)
-        lib.arx_set_option(b"sort_msd_wide_b2max", 11)
-        lib.arx_set_option(b"sort_msd_wide_bits", 0)
-        lib.arx_set_option(b"sort_msd_wide_rpt1", SORT_WIDE_RPT_DEFAULT[0])
-        lib.arx_set_option(b"sort_msd_wide_rpt2", SORT_WIDE_RPT_DEFAULT[1])
-        lib.arx_set_option(b"sort_msd_wide_sample_shift", 4)
-        lib.arx_set_option(b"sort_msd_wide_gap2", 1)
-        lib.arx_set_option(b"sort_msd", -1)
-        lib.arx_set_option(b"sort_msd_segment_rows", 1 << 27)
 
 
 def check_sort_limited_range(amd, lib, rng, n, wide, light=False):
     """Keys that share their top bits (row ids, timestamps, small or clustered integers): the MSD forms must take their
     digits below the shared prefix (sort_msd_prefix) — same order as the oracle with the knob on and off, ascending and
     descending, signed and unsigned, with nulls, for the hybrid form and (wide) the wide two-level form."""
-    opts = {b"sort_msd": 1, b"sort_msd_segment_rows": 4096 if wide else 1 << 27, b"sort_msd_wide": 1 if wide else 0}
-    for k, v in opts.items():
-        assert lib.arx_set_option(k, v) == 0
-    try:
+    opts = {b"sort_msd": 1, b"sort_msd_segment_rows": 4096 if wide else 1 << 27, b"sort_msd_wide": 1 if wide else 0,
+            b"sort_msd_prefix": 1}
+    with util.options(lib, opts):
         cases = [(np.uint64, 0, 1 << 40), (np.uint64, (1 << 62) + 12345, 1 << 33), (np.int64, -(1 << 35), 1 << 36),
                  (np.int64, 1_700_000_000_000_000, 86_400_000_000), (np.uint64, 0, 1 << 63), (np.int64, -5, 11),
                  (np.uint64, 77, 1)]
@@ -995,11 +951,6 @@ def check_sort_limited_range(amd, lib, rng, n, wide, light=False):
                 arr = HostArray(vals.astype(dtype), valid, 0, n)
                 for order, placement in (("ascending", "at_end"), ("descending", "at_start")):
                     check_sort_indices(amd, arr, order, placement, use_pyarrow=False)
-    finally:
-        lib.arx_set_option(b"sort_msd_prefix", 1)
-        lib.arx_set_option(b"sort_msd", -1)
-        lib.arx_set_option(b"sort_msd_segment_rows", 1 << 27)
-        lib.arx_set_option(b"sort_msd_wide", 1)
 
 
 # ------------------------------------------------------------------ group-by
@@ -2189,9 +2140,7 @@ def check_sort_records(amd, rng, n, options=(), ties=True):
     from arrow_amd.array import alloc, current_stream, default_device, to_device
 
     lib, dev = _lib.get_lib(), default_device()
-    for k_, v_ in options:
-        assert lib.arx_set_option(k_, v_) == 0, k_
-    try:
+    with util.options(lib, dict(options)):
         keys = rng.integers(0, 2**64, size=n, dtype=np.uint64)
         if ties:
             keys[::3] = keys[::3] % np.uint64(50)
@@ -2222,10 +2171,6 @@ def check_sort_records(amd, rng, n, options=(), ties=True):
         else:
             got = out[:n].cpu().numpy().view(np.uint64)
             assert_equal(got, want, f"arx_sort_records n={n} options={options}")
-    finally:
-        for k_, v_ in options:
-            lib.arx_set_option(k_, {b"sort_msd": -1, b"sort_msd_sampled": 1, b"sort_msd_segment_rows": 1 << 27, b"sort_msd_wide": 1,
-                                    b"sort_msd_wide_bits": 0}.get(k_, 0))
 
 
 def _gbl_sampled_unit(s, stride):
@@ -2248,9 +2193,7 @@ def check_groupby_lines_plan(amd, rng_for, scale=1, wide_width=True):
     ctr = lambda name: int(lib.arx_get_counter(name))      # noqa: E731
     knobs = {b"groupby_partition_min_rows": 0, b"groupby_lines_min_rows": 1, b"groupby_lines_wgs": 2,
              b"groupby_lines_unit_rows": 4096, b"groupby_lines_sample_rows": 1 << 24}
-    for k_, v_ in knobs.items():
-        assert lib.arx_set_option(k_, v_) == 0, k_
-    try:
+    with util.options(lib, knobs):
         n = 30000 * scale
         # 1. uniform ids, no nulls, one consume: the plan runs (full histogram: n < the sample)
         s0, f0, d0 = ctr(b"groupby_slices_lines"), ctr(b"groupby_lines_fallbacks"), ctr(b"groupby_lines_declined")
@@ -2269,24 +2212,21 @@ def check_groupby_lines_plan(amd, rng_for, scale=1, wide_width=True):
             assert ctr(b"groupby_slices_lines") == s1 + 2
         # 3. a sampled histogram (one 64-row unit in 8) and rows outside the sampled range: keys far away in a unit the
         #    sample does not read are counted by the scatter and consumed by their own pass
-        assert lib.arx_set_option(b"groupby_lines_sample_rows", max(64, n // 8)) == 0
-        assert lib.arx_set_option(b"groupby_lines_range_sample_rows", max(64, n // 8)) == 0
-        stride = max(1, n // max(64, n // 8))
-        assert stride > 1
-        sampled = {_gbl_sampled_unit(s, stride) for s in range((n + 63) // 64 // stride + 2)}
-        unit = next(u for u in range(5, n // 64 - 1) if u not in sampled)
-        for null_p in (0.0, 0.05):
-            rng = rng_for("gbl", 3, null_p)
-            k = util.random_array(rng, np.int32, n, null_p=null_p, lo=1000, hi=200000)
-            v = util.random_array(rng, np.int64, n, null_p=null_p)
-            far = np.array([2**30 + 7, -2**31, 2**31 - 1, 2**30 + 7, -5], np.int32)
-            k.values[k.offset + unit * 64 + 3: k.offset + unit * 64 + 3 + len(far)] = far
-            s1, o1 = ctr(b"groupby_slices_lines"), ctr(b"groupby_lines_outlier_rows")
-            check_groupby_sum(amd, k, v, use_pyarrow=False)
-            assert ctr(b"groupby_slices_lines") == s1 + 1
-            assert ctr(b"groupby_lines_outlier_rows") - o1 >= (3 if null_p else 4), "the far keys are outside the sampled range"
-        assert lib.arx_set_option(b"groupby_lines_sample_rows", 1 << 24) == 0
-        assert lib.arx_set_option(b"groupby_lines_range_sample_rows", 1 << 20) == 0
+        with util.options(lib, {b"groupby_lines_sample_rows": max(64, n // 8), b"groupby_lines_range_sample_rows": max(64, n // 8)}):
+            stride = max(1, n // max(64, n // 8))
+            assert stride > 1
+            sampled = {_gbl_sampled_unit(s, stride) for s in range((n + 63) // 64 // stride + 2)}
+            unit = next(u for u in range(5, n // 64 - 1) if u not in sampled)
+            for null_p in (0.0, 0.05):
+                rng = rng_for("gbl", 3, null_p)
+                k = util.random_array(rng, np.int32, n, null_p=null_p, lo=1000, hi=200000)
+                v = util.random_array(rng, np.int64, n, null_p=null_p)
+                far = np.array([2**30 + 7, -2**31, 2**31 - 1, 2**30 + 7, -5], np.int32)
+                k.values[k.offset + unit * 64 + 3: k.offset + unit * 64 + 3 + len(far)] = far
+                s1, o1 = ctr(b"groupby_slices_lines"), ctr(b"groupby_lines_outlier_rows")
+                check_groupby_sum(amd, k, v, use_pyarrow=False)
+                assert ctr(b"groupby_slices_lines") == s1 + 1
+                assert ctr(b"groupby_lines_outlier_rows") - o1 >= (3 if null_p else 4), "the far keys are outside the sampled range"
         # 4. a hot key: the scatter would need hundreds of rounds per batch — it gives up, nothing consumed, the other plans run
         rng = rng_for("gbl", 4)
         k = util.random_array(rng, np.int32, n, lo=0, hi=50000)
@@ -2317,11 +2257,6 @@ def check_groupby_lines_plan(amd, rng_for, scale=1, wide_width=True):
         v = util.random_array(rng, np.int64, n, lo=2**62, hi=2**63 - 1)
         check_groupby_sum(amd, k, v, use_pyarrow=False)
         assert d0 <= ctr(b"groupby_lines_declined")
-    finally:
-        for k_, v_ in {b"groupby_partition_min_rows": 1 << 17, b"groupby_lines_min_rows": 1 << 22, b"groupby_lines_wgs": 0,
-                       b"groupby_lines_unit_rows": 1 << 21, b"groupby_lines_sample_rows": 1 << 24,
-                       b"groupby_lines_range_sample_rows": 1 << 20}.items():
-            lib.arx_set_option(k_, v_)
 
 
 def check_groupby_range_state(amd, rng_for, scale=1):
@@ -2334,9 +2269,7 @@ def check_groupby_range_state(amd, rng_for, scale=1):
 
     R = amd.compute.RangeGroupBySum
     lib = amd._lib.get_lib()
-    for k_, v_ in {b"groupby_lines_wgs": 2, b"groupby_lines_unit_rows": 4096}.items():
-        assert lib.arx_set_option(k_, v_) == 0
-    try:
+    with util.options(lib, {b"groupby_lines_wgs": 2, b"groupby_lines_unit_rows": 4096}):
         n = 25000 * scale
         for lo, hi, min_count in ((0, 40000, 1), (-70000, -20000, 3), (5, 9_700_000 if scale > 1 else 300_000, 1)):
             rng = rng_for("range-state", lo, hi)
@@ -2394,9 +2327,6 @@ def check_groupby_range_state(amd, rng_for, scale=1):
         assert R.plan_for(n, 0, 3000, sampled=False) is None and R.plan_for(n, -2**31, 2**31 - 1, sampled=False) is None
         assert R.plan_for(n, 0, 3071, sampled=False).width == 8
         assert R.plan_for(n, 0, 1216 * 12288 - 1, sampled=False) is not None and R.plan_for(n, 0, 1216 * 12288, sampled=False) is None
-    finally:
-        lib.arx_set_option(b"groupby_lines_wgs", 0)
-        lib.arx_set_option(b"groupby_lines_unit_rows", 1 << 21)
 
 
 def check_hash_minmax_count_kernels(amd, rng, n=5000, num_groups=37, null_p=0.2):

@@ -244,3 +244,167 @@ def test_concatenate_and_delta_argument_checks(emu_ctx):
                                            None, 2, data.data_ptr(), None, None) == INVALID                   # misaligned suffix bytes
     assert lib.arx_delta_byte_array_expand(prefix.data_ptr(), soff.data_ptr(), suffix.data_ptr(), 9, ooff.data_ptr(), 100, first.data_ptr(),
                                            sfirst.data_ptr(), 2, data.data_ptr(), None, None) == INVALID      # a check without a state word
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The tuning knobs (arx_set_option / arx_get_option).  One row per knob: name, default, probes (value given, value
+# stored).  The numbers are the contract: they were written down from the setters and the Knob initialisers as they
+# stood before the knobs moved into tables, NOT read back from the library — a default or a range that changes in
+# arrow_amd/csrc must be changed here by hand too.
+I32_MAX = 2**31 - 1
+GB_HARD_MAX_SLICE = (1 << 32) - (1 << 26)
+BOOL = ((-1, 1), (0, 0), (1, 1), (2, 1))
+TRI = ((-5, -1), (-1, -1), (0, 0), (1, 1), (7, 1))
+RPT = ((-3, 8), (0, 8), (8, 8), (12, 8), (16, 16), (20, 16), (24, 24), (100, 24))
+SLICE_ROWS = ((0, 4096), (4096, 4096), (5000, 4096), (98304 + 5, 98304), (1 << 30, 1 << 30), (GB_HARD_MAX_SLICE, GB_HARD_MAX_SLICE),
+              (GB_HARD_MAX_SLICE + 1, GB_HARD_MAX_SLICE), (1 << 40, GB_HARD_MAX_SLICE))
+ANY_INT = ((-7, -7), (-1, -1), (0, 0), (9, 9), (100, 100), (I32_MAX, I32_MAX), (2**32 + 5, 5))     # stored as given, truncated to int
+
+
+def _pow2_probes(lo, hi):
+    """The next power of two within 2^lo .. 2^hi: below the range, every power (each a snap point, stored as given), one
+    value just above each power (stored as the next one, or as 2^hi), far above."""
+    inside = tuple(p for k in range(lo, hi + 1) for p in ((1 << k, 1 << k), ((1 << k) + 1, 1 << min(k + 1, hi))))
+    return ((-1, 1 << lo), (0, 1 << lo)) + inside + ((1 << 40, 1 << hi),)
+
+
+KNOBS = (
+    # sort.hip
+    (b"sort_msd", -1, TRI),
+    (b"sort_msd_min_rows", 1 << 22, ((0, 256), (256, 256), (1 << 22, 1 << 22), (I32_MAX, I32_MAX), (2**31, I32_MAX), (2**40, I32_MAX))),
+    (b"sort_msd_sampled", 1, ((-1, 0), (0, 0), (1, 1), (2, 2), (3, 2))),
+    (b"sort_msd_fused", 1, BOOL),
+    (b"sort_msd_segment_rows", 1 << 27, ((0, 1024), (1023, 1024), (1024, 1024), (1 << 27, 1 << 27), (1 << 40, 1 << 40))),
+    (b"sort_msd_final_rows_log2", 1, ((0, 1), (1, 1), (8, 8), (9, 8))),
+    (b"sort_msd_small_bucket", 1, BOOL),
+    (b"sort_msd_wide_sample_shift", 6, ((-1, 0), (0, 0), (6, 6), (8, 8), (9, 8))),
+    (b"sort_xcd_map", 1, ((-1, 0), (0, 0), (1, 1), (7, 7), (8, 7))),
+    (b"sort_msd_wide_bits", 0, ((-1, 0), (0, 0), (20, 20), (21, 20))),
+    (b"sort_msd_wide_b2max", 11, ((-1, 0), (0, 0), (11, 11), (12, 12), (13, 12))),
+    (b"sort_msd_wide_rpt1", 24, RPT),
+    (b"sort_msd_wide_rpt2", 16, RPT),
+    (b"sort_msd_tiny_bucket", 2, ((-1, 0), (0, 0), (2, 2), (3, 2))),
+    (b"sort_msd_bucket_cpt", 4, ((-1, 4), (0, 4), (4, 4), (6, 4), (7, 4), (8, 8), (100, 8))),
+    (b"sort_msd_prefix", 1, BOOL),
+    (b"sort_msd_wide_gap2", 1, BOOL),
+    (b"sort_msd_wide_rec8", 1, BOOL),
+    (b"sort_msd_wide_rec8_tie_shift", 4, ((-1, 0), (0, 0), (4, 4), (40, 40), (41, 40))),
+    (b"sort_msd_wide_wc", 256, ((-1, 0), (0, 0), (256, 256), (4096, 4096), (4097, 4096))),
+    (b"sort_records_in_place", 1, BOOL),
+    (b"sort_vary_sample_shift", 6, ((0, 1), (1, 1), (6, 6), (8, 8), (9, 8))),
+    (b"sort_msd_wide_wc_typed", 1, ((-1, 1), (0, 0), (1, 1), (2, 2), (3, 1))),
+    (b"sort_msd_wide_wc_form", 2, ((-1, 2), (0, 2), (1, 1), (2, 2), (3, 2))),
+    (b"sort_msd_wide_wc_rows", 4, ((0, 4), (4, 4), (5, 4), (6, 6), (7, 4), (8, 8), (9, 4))),
+    (b"sort_msd_wide_wc_min_rows", 1 << 17, ((0, 1), (1, 1), (1 << 17, 1 << 17), (1 << 30, 1 << 30), ((1 << 30) + 1, 1 << 30))),
+    (b"sort_msd_wide_wc_prefetch", 1, BOOL),
+    (b"sort_msd_wide_l2w", 3, ((-1, 0), (0, 0), (3, 3), (4, 3))),
+    (b"sort_msd_wide_sample_strict", 0, BOOL),
+    (b"sort_msd_wide", 1, BOOL),
+    (b"sort_msd_bucket_v2", 1, BOOL),
+    (b"sort_msd_seg_min_bits", 1, ((0, 1), (1, 1), (7, 7), (8, 7))),
+    (b"sort_msd_global_bits", 14, ((1, 2), (2, 2), (14, 14), (15, 14))),
+    (b"sort_fuse_prep", 1, BOOL),
+    (b"sort_chunks", 2048, ((0, 1), (1, 1), (2048, 2048), (16384, 16384), (16385, 16384))),
+    # selection.hip
+    (b"filter_batch", 4, ((-1, 1), (0, 1), (1, 1), (3, 1), (4, 4), (9, 4))),
+    (b"filter_pipe", 1, BOOL),
+    (b"filter_sparse", -1, TRI),
+    # parquet.hip
+    (b"snappy_lds", -1, TRI),
+    # groupby.hip
+    (b"groupby_partition_min_rows", 1 << 17, ((-1, 0), (0, 0), (1 << 17, 1 << 17), (I32_MAX, I32_MAX), (2**31, I32_MAX))),
+    (b"groupby_partition_bits", -1, ANY_INT),
+    (b"groupby_agg_pipe", 1, BOOL),
+    (b"groupby_xcd_map", 1, ((-1, 0), (0, 0), (1, 1), (7, 7), (8, 7))),
+    (b"groupby_b1", -1, ANY_INT),
+    (b"groupby_chunks", 2048, ((0, 1), (1, 1), (2048, 2048), (4096, 4096), (4097, 4096))),
+    (b"groupby_wide_max_bits", 11, ((0, 1), (1, 1), (11, 11), (12, 11))),
+    (b"groupby_wide_room_min_mean", 1 << 14, ((0, 1), (1, 1), (1 << 14, 1 << 14), (I32_MAX, I32_MAX), (2**31, I32_MAX))),
+    (b"groupby_sketch", 1, BOOL),
+    (b"groupby_stripe", 0, ((-4, 0), (0, 0), (1, 4), (3, 4), (4, 4), (7, 4), (68, 68), (70, 68), (1 << 20, 1 << 20), ((1 << 20) + 4, 1 << 20))),
+    (b"groupby_wide_rooms", 1, BOOL),
+    (b"groupby_wide", 1, ((-1, 0), (0, 0), (1, 1), (2, 2), (3, 2))),
+    (b"groupby_wide_agg_chunk_rows", 1 << 21, _pow2_probes(14, 26) + ((3 << 20, 1 << 22),)),
+    (b"groupby_probe_rows", 1 << 25, ((0, 4096), (4095, 4096), (4096, 4096), (1 << 25, 1 << 25), (1 << 40, 1 << 40))),
+    (b"groupby_l1_global", 1, BOOL),
+    (b"groupby_max_slice_rows", 1 << 30, SLICE_ROWS),
+    (b"groupby_wide_max_slice_rows", GB_HARD_MAX_SLICE, SLICE_ROWS),
+    (b"groupby_agg_chunk_rows", 1 << 18, _pow2_probes(12, 24) + ((3 << 17, 1 << 19),)),
+    # groupby_lines.h
+    (b"groupby_lines", 1, BOOL),
+    (b"groupby_lines_min_rows", 1 << 22, ((-5, 1), (0, 1), (1, 1), (1 << 22, 1 << 22), (1 << 40, 1 << 40))),
+    (b"groupby_lines_sample_rows", 1 << 24, ((0, 64), (63, 64), (64, 64), (1 << 24, 1 << 24), (1 << 40, 1 << 40))),
+    (b"groupby_lines_range_sample_rows", 1 << 20, ((0, 64), (63, 64), (64, 64), (1 << 20, 1 << 20), (1 << 40, 1 << 40))),
+    (b"groupby_lines_unit_rows", 1 << 21, ((0, 768), (767, 768), (768, 768), (1 << 21, 1 << 21), (1 << 30, 1 << 30), ((1 << 30) + 1, 1 << 30))),
+    (b"groupby_lines_wgs", 0, ((-1, 0), (0, 0), (4096, 4096), (4097, 4096))),
+)
+COUNTERS = (b"groupby_slices_direct", b"groupby_slices_one_level", b"groupby_slices_two_level", b"groupby_slices_wide",
+            b"groupby_slices_probe", b"groupby_slices_rooms", b"groupby_rooms_overflows", b"groupby_slices_lines",
+            b"groupby_lines_fallbacks", b"groupby_lines_declined", b"groupby_lines_outlier_rows", b"sort_wide_runs",
+            b"sort_wide_rec8_runs", b"sort_wide_rec8_ties", b"sort_wide_rec8_given_up", b"sort_wide_wc_runs",
+            b"sort_wide_wc_given_up", b"set_lookup_lds_probes", b"set_lookup_global_probes")
+
+
+def _check_knob_table(lib):
+    import os
+    import re
+
+    from . import util as U
+
+    names = [k[0] for k in KNOBS]
+    assert len(names) == len(set(names)) == 63
+    # every knob DESIGN.md 4.9 speaks of is in the table
+    design = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "DESIGN.md")).read()
+    sec = design[design.index("### 4.9 A/B knobs"):]
+    sec = sec[:sec.index("\n### ", 4)]
+    for word in re.findall(r"`((?:filter|sort|groupby|snappy)_[a-z0-9_]+)`", sec):
+        assert word.encode() in names, word
+    out = C.c_int64(-12345)
+    for name, default, probes in KNOBS:
+        # (a) the name is a knob, a misspelling of it is not — for the getter and the setter alike
+        for wrong in (name + b"_", name[:-1] + b"0"):
+            assert lib.arx_get_option(wrong, C.byref(out)) == INVALID and _err(lib) == "unknown option '%s'" % wrong.decode()
+            assert lib.arx_set_option(wrong, 1) == INVALID and _err(lib) == "unknown option '%s'" % wrong.decode()
+        # (b) untouched, it holds its default
+        assert U.get_option(lib, name) == default, name
+        # (c) what is stored for what is given
+        assert any(given == default and stored == default for given, stored in probes), name
+        with U.options(lib, {name: default}):
+            for given, stored in probes:
+                assert lib.arx_set_option(name, given) == OK, (name, given)
+                assert U.get_option(lib, name) == stored, (name, given, stored, U.get_option(lib, name))
+                # ... and for no other knob (two rows on one variable would show here)
+                if stored != default:
+                    moved = [other for other, d, _ in KNOBS if other != name and U.get_option(lib, other) != d]
+                    assert not moved, (name, given, moved)
+    assert lib.arx_get_option(None, C.byref(out)) == INVALID and lib.arx_set_option(None, 1) == INVALID
+    assert lib.arx_get_option(names[0], None) == INVALID
+    # (d) and every knob is back at its default
+    for name, default, _ in KNOBS:
+        assert U.get_option(lib, name) == default, name
+
+
+def _check_counters(lib):
+    for name in COUNTERS:
+        assert lib.arx_get_counter(name) >= 0, name
+    for wrong in (b"sort_wide_run", b"groupby_slices", b""):
+        assert lib.arx_get_counter(wrong) == -1 and _err(lib) == "unknown counter '%s'" % wrong.decode()
+    assert lib.arx_get_counter(None) == -1 and _err(lib) == "unknown counter '(null)'"
+
+
+def test_knob_table(emu_ctx):
+    _check_knob_table(emu_ctx._lib.get_lib())
+
+
+def test_counter_names(emu_ctx):
+    _check_counters(emu_ctx._lib.get_lib())
+
+
+@pytest.mark.gpu
+def test_knob_table_on_the_device_library(gpu_ctx):
+    _check_knob_table(gpu_ctx._lib.get_lib())
+
+
+@pytest.mark.gpu
+def test_counter_names_on_the_device_library(gpu_ctx):
+    _check_counters(gpu_ctx._lib.get_lib())

@@ -67,16 +67,13 @@ def test_filter_dense_and_batch_variants(emu_ctx):
     rng = rng_for("fvariants")
     v = U.random_array(rng, np.int64, 9000, null_p=0.1, offset=2)
     m = U.random_mask(rng, 9000, 0.1, null_p=0.05)
-    try:
+    with U.options(lib, {b"filter_batch": 1, b"filter_pipe": 0}):
         for batch in (1, 4):
             for pipe in (0, 1):
                 assert lib.arx_set_option(b"filter_batch", batch) == 0
                 assert lib.arx_set_option(b"filter_pipe", pipe) == 0
                 for sel in ("drop", "emit_null"):
                     P.check_filter(emu_ctx, v, m, sel, use_pyarrow=False)
-    finally:
-        lib.arx_set_option(b"filter_batch", 4)
-        lib.arx_set_option(b"filter_pipe", 1)
 
 
 def test_filter_no_nulls_has_no_validity(emu_ctx):
@@ -295,12 +292,9 @@ def test_hash_sum_kernel_partitioned_by_group_id(emu_ctx, num_groups, n):
     of the dense group id, LDS aggregation, one flush per partition — no partition level (<= 2048 ids), one level,
     two levels; null values, hot groups, several consumes into the same state.  Same results as the per-row form."""
     lib = emu_ctx._lib.get_lib()
-    assert lib.arx_set_option(b"groupby_partition_min_rows", 0) == 0
-    try:
+    with U.options(lib, {b"groupby_partition_min_rows": 0}):
         P.check_hash_sum_kernel(emu_ctx, rng_for("hskp", num_groups), n=n, num_groups=num_groups, null_p=0.1,
                                 use_pyarrow=False)
-    finally:
-        lib.arx_set_option(b"groupby_partition_min_rows", 1 << 17)
 
 
 def test_hash_sum_kernel_no_nulls_has_no_bitmap(emu_ctx):
@@ -312,8 +306,7 @@ def test_filter_forced_sweep_and_sparse_forms(emu_ctx, mode):
     """filter_sparse = 0 forces the sweeping compaction, 1 the gather form, for EVERY selectivity,
     null density, offset, width and length class: both must be bit-exact (auto picks by S/N)."""
     lib = emu_ctx._lib.get_lib()
-    assert lib.arx_set_option(b"filter_sparse", mode) == 0
-    try:
+    with U.options(lib, {b"filter_sparse": mode}):
         for n in (1, 63, 64, 65, 4095, 4096, 4097, 9000):
             for sel in ("drop", "emit_null"):
                 rng = rng_for("fform", n, sel)
@@ -332,8 +325,6 @@ def test_filter_forced_sweep_and_sparse_forms(emu_ctx, mode):
             v = U.random_array(rng, dtype, 12345, null_p=0.1, offset=3)
             m = U.random_mask(rng, 12345, 0.15, null_p=0.05, offset=1)
             P.check_filter(emu_ctx, v, m, "emit_null", use_pyarrow=False)
-    finally:
-        lib.arx_set_option(b"filter_sparse", -1)
 
 
 @pytest.mark.parametrize("l1_global,agg_chunk,bits", [(0, 1 << 16, 9), (1, 1 << 12, 9), (0, 1 << 20, 5), (1, 1 << 18, 11)])
@@ -343,9 +334,7 @@ def test_groupby_partition_knobs(emu_ctx, l1_global, agg_chunk, bits):
     lib = emu_ctx._lib.get_lib()
     opts = {b"groupby_partition_min_rows": 0, b"groupby_partition_bits": bits, b"groupby_l1_global": l1_global,
             b"groupby_agg_chunk_rows": agg_chunk}
-    for k_, v_ in opts.items():
-        assert lib.arx_set_option(k_, v_) == 0
-    try:
+    with U.options(lib, opts):
         rng = rng_for("gbpknobs", l1_global, agg_chunk, bits)
         n = 20000
         k = U.random_array(rng, np.int32, n, null_p=0.02, offset=3, lo=-2**31, hi=2**31 - 1)
@@ -355,10 +344,6 @@ def test_groupby_partition_knobs(emu_ctx, l1_global, agg_chunk, bits):
         k2 = U.random_array(rng, np.int32, n, lo=0, hi=50000)
         v2 = U.random_array(rng, np.int64, n)
         P.check_groupby_sum(emu_ctx, k2, v2, use_pyarrow=False)
-    finally:
-        for k_, v_ in {b"groupby_partition_min_rows": 1 << 17, b"groupby_partition_bits": -1, b"groupby_l1_global": 1,
-                       b"groupby_agg_chunk_rows": 1 << 18}.items():
-            lib.arx_set_option(k_, v_)
 
 
 @pytest.mark.parametrize("n,options", [(0, ()), (1, ()), (9000, ()), (30000, ((b"sort_msd", 1),)),
@@ -388,9 +373,7 @@ def test_groupby_partitioned_path(emu_ctx, bits):
     forced on, for one-level (bits <= 8) and two-level plans, with null keys / null values /
     wrap-around, several consume calls, and keys that overflow one partition's LDS table."""
     lib = emu_ctx._lib.get_lib()
-    assert lib.arx_set_option(b"groupby_partition_min_rows", 0) == 0
-    assert lib.arx_set_option(b"groupby_partition_bits", bits) == 0
-    try:
+    with U.options(lib, {b"groupby_partition_min_rows": 0, b"groupby_partition_bits": bits}):
         rng = rng_for("gbp", bits)
         n = 20000
         k = U.random_array(rng, np.int32, n, null_p=0.02, offset=3, lo=-2**31, hi=2**31 - 1)
@@ -402,9 +385,6 @@ def test_groupby_partitioned_path(emu_ctx, bits):
         k2 = U.random_array(rng, np.int32, n, lo=0, hi=50000)
         v2 = U.random_array(rng, np.int64, n)
         P.check_groupby_sum(emu_ctx, k2, v2, use_pyarrow=False)
-    finally:
-        lib.arx_set_option(b"groupby_partition_min_rows", 1 << 17)
-        lib.arx_set_option(b"groupby_partition_bits", -1)
 
 
 @pytest.mark.parametrize("fused", [1, 0])
@@ -414,16 +394,15 @@ def test_sort_msd_hybrid_path(emu_ctx, global_bits, fused):
     bits are capped] + the windowed final ranking): full-range keys, heavy ties (bucket overflow ->
     LSD fallback), nulls (prep + MSD), descending, signed."""
     lib = emu_ctx._lib.get_lib()
-    assert lib.arx_set_option(b"sort_msd", 1) == 0
-    assert lib.arx_set_option(b"sort_msd_fused", fused) == 0   # 1: LDS-resident bucket finish; 0: local + windowed final
+    opts = {b"sort_msd": 1, b"sort_msd_fused": fused}   # fused 1: LDS-resident bucket finish; 0: local + windowed final
     if global_bits < 0:   # the segmented form: an extra level on the top bits, then one pipeline per segment
         global_bits = -global_bits
-        assert lib.arx_set_option(b"sort_msd_segment_rows", 4096) == 0
+        opts[b"sort_msd_segment_rows"] = 4096
         # beyond the segment size the wide two-level form (run_msd_sort_wide) runs first; fused = 0 switches it off so
         # that the segmented form itself stays covered
-        assert lib.arx_set_option(b"sort_msd_wide", fused) == 0
-    assert lib.arx_set_option(b"sort_msd_global_bits", global_bits) == 0
-    try:
+        opts[b"sort_msd_wide"] = fused
+    opts[b"sort_msd_global_bits"] = global_bits
+    with U.options(lib, opts):
         n = 14000   # (the emulator runs every workgroup as fibers on one core)
         rng = rng_for("msd", global_bits, fused)
         for dtype, order, placement, null_p in ((np.uint64, "ascending", "at_end", 0.0),
@@ -435,12 +414,6 @@ def test_sort_msd_hybrid_path(emu_ctx, global_bits, fused):
         P.check_sort_indices(emu_ctx, ties, "ascending", "at_end", use_pyarrow=False)
         small = U.random_array(rng, np.uint64, 300)
         P.check_sort_indices(emu_ctx, small, "ascending", "at_end", use_pyarrow=False)
-    finally:
-        lib.arx_set_option(b"sort_msd", -1)
-        lib.arx_set_option(b"sort_msd_global_bits", 14)
-        lib.arx_set_option(b"sort_msd_segment_rows", 1 << 27)
-        lib.arx_set_option(b"sort_msd_wide", 1)
-        lib.arx_set_option(b"sort_msd_fused", 1)
 
 
 @pytest.mark.parametrize("b2max", [12, 0])
@@ -462,13 +435,11 @@ def test_sort_wide_register_staged_tiles(emu_ctx, rpt):
     tiles, level-2 tiles that end inside a round of the LDS buffer, rooms that overflow (sorted / blocky inputs)."""
     lib = emu_ctx._lib.get_lib()
     # the 256-thread bucket finish takes over whenever every bucket fits it (always, at these sizes): one case without
-    assert lib.arx_set_option(b"sort_msd_tiny_bucket", {16: 0, 8: 1}.get(rpt[0], 2)) == 0
-    assert lib.arx_set_option(b"sort_msd_bucket_cpt", 8 if rpt[1] == 16 else 4) == 0   # sub-bucket counters per thread of the finish
-    try:
+    with U.options(lib, {
+            b"sort_msd_tiny_bucket": {16: 0, 8: 1}.get(rpt[0], 2),
+            b"sort_msd_bucket_cpt": 8 if rpt[1] == 16 else 4,   # sub-bucket counters per thread of the finish
+    }):
         P.check_sort_wide_sampled(emu_ctx, lib, rng_for("wide-rpt", *rpt), 70_000, 2, 1, 12, rpt=rpt, typed_keys=True)
-    finally:
-        lib.arx_set_option(b"sort_msd_tiny_bucket", 2)
-        lib.arx_set_option(b"sort_msd_bucket_cpt", 4)
 
 
 @pytest.mark.parametrize("bits,b2max", [(13, 12)])
@@ -502,8 +473,7 @@ def test_sort_32bit_and_float_keys(emu_ctx, dtype, msd):
     """array_sort_indices on the other fixed-width key types: 32-bit integers (4 LSD passes), floats
     with NaNs as null-likes next to the nulls whatever the order, -0.0 tying with 0.0, infinities."""
     lib = emu_ctx._lib.get_lib()
-    assert lib.arx_set_option(b"sort_msd", 1 if msd else 0) == 0
-    try:
+    with U.options(lib, {b"sort_msd": 1 if msd else 0}):
         rng = rng_for("sort32f", str(dtype), msd)
         n = 4000   # (emulator: fibers on one core)
         for order, placement, null_p in (("ascending", "at_end", 0.05), ("descending", "at_start", 0.05)):
@@ -519,8 +489,6 @@ def test_sort_32bit_and_float_keys(emu_ctx, dtype, msd):
             else:
                 v[::3] = v[::3] % 17               # ties
             P.check_sort_indices(emu_ctx, a, order, placement)
-    finally:
-        lib.arx_set_option(b"sort_msd", -1)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.uint64, np.int32])
@@ -528,8 +496,7 @@ def test_sort_msd_sampled_splitters(emu_ctx, dtype):
     """The sampled-splitter form of the MSD sort forced on: skewed keys (normal floats, clustered
     integers), duplicates-heavy columns (a bucket overflows -> LSD fallback), nulls, descending."""
     lib = emu_ctx._lib.get_lib()
-    assert lib.arx_set_option(b"sort_msd_sampled", 2) == 0
-    try:
+    with U.options(lib, {b"sort_msd_sampled": 2}):
         rng = rng_for("sampled", str(dtype))
         n = 9000
         for order, placement, null_p in (("ascending", "at_end", 0.0), ("descending", "at_start", 0.04)):
@@ -547,8 +514,6 @@ def test_sort_msd_sampled_splitters(emu_ctx, dtype):
         if np.dtype(dtype).kind == "f":
             dup.values[:] = np.round(dup.values)
         P.check_sort_indices(emu_ctx, dup, "ascending", "at_end", use_pyarrow=False)
-    finally:
-        lib.arx_set_option(b"sort_msd_sampled", 1)
 
 
 # ------------------------------------------------------------------ binary / utf8 take + filter
@@ -620,18 +585,12 @@ def test_sort_msd_bucket_variants_and_segment_fanout(emu_ctx, small_bucket, fina
     opts = {b"sort_msd": 1, b"sort_msd_small_bucket": small_bucket, b"sort_msd_final_rows_log2": final_rows_log2,
             b"sort_msd_seg_min_bits": seg_min_bits, b"sort_msd_segment_rows": 2048 if seg_min_bits > 1 else 1 << 27,
             b"sort_msd_bucket_v2": v2, b"sort_msd_wide": v2}
-    for k, v in opts.items():
-        assert lib.arx_set_option(k, v) == 0
-    try:
+    with U.options(lib, opts):
         rng = rng_for("msdknobs", small_bucket, final_rows_log2, seg_min_bits, v2)
         n = 6000   # (the emulator runs a 1024-thread workgroup as 1024 fibers)
         a = U.random_array(rng, np.uint64, n, null_p=0.02, offset=1)
         a.values[a.offset:a.offset + n - 1:7] = a.values[a.offset + 1:a.offset + n:7]  # ties
         P.check_sort_indices(emu_ctx, a, "descending", "at_start", use_pyarrow=False)
-    finally:
-        for k, v in {b"sort_msd": -1, b"sort_msd_small_bucket": 1, b"sort_msd_final_rows_log2": 1,
-                     b"sort_msd_seg_min_bits": 1, b"sort_msd_segment_rows": 1 << 27, b"sort_msd_bucket_v2": 1, b"sort_msd_wide": 1}.items():
-            lib.arx_set_option(k, v)
 
 
 # ------------------------------------------------------------------ hash_min / hash_max on the fused table
@@ -1068,10 +1027,8 @@ def test_groupby_wide_one_level_form(emu_ctx, bits):
     lib = emu_ctx._lib.get_lib()
     opts = {b"groupby_partition_min_rows": 0, b"groupby_wide": 2, b"groupby_partition_bits": bits,
             b"groupby_wide_agg_chunk_rows": 1 << (14 + bits % 3)}
-    for k_, v_ in opts.items():
-        assert lib.arx_set_option(k_, v_) == 0
     wide0 = lib.arx_get_counter(b"groupby_slices_wide")
-    try:
+    with U.options(lib, opts):
         rng = rng_for("gbwide", bits)
         n = 30000
         k = U.random_array(rng, np.int32, n, null_p=0.02, offset=3, lo=-2**31, hi=2**31 - 1)
@@ -1082,10 +1039,6 @@ def test_groupby_wide_one_level_form(emu_ctx, bits):
         v2 = U.random_array(rng, np.int64, n + 4097)
         P.check_groupby_sum(emu_ctx, k2, v2, use_pyarrow=False)
         assert lib.arx_get_counter(b"groupby_slices_wide") >= wide0 + 3, "the wide plan did not run"
-    finally:
-        for k_, v_ in {b"groupby_partition_min_rows": 1 << 17, b"groupby_wide": 1, b"groupby_partition_bits": -1,
-                       b"groupby_wide_agg_chunk_rows": 1 << 21}.items():
-            lib.arx_set_option(k_, v_)
 
 
 @pytest.mark.parametrize("wide,bits,parts", [(0, 0, 2), (0, 1, 3), (0, 5, 8), (0, 9, 4), (2, 4, 8), (2, 8, 5), (2, 6, 64)])
@@ -1097,9 +1050,7 @@ def test_groupby_consume_partials(emu_ctx, wide, bits, parts):
     lib = emu_ctx._lib.get_lib()
     opts = {b"groupby_partition_min_rows": 0, b"groupby_wide": wide or 1, b"groupby_partition_bits": bits,
             b"groupby_agg_chunk_rows": 1 << 12, b"groupby_wide_agg_chunk_rows": 1 << 14, b"groupby_wide_room_min_mean": 16}
-    for k_, v_ in opts.items():
-        assert lib.arx_set_option(k_, v_) == 0
-    try:
+    with U.options(lib, opts):
         rng = rng_for("gbemit", wide, bits, parts)
         n = 40000
         k = U.random_array(rng, np.int32, n, lo=-2**31, hi=2**31 - 1)
@@ -1114,6 +1065,7 @@ def test_groupby_consume_partials(emu_ctx, wide, bits, parts):
         kn = U.random_array(rng, np.int32, n, null_p=0.01, lo=0, hi=100)
         from arrow_amd import parallel
         assert parallel.consume_partials_regions(kn.to_device(emu_ctx), v.to_device(emu_ctx), 1 << 12, parts) is None
+        # (a forced value the case needs, a threshold above the rows of this shard, not a restore: options() above puts the knob back)
         assert lib.arx_set_option(b"groupby_partition_min_rows", 1 << 17) == 0
         assert parallel.consume_partials(k.to_device(emu_ctx), v.to_device(emu_ctx), 1 << 12, parts) == (None, None)
         # more records than the regions hold (every row its own group and a capacity that promises few groups: the rows that
@@ -1128,14 +1080,6 @@ def test_groupby_consume_partials(emu_ctx, wide, bits, parts):
         k16 = U.random_array(rng, np.int16, n, lo=0, hi=100)      # other key types: through the table (its casts)
         assert lib.arx_set_option(b"groupby_partition_min_rows", 0) == 0
         assert parallel.consume_partials_regions(k16.to_device(emu_ctx), v.to_device(emu_ctx), 1 << 12, parts) is None
-    finally:
-        for k_, v_ in {b"groupby_partition_min_rows": 1 << 17, b"groupby_wide": 1, b"groupby_partition_bits": -1,
-                       b"groupby_agg_chunk_rows": 1 << 18, b"groupby_wide_agg_chunk_rows": 1 << 21,
-                       b"groupby_wide_room_min_mean": 1 << 14}.items():
-            lib.arx_set_option(k_, v_)
-
-
-GROUPBY_STRIPE_DEFAULT = 0   # arrow_amd/csrc/groupby.hip g_gbp_stripe
 
 
 @pytest.mark.parametrize("stripe", [0, 4, 68])
@@ -1148,11 +1092,9 @@ def test_groupby_wide_form_without_histogram(emu_ctx, hot, stripe):
     lib = emu_ctx._lib.get_lib()
     opts = {b"groupby_partition_min_rows": 0, b"groupby_wide": 2, b"groupby_partition_bits": 6, b"groupby_wide_room_min_mean": 16, b"groupby_stripe": stripe,
             b"groupby_wide_max_slice_rows": 98304}
-    for k_, v_ in opts.items():
-        assert lib.arx_set_option(k_, v_) == 0
     names = (b"groupby_slices_rooms", b"groupby_rooms_overflows")
     before = [lib.arx_get_counter(c) for c in names]
-    try:
+    with U.options(lib, opts):
         rng = rng_for("gbrooms", hot)
         n = 250000
         k = U.random_array(rng, np.int32, n, null_p=0.02, lo=-2**31, hi=2**31 - 1)
@@ -1160,11 +1102,6 @@ def test_groupby_wide_form_without_histogram(emu_ctx, hot, stripe):
             k.values[n // 3:] = 7            # two thirds of the rows in ONE group: its partition outgrows its room
         v = U.random_array(rng, np.int64, n, null_p=0.1)
         P.check_groupby_sum(emu_ctx, k, v, skip_nulls=False, min_count=2, batches=1, use_pyarrow=not hot)
-    finally:
-        for k_, v_ in {b"groupby_partition_min_rows": 1 << 17, b"groupby_wide": 1, b"groupby_partition_bits": -1,
-                       b"groupby_wide_room_min_mean": 1 << 14, b"groupby_wide_max_slice_rows": (1 << 32) - (1 << 26),
-                       b"groupby_stripe": GROUPBY_STRIPE_DEFAULT}.items():
-            lib.arx_set_option(k_, v_)
     rooms, overflows = (lib.arx_get_counter(c) - b for c, b in zip(names, before))
     assert rooms >= 1, "the plan without a histogram did not run"
     assert (overflows >= 1) == hot, (rooms, overflows)
@@ -1178,12 +1115,13 @@ def test_groupby_probe_slice_selects_the_plan(emu_ctx, distinct):
     the first groupby_probe_rows keys estimates the distinct keys; few of them, seen often -> the rows run the wide plan, keys
     that do not repeat -> the two-level plan.  Same groups either way."""
     lib = emu_ctx._lib.get_lib()
-    assert lib.arx_set_option(b"groupby_partition_min_rows", 0) == 0
-    assert lib.arx_set_option(b"groupby_probe_rows", 4096) == 0
-    assert lib.arx_set_option(b"groupby_wide_max_bits", 3) == 0    # (so that the capacity bound alone cannot pick the wide plan)
     names = (b"groupby_slices_probe", b"groupby_slices_wide", b"groupby_slices_two_level")
     before = [lib.arx_get_counter(c) for c in names]
-    try:
+    with U.options(lib, {
+            b"groupby_partition_min_rows": 0,
+            b"groupby_probe_rows": 4096,
+            b"groupby_wide_max_bits": 3,    # (so that the capacity bound alone cannot pick the wide plan)
+    }):
         rng = rng_for("gbprobe", distinct)
         n = 9 * (4096) + 1234
         hi = distinct if distinct else 2**31 - 1
@@ -1191,10 +1129,6 @@ def test_groupby_probe_slice_selects_the_plan(emu_ctx, distinct):
         v = U.random_array(rng, np.int64, n, null_p=0.05)
         P.check_groupby_sum(emu_ctx, k, v, capacity=1 << 21, batches=1, use_pyarrow=False)
         P.check_groupby_sum(emu_ctx, k, v, capacity=1 << 21, batches=2, use_pyarrow=False)   # second consume: table not empty
-    finally:
-        lib.arx_set_option(b"groupby_partition_min_rows", 1 << 17)
-        lib.arx_set_option(b"groupby_probe_rows", 1 << 25)
-        lib.arx_set_option(b"groupby_wide_max_bits", 11)
     probe, wide, two = (lib.arx_get_counter(c) - b for c, b in zip(names, before))
     assert probe == 3, "one sketch (round 3: one probe slice) per consume call"
     if distinct:

@@ -63,16 +63,13 @@ def test_filter_tuning_variants_agree(gpu_ctx):
     rng = rng_for("fvariants")
     v = U.random_array(rng, np.int64, 2_000_003, null_p=0.1, offset=2)
     m = U.random_mask(rng, 2_000_003, 0.1, null_p=0.05)
-    try:
+    with U.options(lib, {b"filter_batch": 1, b"filter_pipe": 0}):
         for batch in (1, 4):
             for pipe in (0, 1):
                 assert lib.arx_set_option(b"filter_batch", batch) == 0
                 assert lib.arx_set_option(b"filter_pipe", pipe) == 0
                 for sel in ("drop", "emit_null"):
                     P.check_filter(gpu_ctx, v, m, sel, use_pyarrow=False)
-    finally:
-        lib.arx_set_option(b"filter_batch", 4)
-        lib.arx_set_option(b"filter_pipe", 1)
 
 
 def test_filter_10m_rows_config1(gpu_ctx):
@@ -358,12 +355,9 @@ def test_hash_sum_kernel_partitioned_by_group_id(gpu_ctx, num_groups, n):
     of the dense group id, LDS aggregation, one flush per partition — no partition level (<= 2048 ids), one level,
     two levels; null values, hot groups, several consumes into the same state.  Same results as the per-row form."""
     lib = gpu_ctx._lib.get_lib()
-    assert lib.arx_set_option(b"groupby_partition_min_rows", 0) == 0
-    try:
+    with U.options(lib, {b"groupby_partition_min_rows": 0}):
         P.check_hash_sum_kernel(gpu_ctx, rng_for("hskp", num_groups), n=n, num_groups=num_groups, null_p=0.1,
                                 use_pyarrow=False)
-    finally:
-        lib.arx_set_option(b"groupby_partition_min_rows", 1 << 17)
 
 
 def test_hash_sum_kernel_no_nulls_has_no_bitmap(gpu_ctx):
@@ -375,8 +369,7 @@ def test_filter_forced_sweep_and_sparse_forms(gpu_ctx, mode):
     """filter_sparse = 0 forces the sweeping compaction, 1 the gather form, for EVERY selectivity,
     null density, offset, width and length class: both must be bit-exact (auto picks by S/N)."""
     lib = gpu_ctx._lib.get_lib()
-    assert lib.arx_set_option(b"filter_sparse", mode) == 0
-    try:
+    with U.options(lib, {b"filter_sparse": mode}):
         for n in (1, 63, 64, 65, 4095, 4096, 4097, 1000003):
             for sel in ("drop", "emit_null"):
                 rng = rng_for("fform", n, sel)
@@ -395,8 +388,6 @@ def test_filter_forced_sweep_and_sparse_forms(gpu_ctx, mode):
             v = U.random_array(rng, dtype, 12345, null_p=0.1, offset=3)
             m = U.random_mask(rng, 12345, 0.15, null_p=0.05, offset=1)
             P.check_filter(gpu_ctx, v, m, "emit_null", use_pyarrow=False)
-    finally:
-        lib.arx_set_option(b"filter_sparse", -1)
 
 
 @pytest.mark.parametrize("bits", [0, 1, 5, 9, 11])
@@ -405,9 +396,7 @@ def test_groupby_partitioned_path(gpu_ctx, bits):
     forced on, for one-level (bits <= 8) and two-level plans, with null keys / null values /
     wrap-around, several consume calls, and keys that overflow one partition's LDS table."""
     lib = gpu_ctx._lib.get_lib()
-    assert lib.arx_set_option(b"groupby_partition_min_rows", 0) == 0
-    assert lib.arx_set_option(b"groupby_partition_bits", bits) == 0
-    try:
+    with U.options(lib, {b"groupby_partition_min_rows": 0, b"groupby_partition_bits": bits}):
         rng = rng_for("gbp", bits)
         n = 3000003
         k = U.random_array(rng, np.int32, n, null_p=0.02, offset=3, lo=-2**31, hi=2**31 - 1)
@@ -419,9 +408,6 @@ def test_groupby_partitioned_path(gpu_ctx, bits):
         k2 = U.random_array(rng, np.int32, n, lo=0, hi=50000)
         v2 = U.random_array(rng, np.int64, n)
         P.check_groupby_sum(gpu_ctx, k2, v2, use_pyarrow=False)
-    finally:
-        lib.arx_set_option(b"groupby_partition_min_rows", 1 << 17)
-        lib.arx_set_option(b"groupby_partition_bits", -1)
 
 
 @pytest.mark.parametrize("order,placement", [("ascending", "at_end"), ("descending", "at_start")])
@@ -448,9 +434,7 @@ def test_groupby_partition_knobs(gpu_ctx, l1_global, agg_chunk, bits):
     lib = gpu_ctx._lib.get_lib()
     opts = {b"groupby_partition_min_rows": 0, b"groupby_partition_bits": bits, b"groupby_l1_global": l1_global,
             b"groupby_agg_chunk_rows": agg_chunk}
-    for k_, v_ in opts.items():
-        assert lib.arx_set_option(k_, v_) == 0
-    try:
+    with U.options(lib, opts):
         rng = rng_for("gbpknobs", l1_global, agg_chunk, bits)
         n = 3000000
         k = U.random_array(rng, np.int32, n, null_p=0.02, offset=3, lo=-2**31, hi=2**31 - 1)
@@ -460,10 +444,6 @@ def test_groupby_partition_knobs(gpu_ctx, l1_global, agg_chunk, bits):
         k2 = U.random_array(rng, np.int32, n, lo=0, hi=50000)
         v2 = U.random_array(rng, np.int64, n)
         P.check_groupby_sum(gpu_ctx, k2, v2, use_pyarrow=False)
-    finally:
-        for k_, v_ in {b"groupby_partition_min_rows": 1 << 17, b"groupby_partition_bits": -1, b"groupby_l1_global": 1,
-                       b"groupby_agg_chunk_rows": 1 << 18}.items():
-            lib.arx_set_option(k_, v_)
 
 
 @pytest.mark.parametrize("bits", [1, 4, 8, 11])
@@ -474,10 +454,8 @@ def test_groupby_wide_one_level_form(gpu_ctx, bits):
     lib = gpu_ctx._lib.get_lib()
     opts = {b"groupby_partition_min_rows": 0, b"groupby_wide": 2, b"groupby_partition_bits": bits,
             b"groupby_wide_agg_chunk_rows": 1 << (14 + bits % 3)}
-    for k_, v_ in opts.items():
-        assert lib.arx_set_option(k_, v_) == 0
     wide0 = lib.arx_get_counter(b"groupby_slices_wide")
-    try:
+    with U.options(lib, opts):
         rng = rng_for("gbwide", bits)
         n = 3000000
         k = U.random_array(rng, np.int32, n, null_p=0.02, offset=3, lo=-2**31, hi=2**31 - 1)
@@ -488,13 +466,6 @@ def test_groupby_wide_one_level_form(gpu_ctx, bits):
         v2 = U.random_array(rng, np.int64, n + 4097)
         P.check_groupby_sum(gpu_ctx, k2, v2, use_pyarrow=False)
         assert lib.arx_get_counter(b"groupby_slices_wide") >= wide0 + 3, "the wide plan did not run"
-    finally:
-        for k_, v_ in {b"groupby_partition_min_rows": 1 << 17, b"groupby_wide": 1, b"groupby_partition_bits": -1,
-                       b"groupby_wide_agg_chunk_rows": 1 << 21}.items():
-            lib.arx_set_option(k_, v_)
-
-
-GROUPBY_STRIPE_DEFAULT = 0   # arrow_amd/csrc/groupby.hip g_gbp_stripe
 
 
 @pytest.mark.parametrize("stripe", [0, 276])
@@ -507,11 +478,9 @@ def test_groupby_wide_form_without_histogram(gpu_ctx, hot, stripe):
     lib = gpu_ctx._lib.get_lib()
     opts = {b"groupby_partition_min_rows": 0, b"groupby_wide": 2, b"groupby_partition_bits": 11, b"groupby_wide_room_min_mean": 16, b"groupby_stripe": stripe,
             b"groupby_wide_max_slice_rows": 2457600}
-    for k_, v_ in opts.items():
-        assert lib.arx_set_option(k_, v_) == 0
     names = (b"groupby_slices_rooms", b"groupby_rooms_overflows")
     before = [lib.arx_get_counter(c) for c in names]
-    try:
+    with U.options(lib, opts):
         rng = rng_for("gbrooms", hot)
         n = 3200000
         k = U.random_array(rng, np.int32, n, null_p=0.02, lo=-2**31, hi=2**31 - 1)
@@ -519,11 +488,6 @@ def test_groupby_wide_form_without_histogram(gpu_ctx, hot, stripe):
             k.values[n // 3:] = 7            # two thirds of the rows in ONE group: its partition outgrows its room
         v = U.random_array(rng, np.int64, n, null_p=0.1)
         P.check_groupby_sum(gpu_ctx, k, v, skip_nulls=False, min_count=2, batches=1, use_pyarrow=not hot)
-    finally:
-        for k_, v_ in {b"groupby_partition_min_rows": 1 << 17, b"groupby_wide": 1, b"groupby_partition_bits": -1,
-                       b"groupby_wide_room_min_mean": 1 << 14, b"groupby_wide_max_slice_rows": (1 << 32) - (1 << 26),
-                       b"groupby_stripe": GROUPBY_STRIPE_DEFAULT}.items():
-            lib.arx_set_option(k_, v_)
     rooms, overflows = (lib.arx_get_counter(c) - b for c, b in zip(names, before))
     assert rooms >= 1, "the plan without a histogram did not run"
     assert (overflows >= 1) == hot, (rooms, overflows)
@@ -537,12 +501,13 @@ def test_groupby_probe_slice_selects_the_plan(gpu_ctx, distinct):
     the first groupby_probe_rows keys estimates the distinct keys; few of them, seen often -> the rows run the wide plan, keys
     that do not repeat -> the two-level plan.  Same groups either way."""
     lib = gpu_ctx._lib.get_lib()
-    assert lib.arx_set_option(b"groupby_partition_min_rows", 0) == 0
-    assert lib.arx_set_option(b"groupby_probe_rows", 262144) == 0
-    assert lib.arx_set_option(b"groupby_wide_max_bits", 6) == 0    # (so that the capacity bound alone cannot pick the wide plan)
     names = (b"groupby_slices_probe", b"groupby_slices_wide", b"groupby_slices_two_level")
     before = [lib.arx_get_counter(c) for c in names]
-    try:
+    with U.options(lib, {
+            b"groupby_partition_min_rows": 0,
+            b"groupby_probe_rows": 262144,
+            b"groupby_wide_max_bits": 6,    # (so that the capacity bound alone cannot pick the wide plan)
+    }):
         rng = rng_for("gbprobe", distinct)
         n = 9 * 262144 + 1234
         hi = distinct if distinct else 2**31 - 1
@@ -551,10 +516,6 @@ def test_groupby_probe_slice_selects_the_plan(gpu_ctx, distinct):
         cap = 1 << 21 if distinct else 1 << 23     # (2.4M distinct keys need the larger table)
         P.check_groupby_sum(gpu_ctx, k, v, capacity=cap, batches=1, use_pyarrow=False)
         P.check_groupby_sum(gpu_ctx, k, v, capacity=cap, batches=2, use_pyarrow=False)   # second consume: table not empty
-    finally:
-        lib.arx_set_option(b"groupby_partition_min_rows", 1 << 17)
-        lib.arx_set_option(b"groupby_probe_rows", 1 << 25)
-        lib.arx_set_option(b"groupby_wide_max_bits", 11)
     probe, wide, two = (lib.arx_get_counter(c) - b for c, b in zip(names, before))
     assert probe == 3, "one sketch (round 3: one probe slice) per consume call"
     if distinct:
@@ -570,19 +531,15 @@ def test_groupby_consume_partials(gpu_ctx, wide, bits, parts, keys_hi):
     than its LDS tables hold; owners, sums, counts, the receivers' merges and the too-small-region status are checked by
     check_groupby_consume_partials."""
     lib = gpu_ctx._lib.get_lib()
+    # (room_min_mean 1 << 14 where the wide form is not forced: a value this case runs with, not a restore)
     opts = {b"groupby_wide": wide, b"groupby_partition_bits": bits, b"groupby_wide_room_min_mean": 16 if wide == 2 else 1 << 14}
-    for k_, v_ in opts.items():
-        assert lib.arx_set_option(k_, v_) == 0
-    try:
+    with U.options(lib, opts):
         rng = rng_for("gbemit", wide, bits, parts)
         n = 3_000_000
         k = U.random_array(rng, np.int32, n, lo=0, hi=keys_hi, offset=3)
         v = U.random_array(rng, np.int64, n, offset=1)
         records = P.check_groupby_consume_partials(gpu_ctx, k, v, parts, capacity=1 << 23)
         assert records >= keys_hi * (1 - np.exp(-n / keys_hi)) * 0.99      # (at least the distinct keys)
-    finally:
-        for k_, v_ in {b"groupby_wide": 1, b"groupby_partition_bits": -1, b"groupby_wide_room_min_mean": 1 << 14}.items():
-            lib.arx_set_option(k_, v_)
 
 
 def test_groupby_virtual_ranks_on_one_gpu(gpu_ctx):
@@ -639,16 +596,15 @@ def test_sort_msd_hybrid_path(gpu_ctx, global_bits, fused):
     bits are capped] + the windowed final ranking): full-range keys, heavy ties (bucket overflow ->
     LSD fallback), nulls (prep + MSD), descending, signed."""
     lib = gpu_ctx._lib.get_lib()
-    assert lib.arx_set_option(b"sort_msd", 1) == 0
-    assert lib.arx_set_option(b"sort_msd_fused", fused) == 0   # 1: LDS-resident bucket finish; 0: local + windowed final
+    opts = {b"sort_msd": 1, b"sort_msd_fused": fused}   # fused 1: LDS-resident bucket finish; 0: local + windowed final
     if global_bits < 0:   # the segmented form: an extra level on the top bits, then one pipeline per segment
         global_bits = -global_bits
-        assert lib.arx_set_option(b"sort_msd_segment_rows", 4096) == 0
+        opts[b"sort_msd_segment_rows"] = 4096
         # beyond the segment size the wide two-level form (run_msd_sort_wide) runs first; fused = 0 switches it off so
         # that the segmented form itself stays covered
-        assert lib.arx_set_option(b"sort_msd_wide", fused) == 0
-    assert lib.arx_set_option(b"sort_msd_global_bits", global_bits) == 0
-    try:
+        opts[b"sort_msd_wide"] = fused
+    opts[b"sort_msd_global_bits"] = global_bits
+    with U.options(lib, opts):
         n = 6000011
         rng = rng_for("msd", global_bits, fused)
         for dtype, order, placement, null_p in ((np.uint64, "ascending", "at_end", 0.0),
@@ -661,12 +617,6 @@ def test_sort_msd_hybrid_path(gpu_ctx, global_bits, fused):
         P.check_sort_indices(gpu_ctx, ties, "ascending", "at_end", use_pyarrow=False)
         small = U.random_array(rng, np.uint64, 300)
         P.check_sort_indices(gpu_ctx, small, "ascending", "at_end", use_pyarrow=False)
-    finally:
-        lib.arx_set_option(b"sort_msd", -1)
-        lib.arx_set_option(b"sort_msd_global_bits", 14)
-        lib.arx_set_option(b"sort_msd_segment_rows", 1 << 27)
-        lib.arx_set_option(b"sort_msd_wide", 1)
-        lib.arx_set_option(b"sort_msd_fused", 1)
 
 
 @pytest.mark.parametrize("shift,gap2,b2max", [(4, 1, 12), (2, 1, 12), (4, 0, 12), (0, 1, 12), (0, 0, 12), (4, 1, 0),
@@ -683,14 +633,12 @@ def test_sort_wide_sampled_level1(gpu_ctx, shift, gap2, b2max):
 def test_sort_wide_register_staged_tiles(gpu_ctx, rpt):
     """Level-1 / level-2 scatter tiles of 8 (LDS-resident), 16 and 24 (register-staged) rows per thread."""
     lib = gpu_ctx._lib.get_lib()
-    assert lib.arx_set_option(b"sort_msd_tiny_bucket", {16: 0, 8: 1}.get(rpt[0], 2)) == 0   # (256- / 512-thread bucket finish)
-    assert lib.arx_set_option(b"sort_msd_bucket_cpt", 8 if rpt[1] == 16 else 4) == 0   # sub-bucket counters per thread of the finish
-    try:
+    with U.options(lib, {
+            b"sort_msd_tiny_bucket": {16: 0, 8: 1}.get(rpt[0], 2),   # (256- / 512-thread bucket finish)
+            b"sort_msd_bucket_cpt": 8 if rpt[1] == 16 else 4,   # sub-bucket counters per thread of the finish
+    }):
         P.check_sort_wide_sampled(gpu_ctx, lib, rng_for("wide-rpt", *rpt), 3_000_011, 4, 1, 12, rpt=rpt, typed_keys=True)
         P.check_sort_wide_many_bins(gpu_ctx, lib, rng_for("wide-rpt-bins", *rpt), 2_000_003, 16, 12, combos=((0, 0), (2, 1)), rpt=rpt)
-    finally:
-        lib.arx_set_option(b"sort_msd_tiny_bucket", 2)
-        lib.arx_set_option(b"sort_msd_bucket_cpt", 4)
 
 
 @pytest.mark.parametrize("n,bits,gap2,shift,rpt,b2max,wc,prefetch,l2w", [(3_000_011, 0, 1, 4, (24, 16), 11, 256, 1, 1), (3_000_003, 14, 0, 2, (8, 8), 11, 0, 1, 2),
@@ -721,8 +669,7 @@ def test_sort_32bit_and_float_keys(gpu_ctx, dtype, msd):
     """array_sort_indices on the other fixed-width key types: 32-bit integers (4 LSD passes), floats
     with NaNs as null-likes next to the nulls whatever the order, -0.0 tying with 0.0, infinities."""
     lib = gpu_ctx._lib.get_lib()
-    assert lib.arx_set_option(b"sort_msd", 1 if msd else 0) == 0
-    try:
+    with U.options(lib, {b"sort_msd": 1 if msd else 0}):
         rng = rng_for("sort32f", str(dtype), msd)
         n = 5000003
         for order, placement, null_p in (("ascending", "at_end", 0.05), ("descending", "at_start", 0.05),
@@ -739,8 +686,6 @@ def test_sort_32bit_and_float_keys(gpu_ctx, dtype, msd):
             else:
                 v[::3] = v[::3] % 17               # ties
             P.check_sort_indices(gpu_ctx, a, order, placement)
-    finally:
-        lib.arx_set_option(b"sort_msd", -1)
 
 
 def test_sort_virtual_ranks_on_one_gpu(gpu_ctx):
@@ -816,9 +761,7 @@ def test_sort_msd_bucket_variants_on_gpu(gpu_ctx, small_bucket, final_rows_log2,
     lib = gpu_ctx._lib.get_lib()
     opts = {b"sort_msd": 1, b"sort_msd_small_bucket": small_bucket, b"sort_msd_final_rows_log2": final_rows_log2,
             b"sort_msd_segment_rows": seg_rows, b"sort_msd_bucket_v2": v2, b"sort_msd_wide": v2}
-    for k, v in opts.items():
-        assert lib.arx_set_option(k, v) == 0
-    try:
+    with U.options(lib, opts):
         rng = rng_for("msdknobs-gpu", small_bucket, final_rows_log2, seg_rows, v2)
         n = 5_000_011
         a = U.random_array(rng, np.uint64, n, null_p=0.02, offset=1)
@@ -826,10 +769,6 @@ def test_sort_msd_bucket_variants_on_gpu(gpu_ctx, small_bucket, final_rows_log2,
         P.check_sort_indices(gpu_ctx, a, "descending", "at_start", use_pyarrow=False)
         b = U.random_array(rng, np.int64, n, offset=0)
         P.check_sort_indices(gpu_ctx, b, "ascending", "at_end", use_pyarrow=False)
-    finally:
-        for k, v in {b"sort_msd": -1, b"sort_msd_small_bucket": 1, b"sort_msd_final_rows_log2": 1,
-                     b"sort_msd_segment_rows": 1 << 27, b"sort_msd_bucket_v2": 1, b"sort_msd_wide": 1}.items():
-            lib.arx_set_option(k, v)
 
 
 @pytest.mark.parametrize("placement,window", [("at_end", None), ("at_start", None),
@@ -937,8 +876,7 @@ def test_sort_msd_sampled_splitters(gpu_ctx, dtype):
     """The sampled-splitter form of the MSD sort forced on: skewed keys (normal floats, clustered
     integers), duplicates-heavy columns (a bucket overflows -> LSD fallback), nulls, descending."""
     lib = gpu_ctx._lib.get_lib()
-    assert lib.arx_set_option(b"sort_msd_sampled", 2) == 0
-    try:
+    with U.options(lib, {b"sort_msd_sampled": 2}):
         rng = rng_for("sampled", str(dtype))
         n = 4000003
         for order, placement, null_p in (("ascending", "at_end", 0.0), ("descending", "at_start", 0.04)):
@@ -956,8 +894,6 @@ def test_sort_msd_sampled_splitters(gpu_ctx, dtype):
         if np.dtype(dtype).kind == "f":
             dup.values[:] = np.round(dup.values)
         P.check_sort_indices(gpu_ctx, dup, "ascending", "at_end", use_pyarrow=False)
-    finally:
-        lib.arx_set_option(b"sort_msd_sampled", 1)
 
 
 # ------------------------------------------------------------------ binary / utf8 take + filter

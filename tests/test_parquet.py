@@ -131,11 +131,8 @@ def check_snappy_kernel(amd, rng, scale=1):
 
 def _with_snappy_form(amd, lds, fn):
     lib = amd._lib.get_lib()
-    assert lib.arx_set_option(b"snappy_lds", lds) == 0
-    try:
+    with U.options(lib, {b"snappy_lds": lds}):
         fn()
-    finally:
-        lib.arx_set_option(b"snappy_lds", -1)
 
 
 @pytest.mark.emu

@@ -2,6 +2,8 @@
 arrays / pyarrow / oracle inputs, seeded generators (in the spirit of arrow/testing/random.h)."""
 from __future__ import annotations
 
+import contextlib
+import ctypes
 import dataclasses
 
 import numpy as np
@@ -191,3 +193,26 @@ def random_binary(rng, length, null_p=0.0, offset=0, tail=0, max_len=24, utf8=Fa
         data = rng.integers(0, 255, size=total, endpoint=True).astype(np.uint8)
     valid = (rng.random(n) >= null_p) if null_p > 0 else None
     return HostBinaryArray(offsets, data, valid, offset, length, utf8)
+
+
+def get_option(lib, name: bytes) -> int:
+    """The value the knob `name` holds now (arx_get_option)."""
+    value = ctypes.c_int64()
+    assert lib.arx_get_option(name, ctypes.byref(value)) == 0, (name, lib.arx_last_error())
+    return value.value
+
+
+@contextlib.contextmanager
+def options(lib, values):
+    """Sets the tuning knobs `values` ({name: value}, arx_set_option) for the body of the `with` and then puts back what
+    each held before, also when the body raises.  Only the knobs named here are put back: one that the body sets on its
+    way is named here too (with its first value), or is set through an options() of its own."""
+    saved = {}
+    try:
+        for name, value in values.items():
+            saved[name] = get_option(lib, name)
+            assert lib.arx_set_option(name, value) == 0, (name, value)
+        yield
+    finally:
+        for name, value in saved.items():
+            lib.arx_set_option(name, value)
