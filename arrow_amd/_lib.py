@@ -240,6 +240,9 @@ SIGNATURES = {
     "arx_hash_join_expand": (_int, [_p, _p, _p, _i64, _p, _p, _int, _i64, _p, _p, _p, _p]),
     "arx_hash_join_build_mask": (_int, [_p, _p, _i64, _p, _int, _p, _p]),
     "arx_hash_join_append_build_rows": (_int, [_p, _i64, _i64, _p, _p, _p, _p, _p]),
+    "arx_hash_join_filter_count": (_int, [_span, _p, _p, _i64, _int, _p, _p, _i64, _p, _p, _p, _p, _sz, C.POINTER(_i64), _p]),
+    "arx_hash_join_filter_compact": (_int, [_p, _p, _i64, _p, _p, _i64, _p, _p, _int, _i64, _p, _p, _p, _p]),
+    "arx_hash_join_flags_to_mask": (_int, [_p, _i64, _int, _p, _p]),
     "arx_binary_key_verify": (_int, [_bspan, _p, _p, C.POINTER(_i64), _p, _p]),
     "arx_group_first_rows": (_int, [_p, _i64, _i64, _p, _p]),
     "arx_group_edge_rows": (_int, [_p, _p, _i64, _i64, _i64, _int, _p, _p, _p]),

@@ -2428,7 +2428,7 @@ def _ptr_or_none(t):
     return None if t is None else t.data_ptr()
 
 
-def hash_join_indices(left_keys, right_keys, join_type="inner", null_equals_null=False, max_output_rows=None):
+def hash_join_indices(left_keys, right_keys, join_type="inner", null_equals_null=False, max_output_rows=None, filter=None):  # noqa: A002
     """The row pairs of the equi-join of the left (probe) and right (build) inputs on their key columns, as
     (left_indices, right_indices): int64 device Arrays, null where a side is unmatched (outer joins).  Semi / anti joins
     return only their side's indices and None for the other.  Keys: lists of equal-typed columns (fixed-width types
@@ -2436,7 +2436,13 @@ def hash_join_indices(left_keys, right_keys, join_type="inner", null_equals_null
     otherwise a null key matches nothing.  Row order: inner / outer rows follow the left rows, the right rows of one left
     row ascend, the right-only rows of right / full outer joins come last in right-row order; semi / anti rows are in
     input order.  A join of more than max_output_rows rows (default: what free device memory holds) raises
-    ArrowCapacityError before the output is allocated."""
+    ArrowCapacityError before the output is allocated.
+    filter: the residual predicate of HashJoinNodeOptions::filter as a callable (left_rows, right_rows) -> boolean Array
+    over the T candidate pairs (the key-equal pairs in the order above, as two int64 Arrays).  A pair is a match only where
+    the result is true (null: no match); which probe and build rows count as matched for outer, semi and anti joins
+    follows from the passing pairs, per build row.  The candidate pairs are allocated first and stay live while the
+    output is written: the limit is applied to their number and to the output's number of rows, each on its own, not to
+    the sum, so peak memory is up to twice what the limit alone suggests."""
     jt = _join_type_code(join_type)
     left_keys, right_keys = list(left_keys), list(right_keys)
     if not left_keys or len(left_keys) != len(right_keys):
@@ -2461,21 +2467,19 @@ def hash_join_indices(left_keys, right_keys, join_type="inner", null_equals_null
     probe_ids = grouper.lookup(lcols)
     build_valid = _key_validity([k for k, s in zip(right_keys, eq_is) if not s], nb, dev)
     probe_valid = _key_validity([probe_ids] + [k for k, s in zip(left_keys, eq_is) if not s], nl, dev)
-    bids, pids = build_ids.values_ptr(), probe_ids.values_ptr()
+    bids = build_ids.values_ptr()
 
-    offsets = alloc((nl + 1) * 8, dev)
-    ws = _workspace(dev, lib.arx_hash_join_workspace_bytes(max(num_groups, nl)), "hash_join")
     group_offsets = alloc((num_groups + 1) * 8, dev)
+    ws = _workspace(dev, lib.arx_hash_join_workspace_bytes(max(num_groups, nl)), "hash_join")
     check(lib.arx_hash_join_group_offsets(bids, _ptr_or_none(build_valid), nb, num_groups, group_offsets.data_ptr(),
                                           ws.data_ptr(), ws.numel(), stream))
+    j = _PreparedJoin(dev, nl, nb, probe_ids, probe_valid, build_ids, build_valid, group_offsets, num_groups,
+                      _max_output_rows(dev) if max_output_rows is None else int(max_output_rows))
+    if filter is not None:
+        return _hash_join_filtered(j, jt, filter)
     right_side = jt in (1, 3, 6, 7)
     matched = alloc(max(1, num_groups), dev, zero=True) if right_side else None
-    total = C.c_int64(0)
-    limit = _max_output_rows(dev) if max_output_rows is None else int(max_output_rows)
-    check(lib.arx_hash_join_probe_count(pids, _ptr_or_none(probe_valid), nl, group_offsets.data_ptr(), num_groups, jt,
-                                        _ptr_or_none(matched), limit, offsets.data_ptr(), ws.data_ptr(),
-                                        ws.numel(), C.byref(total), stream))
-    total = total.value
+    total = j.probe_count(jt, matched)
 
     def build_rows(want_matched: int) -> Array:
         mask = alloc(bitmap_nbytes(nb), dev)
@@ -2487,46 +2491,150 @@ def hash_join_indices(left_keys, right_keys, join_type="inner", null_equals_null
         rows = build_rows(1 if jt == 1 else 0)
         return None, Array(int64, rows.length, rows.buffers, 0, rows.offset)
     pairs = jt in (4, 5, 6, 7)
-    sorted_rows = None
-    if pairs and total:
-        sorted_rows = sort_indices(Array(uint32, nb, [build_valid, build_ids.data],
-                                         kUnknownNullCount if build_valid is not None else 0, 0))
     tail = build_rows(0) if jt in (6, 7) else None
-    n_out = total + (tail.length if tail is not None else 0)
-    if n_out > limit:     # the right-only tail of a right / full outer join counts too
-        raise _lib.ArrowCapacityError(f"hash join: the output would have {n_out} rows, more than the {limit} that can "
-                                      "be allocated")
+    n_out = j.checked_output_rows(total, tail)
     out_left = alloc(max(1, n_out) * 8, dev)
     out_right = alloc(max(1, n_out) * 8, dev) if pairs else None
     right_valid = alloc(bitmap_nbytes(n_out), dev) if jt in (5, 7) else None
-    check(lib.arx_hash_join_expand(offsets.data_ptr(), pids, _ptr_or_none(probe_valid), nl, group_offsets.data_ptr(),
-                                   _ptr_or_none(sorted_rows.data if sorted_rows is not None else None), jt, total,
-                                   out_left.data_ptr(), _ptr_or_none(out_right), _ptr_or_none(right_valid), stream))
-    left_valid = None
-    if tail is not None and tail.length:
-        left_valid = alloc(bitmap_nbytes(n_out), dev)
-        check(lib.arx_hash_join_append_build_rows(tail.values_ptr(), tail.length, total, out_left.data_ptr(),
-                                                  left_valid.data_ptr(), out_right.data_ptr(),
-                                                  _ptr_or_none(right_valid), stream))
+    j.expand(jt, total, out_left, out_right, right_valid)
+    return j.finish(tail, total, n_out, out_left, out_right, right_valid)
 
-    def idx(buf, valid, nulls):
-        a = Array(int64, n_out, [valid, buf], kUnknownNullCount if valid is not None else 0, 0)
-        if valid is not None and nulls is not None:
-            a._null_count = nulls
-        return a
 
-    left = idx(out_left, left_valid, tail.length if left_valid is not None else None)
-    if not pairs:
-        return left, None
-    return left, idx(out_right, right_valid, None)
+class _PreparedJoin:
+    """What both paths of hash_join_indices share once the key rows are ids and the group offsets exist: the probe count
+    into `offsets` (the read-back), the expand over the stably sorted build rows, the capacity check that counts the
+    right-only tail, and the tail append."""
+
+    def __init__(self, dev, nl, nb, probe_ids, probe_valid, build_ids, build_valid, group_offsets, num_groups, limit):
+        self.dev, self.nl, self.nb, self.limit = dev, nl, nb, limit
+        self.probe_ids, self.probe_valid, self.build_ids, self.build_valid = probe_ids, probe_valid, build_ids, build_valid
+        self.group_offsets, self.num_groups = group_offsets, num_groups
+        self.offsets = alloc((nl + 1) * 8, dev)
+        self.lib, self.stream = _lib_and_stream(dev)
+
+    def workspace(self, length: int):
+        return _workspace(self.dev, self.lib.arx_hash_join_workspace_bytes(length), "hash_join")
+
+    def probe_count(self, jt: int, matched) -> int:
+        ws = self.workspace(max(self.num_groups, self.nl))
+        total = C.c_int64(0)
+        check(self.lib.arx_hash_join_probe_count(self.probe_ids.values_ptr(), _ptr_or_none(self.probe_valid), self.nl,
+                                                 self.group_offsets.data_ptr(), self.num_groups, jt, _ptr_or_none(matched),
+                                                 self.limit, self.offsets.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                 C.byref(total), self.stream))
+        return total.value
+
+    def expand(self, jt: int, total: int, out_left, out_right, right_valid) -> None:
+        """Slots [0, total) of the probe count's offsets; the build rows by group come from the stable sort of the ids."""
+        sorted_rows = None
+        if out_right is not None and total:
+            sorted_rows = sort_indices(Array(uint32, self.nb, [self.build_valid, self.build_ids.data],
+                                             kUnknownNullCount if self.build_valid is not None else 0, 0))
+        check(self.lib.arx_hash_join_expand(self.offsets.data_ptr(), self.probe_ids.values_ptr(),
+                                            _ptr_or_none(self.probe_valid), self.nl, self.group_offsets.data_ptr(),
+                                            _ptr_or_none(sorted_rows.data if sorted_rows is not None else None), jt, total,
+                                            out_left.data_ptr(), _ptr_or_none(out_right), _ptr_or_none(right_valid),
+                                            self.stream))
+
+    def checked_output_rows(self, total: int, tail) -> int:
+        n_out = total + (tail.length if tail is not None else 0)
+        if n_out > self.limit:     # the right-only tail of a right / full outer join counts too
+            raise _lib.ArrowCapacityError(f"hash join: the output would have {n_out} rows, more than the {self.limit} "
+                                          "that can be allocated")
+        return n_out
+
+    def finish(self, tail, total: int, n_out: int, out_left, out_right, right_valid):
+        """Appends the right-only tail (null left indices) behind the `total` probe-side rows; the two index Arrays."""
+        left_valid = None
+        if tail is not None and tail.length:
+            left_valid = alloc(bitmap_nbytes(n_out), self.dev)
+            check(self.lib.arx_hash_join_append_build_rows(tail.values_ptr(), tail.length, total, out_left.data_ptr(),
+                                                           left_valid.data_ptr(), out_right.data_ptr(),
+                                                           _ptr_or_none(right_valid), self.stream))
+        left = _join_index_array(out_left, n_out, left_valid, tail.length if left_valid is not None else None)
+        return left, (_join_index_array(out_right, n_out, right_valid) if out_right is not None else None)
+
+
+def _join_index_array(buf, n: int, valid=None, nulls=None) -> Array:
+    a = Array(int64, n, [valid, buf], kUnknownNullCount if valid is not None else 0, 0)
+    if valid is not None and nulls is not None:
+        a._null_count = nulls
+    return a
+
+
+def _rows_of_flags(flags: torch.Tensor, n: int, want_set: int, dev) -> Array:
+    """The rows whose byte flag is set (want_set 1) or clear (0), ascending: arx_hash_join_flags_to_mask + compaction."""
+    lib, stream = _lib_and_stream(dev)
+    mask = alloc(bitmap_nbytes(n), dev)
+    check(lib.arx_hash_join_flags_to_mask(flags.data_ptr(), n, want_set, mask.data_ptr(), stream))
+    return indices_nonzero(Array(bool_, n, [None, mask], 0, 0))
+
+
+def _hash_join_filtered(j: _PreparedJoin, jt: int, predicate):
+    """hash_join_indices with a residual filter: the candidates as an inner join, the predicate over them, then the
+    filter kernels of csrc/hash_join.hip (pass words and their prefix, per-row counts, compaction, flag masks).  Semi and
+    anti outputs are at most one input long and are not checked against the limit; the candidates and the pair outputs
+    are, before they are allocated."""
+    lib, stream, dev, nl, nb = j.lib, j.stream, j.dev, j.nl, j.nb
+    T = j.probe_count(4, None)
+    cand_left, cand_right = alloc(max(1, T) * 8, dev), alloc(max(1, T) * 8, dev)
+    passed = None
+    if T:
+        j.expand(4, T, cand_left, cand_right, None)
+        passed = predicate(_join_index_array(cand_left, T), _join_index_array(cand_right, T))
+        if not isinstance(passed, Array) or passed.type != bool_ or passed.length != T:
+            raise ArrowInvalid(f"hash join: the filter must return a boolean Array of {T} rows (one per candidate pair)")
+    span = passed.span() if passed is not None else _lib.ArxSpan(None, None, 0, 0, 0)
+    words = (T + 63) // 64
+    build_hit = alloc(max(1, nb), dev, zero=True) if jt in (1, 3, 6, 7) else None
+    probe_hit = alloc(max(1, nl), dev) if jt in (0, 2) else None
+    pass_bits = alloc(max(1, words) * 8, dev)
+    prefix = alloc((words + 1) * 8, dev)
+    new_offsets = alloc((nl + 1) * 8, dev)
+    ws = j.workspace(max(nl, words))
+    total = C.c_int64(0)
+    check(lib.arx_hash_join_filter_count(C.byref(span), j.offsets.data_ptr(), cand_right.data_ptr(), nl, jt,
+                                         _ptr_or_none(build_hit), _ptr_or_none(probe_hit), j.limit, pass_bits.data_ptr(),
+                                         prefix.data_ptr(), new_offsets.data_ptr(), ws.data_ptr(), ws.numel(),
+                                         C.byref(total), stream))
+    total = total.value
+    if jt in (0, 2):          # left semi / left anti
+        rows = _rows_of_flags(probe_hit, nl, 1 if jt == 0 else 0, dev)
+        return Array(int64, rows.length, rows.buffers, 0, rows.offset), None
+    if jt in (1, 3):          # right semi / right anti
+        rows = _rows_of_flags(build_hit, nb, 1 if jt == 1 else 0, dev)
+        return None, Array(int64, rows.length, rows.buffers, 0, rows.offset)
+    tail = _rows_of_flags(build_hit, nb, 0, dev) if jt in (6, 7) else None
+    n_out = j.checked_output_rows(total, tail)
+    out_left, out_right = alloc(max(1, n_out) * 8, dev), alloc(max(1, n_out) * 8, dev)
+    right_valid = alloc(bitmap_nbytes(n_out), dev) if jt in (5, 7) else None
+    check(lib.arx_hash_join_filter_compact(pass_bits.data_ptr(), prefix.data_ptr(), T, j.offsets.data_ptr(),
+                                           new_offsets.data_ptr(), nl, cand_left.data_ptr(), cand_right.data_ptr(), jt,
+                                           total, out_left.data_ptr(), out_right.data_ptr(), _ptr_or_none(right_valid),
+                                           stream))
+    return j.finish(tail, total, n_out, out_left, out_right, right_valid)
+
+
+class _GatheredColumns(dict):
+    """name -> the column gathered at the candidate pairs' rows, taken when first asked for (only what the filter reads)."""
+
+    def __init__(self, columns, rows):
+        super().__init__()
+        self._columns, self._rows = columns, rows
+
+    def __missing__(self, name):
+        self[name] = take(self._columns[name], self._rows, boundscheck=False)
+        return self[name]
 
 
 def hash_join(left_columns, right_columns, left_keys, right_keys, join_type="inner", left_output=None,
-              right_output=None, left_suffix="", right_suffix="", null_equals_null=False):
+              right_output=None, left_suffix="", right_suffix="", null_equals_null=False, filter=None):  # noqa: A002
     """HashJoinNode over whole inputs held on the device: left_columns / right_columns map names to Arrays (fixed-width,
     boolean, utf8 / binary), left_keys / right_keys name the key columns.  Output columns: left_output then right_output
     (default: every column of the side(s) the join type emits), names that occur on both sides get the suffixes
-    (HashJoinSchema's rule).  Returns a list of (name, Array), gathered with `take` by hash_join_indices' row pairs."""
+    (HashJoinSchema's rule).  Returns a list of (name, Array), gathered with `take` by hash_join_indices' row pairs.
+    filter: the residual predicate, a callable (left, right) -> boolean Array over the candidate pairs; left / right map
+    every column name of their side to that column gathered at the pairs (gathered when first read)."""
     jt = _join_type_code(join_type)
     left_columns, right_columns = dict(left_columns), dict(right_columns)
     as_list = lambda k: [k] if isinstance(k, str) else list(k)   # noqa: E731
@@ -2535,8 +2643,12 @@ def hash_join(left_columns, right_columns, left_keys, right_keys, join_type="inn
     ro = [] if jt in (0, 2) else (list(right_columns) if right_output is None else as_list(right_output))
     payload = [left_columns[n] for n in lo] + [right_columns[n] for n in ro]
     dev = next(iter(left_columns.values())).device
+    pair_filter = None
+    if filter is not None:
+        pair_filter = lambda lrows, rrows: filter(_GatheredColumns(left_columns, lrows),   # noqa: E731
+                                                  _GatheredColumns(right_columns, rrows))
     li, ri = hash_join_indices([left_columns[k] for k in lk], [right_columns[k] for k in rk], jt, null_equals_null,
-                               max_output_rows=_max_output_rows(dev, _payload_row_bytes(payload)))
+                               max_output_rows=_max_output_rows(dev, _payload_row_bytes(payload)), filter=pair_filter)
     out = []
     for names, cols, ix, suffix, other in ((lo, left_columns, li, left_suffix, ro), (ro, right_columns, ri, right_suffix, lo)):
         for name in names:

@@ -20,6 +20,7 @@
 // numbers in DESIGN.md are quoted for and the one whole Acero plans run in (rows f2-f4: exec-node factories,
 // sibling kernels, Parquet decode).
 #include <arrow/acero/exec_plan.h>
+#include <arrow/acero/hash_join_node.h>
 #include <arrow/acero/options.h>
 #include <arrow/api.h>
 #include <arrow/c/abi.h>
@@ -100,6 +101,7 @@ namespace {
 #include "plugin/sharded.inc"
 #include "plugin/sharded_sort.inc"
 #include "plugin/order_by_node.inc"
+#include "plugin/hash_join_node.inc"
 #include "plugin/rank.inc"
 #include "plugin/acero_source.inc"
 #include "plugin/acero_coalesce.inc"

@@ -17,6 +17,17 @@
 //                 validity is two ballots per wave, interleaved into two 64-bit words.
 //   build side    the matched bytes become a mask over build rows (matched / unmatched, null keys counted unmatched);
 //                 the caller compacts it with arx_mask_to_indices and appends the rows with a null left index.
+//   residual      HashJoinNodeOptions::filter: a key-equal pair is a match only where the filter is true (null: no match).
+//   filter        The caller expands the CANDIDATES as an inner join, evaluates the filter over the T candidate slots and
+//                 hands in the boolean column.  filter count: pass word = value AND validity, one popcount per 64-slot
+//                 word, scanned (the three launches above) into P: passing slots before slot j in O(1).  A probe row's
+//                 passing pairs are P(offsets[i + 1]) - P(offsets[i]); its output rows follow by join type and are
+//                 scanned into the new offsets (the one more read-back).  Passing slots mark build ROWS (a byte each,
+//                 plain store of 1): the filter tells apart rows that share a key.  filter compact: one lane per
+//                 candidate slot, slot j of row r lands at new_offsets[r] + P(j) - P(offsets[r]); one lane per probe row
+//                 writes the (row, null) slot of a left / full outer row without a passing pair.  All work is per slot
+//                 or per row, O(1) each: a hot key costs per slot what any other input costs.  Byte flags become the
+//                 masks of semi / anti joins and of the right-only tail (flags_to_mask, either polarity).
 #include "arx_common.h"
 
 #include <cstring>
@@ -316,6 +327,111 @@ __global__ void append_build_rows_kernel(const uint64_t* rows, int64_t count, in
   }
 }
 
+// ----------------------------------------------------------------------------------------------- residual filter
+// P(x): the passing slots in [0, x), x in [0, T].  prefix has one entry per 64-slot word plus the total at [words].
+__device__ __forceinline__ int64_t passing_before(const uint64_t* pass_bits, const int64_t* prefix, int64_t x) {
+  const int64_t w = x >> 6;
+  const int r = int(x & 63);
+  int64_t p = prefix[w];
+  if (r != 0) p += __popcll(pass_bits[w] & low_mask64(r));   // (r == 0: word w may be one past the last)
+  return p;
+}
+
+__device__ __forceinline__ int64_t filtered_row_count(int jt, int64_t passing) {
+  switch (jt) {
+    case kLeftSemi: return passing > 0;
+    case kLeftAnti: return passing == 0;
+    case kInner:
+    case kRightOuter: return passing;
+    case kLeftOuter:
+    case kFullOuter: return passing > 0 ? passing : 1;
+    default: return 0;   // right semi / right anti: rows come from the build flags
+  }
+}
+
+// One lane per candidate slot, a wave per 64-slot word: pass word = values AND validity (lane 0 stores it and its
+// popcount), and the build row of every passing slot is flagged.
+__global__ void __launch_bounds__(kBlock) filter_pass_kernel(Bits values, Bits validity, int64_t total,
+                                                             const int64_t* cand_right, uint8_t* build_hit,
+                                                             uint64_t* pass_bits, int64_t* prefix) {
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  for (int64_t base = int64_t(blockIdx.x) * kBlock; base < total; base += stride) {
+    const int64_t j = base + threadIdx.x;
+    const int64_t w = j >> 6;                    // wave-uniform: kBlock and base are multiples of 64
+    if ((w << 6) >= total) continue;             // the whole wave is past the end
+    const uint64_t word = load_word(values, w) & load_word(validity, w);
+    if (build_hit != nullptr && j < total && ((word >> (j & 63)) & 1)) build_hit[cand_right[j]] = 1;
+    if (lane_id() == 0) {
+      pass_bits[w] = word;
+      prefix[w] = __popcll(word);
+    }
+  }
+}
+
+__global__ void filter_count_kernel(const int64_t* offsets, int64_t n, const uint64_t* pass_bits, const int64_t* prefix,
+                                    int jt, uint8_t* probe_hit, int64_t* counts) {
+  for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += int64_t(gridDim.x) * kBlock) {
+    const int64_t passing = passing_before(pass_bits, prefix, offsets[i + 1]) - passing_before(pass_bits, prefix, offsets[i]);
+    if (probe_hit != nullptr) probe_hit[i] = passing > 0;
+    counts[i] = filtered_row_count(jt, passing);
+  }
+}
+
+// One lane per candidate slot: a passing slot's pair goes to its final place.  cand_left[j] is the slot's probe row.
+__global__ void __launch_bounds__(kBlock) filter_compact_kernel(const uint64_t* pass_bits, const int64_t* prefix,
+                                                                int64_t total, const int64_t* offsets,
+                                                                const int64_t* new_offsets, const int64_t* cand_left,
+                                                                const int64_t* cand_right, int64_t* out_left,
+                                                                int64_t* out_right) {
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  for (int64_t j = int64_t(blockIdx.x) * kBlock + threadIdx.x; j < total; j += stride) {
+    if (!((pass_bits[j >> 6] >> (j & 63)) & 1)) continue;
+    const int64_t row = cand_left[j];
+    const int64_t dst = new_offsets[row] + passing_before(pass_bits, prefix, j) - passing_before(pass_bits, prefix, offsets[row]);
+    out_left[dst] = row;
+    out_right[dst] = cand_right[j];
+  }
+}
+
+// One lane per probe row (left / full outer): a row without a passing pair owns one slot, (row, null).  The null right
+// index is written as -1 and turned into (0, bit clear) by the validity kernel below.
+__global__ void filter_unmatched_kernel(const int64_t* offsets, const int64_t* new_offsets, int64_t n,
+                                        const uint64_t* pass_bits, const int64_t* prefix, int64_t* out_left,
+                                        int64_t* out_right) {
+  for (int64_t i = int64_t(blockIdx.x) * kBlock + threadIdx.x; i < n; i += int64_t(gridDim.x) * kBlock) {
+    if (passing_before(pass_bits, prefix, offsets[i + 1]) != passing_before(pass_bits, prefix, offsets[i])) continue;
+    const int64_t dst = new_offsets[i];
+    out_left[dst] = i;
+    out_right[dst] = -1;
+  }
+}
+
+// Validity of the right indices: bit d = out_right[d] >= 0, one ballot word per wave; the -1 marks become 0.
+__global__ void __launch_bounds__(kBlock) right_validity_kernel(int64_t* out_right, int64_t n, uint64_t* out_bits) {
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  for (int64_t base = int64_t(blockIdx.x) * kBlock; base < n; base += stride) {
+    const int64_t d = base + threadIdx.x;
+    bool valid = false;
+    if (d < n) {
+      valid = out_right[d] >= 0;
+      if (!valid) out_right[d] = 0;
+    }
+    const uint64_t word = __ballot(valid);
+    if (lane_id() == 0 && (d >> 6) < ((n + 63) >> 6)) out_bits[d >> 6] = word;
+  }
+}
+
+// bit i = (flags[i] != 0) == (want_set != 0); one ballot word per wave.
+__global__ void __launch_bounds__(kBlock) flags_to_mask_kernel(const uint8_t* flags, int64_t n, int want_set, uint64_t* out) {
+  const int64_t stride = int64_t(gridDim.x) * kBlock;
+  for (int64_t base = int64_t(blockIdx.x) * kBlock; base < n; base += stride) {
+    const int64_t i = base + threadIdx.x;
+    const bool hit = i < n && (flags[i] != 0) == (want_set != 0);
+    const uint64_t word = __ballot(hit);
+    if (lane_id() == 0 && (i >> 6) < ((n + 63) >> 6)) out[i >> 6] = word;
+  }
+}
+
 int check_join_type(int jt, const char* what) {
   if (jt < kLeftSemi || jt > kFullOuter) {
     set_error("%s: join type %d is not an arrow::acero::JoinType (0 .. 7)", what, jt);
@@ -473,6 +589,95 @@ int arx_hash_join_append_build_rows(const uint64_t* build_rows, int64_t count, i
                      start, out_left, static_cast<uint64_t*>(out_left_validity), out_right,
                      static_cast<uint64_t*>(out_right_validity));
   ARX_CHECK_LAUNCH("append_build_rows_kernel");
+  return ARX_OK;
+}
+
+int arx_hash_join_filter_count(const ArxSpan* pass, const int64_t* offsets, const int64_t* cand_right,
+                               int64_t num_probe_rows, int join_type, uint8_t* build_hit, uint8_t* probe_hit,
+                               int64_t max_output, void* out_pass_bits, int64_t* out_pass_prefix, int64_t* out_new_offsets,
+                               void* ws, size_t ws_bytes, int64_t* out_total, void* stream) {
+  if (const int rc = check_join_type(join_type, "hash join filter count"); rc != ARX_OK) return rc;
+  if (pass == nullptr || pass->length < 0 || num_probe_rows < 0 || out_pass_prefix == nullptr || out_new_offsets == nullptr ||
+      out_total == nullptr || (num_probe_rows > 0 && offsets == nullptr) ||
+      (pass->length > 0 && (pass->data == nullptr || out_pass_bits == nullptr || num_probe_rows == 0)) ||
+      (pass->length > 0 && build_hit != nullptr && cand_right == nullptr)) {
+    set_error("hash join filter count: NULL argument, negative length or candidates without probe rows");
+    return ARX_INVALID;
+  }
+  hipStream_t st = as_stream(stream);
+  const int64_t total = pass->length, words = (total + 63) >> 6;
+  if (total > 0) {
+    const Bits values = make_bits(pass->data, pass->offset, total);
+    const Bits validity = make_bits(pass->null_count == 0 ? nullptr : pass->validity, pass->offset, total);
+    hipLaunchKernelGGL(filter_pass_kernel, dim3(grid_for(total)), dim3(kBlock), 0, st, values, validity, total, cand_right,
+                       build_hit, static_cast<uint64_t*>(out_pass_bits), out_pass_prefix);
+    ARX_CHECK_LAUNCH("filter_pass_kernel");
+  }
+  if (const int rc = scan_in_place(out_pass_prefix, words, ws, ws_bytes, st); rc != ARX_OK) return rc;
+  if (num_probe_rows > 0) {
+    hipLaunchKernelGGL(filter_count_kernel, dim3(grid_for(num_probe_rows)), dim3(kBlock), 0, st, offsets, num_probe_rows,
+                       static_cast<const uint64_t*>(out_pass_bits), out_pass_prefix, join_type, probe_hit, out_new_offsets);
+    ARX_CHECK_LAUNCH("filter_count_kernel");
+  }
+  if (const int rc = scan_in_place(out_new_offsets, num_probe_rows, ws, ws_bytes, st); rc != ARX_OK) return rc;
+  uint64_t header[2] = {0, 0};
+  ARX_HIP(hipMemcpyAsync(header, ws, sizeof(header), hipMemcpyDeviceToHost, st));
+  ARX_HIP(hipStreamSynchronize(st));
+  *out_total = static_cast<int64_t>(header[0]);   // at most T + num_probe_rows: no overflow to report
+  if (max_output >= 0 && *out_total > max_output) {
+    set_error("hash join: the filtered output would have %lld rows, more than the %lld that can be allocated",
+              (long long)*out_total, (long long)max_output);
+    return ARX_CAPACITY_ERROR;
+  }
+  return ARX_OK;
+}
+
+int arx_hash_join_filter_compact(const void* pass_bits, const int64_t* pass_prefix, int64_t num_candidates,
+                                 const int64_t* offsets, const int64_t* new_offsets, int64_t num_probe_rows,
+                                 const int64_t* cand_left, const int64_t* cand_right, int join_type, int64_t total,
+                                 int64_t* out_left, int64_t* out_right, void* out_right_validity, void* stream) {
+  if (const int rc = check_join_type(join_type, "hash join filter compact"); rc != ARX_OK) return rc;
+  if (join_type != kInner && join_type != kLeftOuter && join_type != kRightOuter && join_type != kFullOuter) {
+    set_error("hash join filter compact: join type %d emits no pairs (semi / anti rows come from the flags)", join_type);
+    return ARX_INVALID;
+  }
+  const bool outer = join_type == kLeftOuter || join_type == kFullOuter;
+  if (num_candidates < 0 || num_probe_rows < 0 || total < 0 ||
+      (total > 0 && (out_left == nullptr || out_right == nullptr || offsets == nullptr || new_offsets == nullptr ||
+                     pass_prefix == nullptr)) ||
+      (total > 0 && outer && out_right_validity == nullptr) ||
+      (num_candidates > 0 && (pass_bits == nullptr || cand_left == nullptr || cand_right == nullptr))) {
+    set_error("hash join filter compact: NULL argument or negative length");
+    return ARX_INVALID;
+  }
+  if (total == 0) return ARX_OK;
+  hipStream_t st = as_stream(stream);
+  if (num_candidates > 0) {
+    hipLaunchKernelGGL(filter_compact_kernel, dim3(grid_for(num_candidates)), dim3(kBlock), 0, st,
+                       static_cast<const uint64_t*>(pass_bits), pass_prefix, num_candidates, offsets, new_offsets, cand_left,
+                       cand_right, out_left, out_right);
+    ARX_CHECK_LAUNCH("filter_compact_kernel");
+  }
+  if (outer) {
+    hipLaunchKernelGGL(filter_unmatched_kernel, dim3(grid_for(num_probe_rows)), dim3(kBlock), 0, st, offsets, new_offsets,
+                       num_probe_rows, static_cast<const uint64_t*>(pass_bits), pass_prefix, out_left, out_right);
+    ARX_CHECK_LAUNCH("filter_unmatched_kernel");
+    hipLaunchKernelGGL(right_validity_kernel, dim3(grid_for(total)), dim3(kBlock), 0, st, out_right, total,
+                       static_cast<uint64_t*>(out_right_validity));
+    ARX_CHECK_LAUNCH("right_validity_kernel");
+  }
+  return ARX_OK;
+}
+
+int arx_hash_join_flags_to_mask(const uint8_t* flags, int64_t length, int want_set, void* out_bits, void* stream) {
+  if (length < 0 || (length > 0 && (flags == nullptr || out_bits == nullptr))) {
+    set_error("hash join flags to mask: NULL argument or negative length");
+    return ARX_INVALID;
+  }
+  if (length == 0) return ARX_OK;
+  hipLaunchKernelGGL(flags_to_mask_kernel, dim3(grid_for(length)), dim3(kBlock), 0, as_stream(stream), flags, length,
+                     want_set, static_cast<uint64_t*>(out_bits));
+  ARX_CHECK_LAUNCH("flags_to_mask_kernel");
   return ARX_OK;
 }
 

@@ -17,7 +17,8 @@
 //   table_source  a table with a device-resident column -> RocmTableSourceNode (whole chunks), else the stock node;
 //   aggregate     downstream of a RocmTableSourceNode / coalesce_rocm -> aggregate_rocm, falling back to the stock
 //                 GroupByNode / ScalarAggregateNode for what aggregate_rocm declines (NotImplemented);
-//   order_by      likewise -> order_by_rocm.
+//   order_by      likewise -> order_by_rocm;
+//   hashjoin      (always, as part of the guard) a device source on either side -> hashjoin_rocm or its NotImplemented.
 // arrow_amd_override_acero_factories(0) switches the re-routing off again; the wrappers stay in place as the GUARD described
 // further down (a keyed aggregation over device-resident key columns never reaches the reference's CPU Grouper).
 // Call it while no plan is being built on another thread: the registry has no lock, the entries are replaced once (at
@@ -52,7 +53,8 @@ arrow::Result<AceroFactoryMap*> DefaultRegistryFactories() {
                                   "(vptr + unordered_map): Acero factories left as they are");
   }
   auto* map = reinterpret_cast<AceroFactoryMap*>(after_vptr);
-  for (const char* name : {"aggregate_rocm", "table_source_rocm", "order_by_rocm", "aggregate", "table_source", "order_by", "filter"}) {
+  for (const char* name : {"aggregate_rocm", "table_source_rocm", "order_by_rocm", "hashjoin_rocm", "aggregate", "table_source", "order_by", "hashjoin",
+                           "filter"}) {
     if (map->find(name) == map->end()) {
       return Status::NotImplemented("arrow_amd: the default ExecFactoryRegistry's map was not recognised (no '", name, "')");
     }
@@ -262,7 +264,7 @@ Status OverrideAceroFactories(int mode) {
   g_override_full.store(mode > 0);
   g_source_whole_chunks.store(mode >= 0);
   if (!g_stock_factories.empty()) return Status::OK();   // the wrappers are in place: `on` is all they look at
-  for (const char* name : {"table_source", "aggregate", "order_by"}) g_stock_factories[name] = (*map)[name];
+  for (const char* name : {"table_source", "aggregate", "order_by", "hashjoin"}) g_stock_factories[name] = (*map)[name];
   const AceroFactory stock_source = g_stock_factories["table_source"];
   (*map)["table_source"] = [stock_source](ac::ExecPlan* plan, std::vector<ac::ExecNode*> inputs,
                                           const ac::ExecNodeOptions& options) -> arrow::Result<ac::ExecNode*> {
@@ -314,6 +316,25 @@ Status OverrideAceroFactories(int mode) {
       if (made.ok() || !made.status().IsNotImplemented()) return made;
     }
     return stock_order_by(plan, std::move(inputs), options);
+  };
+  // hashjoin: HashJoinNode row-encodes keys and payload on the CPU.  With a remembered device source among the inputs of
+  // either side the join is hashjoin_rocm, or its NotImplemented: such a plan never reaches the stock node.
+  const AceroFactory stock_hashjoin = g_stock_factories["hashjoin"];
+  (*map)["hashjoin"] = [stock_hashjoin](ac::ExecPlan* plan, std::vector<ac::ExecNode*> inputs,
+                                        const ac::ExecNodeOptions& options) -> arrow::Result<ac::ExecNode*> {
+    std::vector<DeviceSourceInfo> tables;
+    CollectDeviceSources(inputs, &tables);
+    if (tables.empty()) return stock_hashjoin(plan, std::move(inputs), options);
+    auto made = RocmHashJoinNode::Make(plan, inputs, options);
+    if (made.ok()) {
+      if (!g_override_full.load()) g_guard_takeovers.fetch_add(1, std::memory_order_relaxed);
+      return made;
+    }
+    if (!made.status().IsNotImplemented()) return made;
+    g_guard_refusals.fetch_add(1, std::memory_order_relaxed);
+    return made.status().WithMessage(made.status().message(),
+                                     " (arrow_amd: an input of this join is device-resident; the reference's HashJoinNode "
+                                     "encodes rows on the host — refused instead)");
   };
   return Status::OK();
 }

@@ -14,7 +14,9 @@
 // indices as the reference node; registered under a NEW name (duplicates are rejected, acero/exec_plan.cc:1132-1142).
 // TableSourceNodeOptions::max_batch_size left at its default (1Mi rows, options.h kDefaultTableSourceNodeMaxBatchSize)
 // is replaced by the plugin's table_source_rows (2^27): the default was chosen for host memory.
-// Nodes that index rows with 16 bits (the hash join's) must not sit downstream of this source.
+// Nodes that index rows with 16 bits (the hash join's) must not sit downstream of this source.  The guard in
+// plugin/acero_override.inc keeps the stock `hashjoin` away from it: a join with a remembered device source among its
+// inputs is built as hashjoin_rocm (plugin/hash_join_node.inc) or refused with a Status.
 class RocmTableSourceNode : public ac::ExecNode {
  public:
   RocmTableSourceNode(ac::ExecPlan* plan, std::shared_ptr<arrow::Table> table, int64_t batch_rows)

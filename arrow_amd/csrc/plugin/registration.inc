@@ -357,6 +357,10 @@ Status RegisterAll() {
     if (!st.ok() && !st.IsKeyError()) return st;
   }
   {
+    const Status st = ac::default_exec_factory_registry()->AddFactory("hashjoin_rocm", RocmHashJoinNode::Make);
+    if (!st.ok() && !st.IsKeyError()) return st;
+  }
+  {
     const Status st = ac::default_exec_factory_registry()->AddFactory("table_source_rocm", RocmTableSourceNode::Make);
     if (!st.ok() && !st.IsKeyError()) return st;
   }

@@ -1278,7 +1278,33 @@ int arx_set_lookup_index_in_binary(const void* state, const ArxBinarySpan* value
  * arx_filter_count + arx_mask_to_indices (index_width 8).  Asynchronous.
  * arx_hash_join_append_build_rows: slots [start, start + count) get a null left index and out_right = build_rows[k]
  * (uint64 row numbers); out_left_validity (ceil((start + count) / 64) words) is written whole: valid below start, null
- * from it; out_right_validity (may be NULL) keeps its bits below start and is set from it.  Asynchronous. */
+ * from it; out_right_validity (may be NULL) keeps its bits below start and is set from it.  Asynchronous.
+ *
+ * Residual filter (HashJoinNodeOptions::filter): a pair of key-equal rows is a match only where the filter is true; a
+ * null result is no match.  It is not a post-filter: it decides which probe and build ROWS count as matched for outer,
+ * semi and anti joins (per build row, not per group: the filter tells apart rows that share a key).  The caller counts
+ * and expands the CANDIDATES as an inner join (offsets[num_probe_rows + 1], cand_left[T], cand_right[T] from
+ * arx_hash_join_probe_count / arx_hash_join_expand), gathers the columns the filter reads, evaluates it over the T
+ * slots and passes the boolean column.  The row order above holds among the passing pairs.
+ * arx_hash_join_filter_count: synchronous (one read-back: the filtered total).  pass: a boolean column of T rows, any
+ * offset (data = its value bits, validity may be NULL).  out_pass_bits (ceil(T / 64) words) = value AND validity;
+ * out_pass_prefix[ceil(T / 64) + 1] (int64) = the passing slots before each 64-slot word, the last entry their total.
+ * out_new_offsets[num_probe_rows + 1] = the exclusive scan of every probe row's output rows given the p passing slots of
+ * its run [offsets[i], offsets[i + 1]): p (inner, right outer), max(p, 1) (left / full outer), p > 0 (left semi), p == 0
+ * (left anti), 0 (right semi / anti); *out_total = the sum (the right-only tail not included).  build_hit (one byte per
+ * build row, caller-zeroed, may be NULL): set to 1 at cand_right[j] of every passing slot j.  probe_hit (one byte per
+ * probe row, may be NULL): 1 where p > 0, else 0.  ws: arx_hash_join_workspace_bytes(max(num_probe_rows, ceil(T / 64))).
+ * A total above max_output (>= 0; -1: no limit) returns ARX_CAPACITY_ERROR before anything is allocated for the output.
+ * pass->length must equal offsets[num_probe_rows], the candidate total the probe count returned: that entry lives on the
+ * device and is not re-read, so a shorter pass column is the caller's error (words past its end would be read).
+ * arx_hash_join_filter_compact (inner and outer joins): passing slot j of probe row r = cand_left[j] is written to output
+ * slot new_offsets[r] + (passing slots in [offsets[r], j)); a left / full outer row without a passing slot gets
+ * (r, null) at new_offsets[r] (right index 0, bit clear); out_right_validity (ceil(total / 64) words, left / full outer
+ * only) is written whole.  One lane per candidate slot and one per probe row: a key with many build rows costs per slot
+ * what any other input costs.  Asynchronous.
+ * arx_hash_join_flags_to_mask: out_bits bit i = (flags[i] != 0) == (want_set != 0) over `length` byte flags: build rows
+ * hit / not hit (right semi, right anti and the right-only tail), probe rows with / without a passing pair (left semi /
+ * anti); to compact with arx_filter_count + arx_mask_to_indices.  Asynchronous. */
 size_t arx_hash_join_workspace_bytes(int64_t length);
 int arx_hash_join_key_validity(const ArxSpan* columns, int num_columns, int64_t length, void* out_bits, void* stream);
 int arx_hash_join_bool_key(const ArxSpan* values, uint8_t* out, void* stream);
@@ -1295,6 +1321,15 @@ int arx_hash_join_build_mask(const uint32_t* build_ids, const void* build_valid,
                              const uint8_t* matched, int want_matched, void* out_bits, void* stream);
 int arx_hash_join_append_build_rows(const uint64_t* build_rows, int64_t count, int64_t start, int64_t* out_left,
                                     void* out_left_validity, int64_t* out_right, void* out_right_validity, void* stream);
+int arx_hash_join_filter_count(const ArxSpan* pass, const int64_t* offsets, const int64_t* cand_right,
+                               int64_t num_probe_rows, int join_type, uint8_t* build_hit, uint8_t* probe_hit,
+                               int64_t max_output, void* out_pass_bits, int64_t* out_pass_prefix, int64_t* out_new_offsets,
+                               void* ws, size_t ws_bytes, int64_t* out_total, void* stream);
+int arx_hash_join_filter_compact(const void* pass_bits, const int64_t* pass_prefix, int64_t num_candidates,
+                                 const int64_t* offsets, const int64_t* new_offsets, int64_t num_probe_rows,
+                                 const int64_t* cand_left, const int64_t* cand_right, int join_type, int64_t total,
+                                 int64_t* out_left, int64_t* out_right, void* out_right_validity, void* stream);
+int arx_hash_join_flags_to_mask(const uint8_t* flags, int64_t length, int want_set, void* out_bits, void* stream);
 
 #ifdef __cplusplus
 }

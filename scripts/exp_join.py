@@ -1,9 +1,11 @@
 """Times the full-size inner join: 2^27 int64 probe rows against 2^24 build rows, a quarter of the build keys
 duplicated (the keys of tests/test_hash_join.py::test_gpu_hash_join_full_size).  Device route: the mirror,
 compute.hash_join_indices (Grouper consume / lookup, csrc/hash_join.hip, the stable sort of the build ids).
-Baseline: pa.Table.join of the same keys on the host, on up to 16 CPU threads.  Prints one JSON line.
+Baseline: pa.Table.join of the same keys on the host, on up to 16 CPU threads.  A second leg adds a residual filter that
+passes about half the pairs (left row number + right row number even; left outer, so the count, compact, unmatched-row
+and validity kernels all run); the predicate's element-wise calls are timed apart.  Prints one JSON line.
 
-    python scripts/exp_join.py [--log2-probe 27] [--log2-build 24] [--reps 5]
+    python scripts/exp_join.py [--log2-probe 27] [--log2-build 24] [--reps 5] [--host-reps 1]
 """
 import argparse
 import json
@@ -47,6 +49,34 @@ def main():
             times.append(time.perf_counter() - t0)
         rows = li.length
         del li, ri
+    # residual filter: (lid + rid) even, about half the pairs; evaluated with the mirror's element-wise kernels
+    def half(lrows, rrows):
+        s = amd.compute.add(lrows, rrows)
+        q = amd.compute.divide(s, 2)
+        return amd.compute.equal(amd.compute.add(q, q), s)
+
+    # the predicate's own element-wise calls are timed apart, so that the rest is the join with its filter kernels
+    ftimes, ptimes, frows, cands = [], [], 0, 0
+    for i in range(a.reps + 1):
+        spent = [0.0]
+
+        def timed(lrows, rrows):
+            torch.cuda.synchronize()
+            p0 = time.perf_counter()
+            out = half(lrows, rrows)
+            torch.cuda.synchronize()
+            spent[0] += time.perf_counter() - p0
+            return out
+
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        li, ri = amd.compute.hash_join_indices([dprobe], [dbuild], "left outer", filter=timed)
+        torch.cuda.synchronize()
+        if i:
+            ftimes.append(time.perf_counter() - t0 - spent[0])
+            ptimes.append(spent[0])
+        frows, cands = li.length, rows
+        del li, ri
     pa.set_cpu_count(min(16, os.cpu_count() or 1))
     lt = pa.table({"k": probe, "lid": np.arange(nl, dtype=np.int64)})
     rt = pa.table({"k": build, "rid": np.arange(nb, dtype=np.int64)})
@@ -60,6 +90,9 @@ def main():
     dev_ms = 1e3 * float(np.median(times))
     host_ms = 1e3 * float(np.median(host)) if host else float("nan")
     print(json.dumps({"probe_rows": nl, "build_rows": nb, "output_rows": int(rows), "device_mirror_ms": round(dev_ms, 2),
+                      "filtered_left_outer_rows": int(frows), "candidate_pairs": int(cands),
+                      "device_mirror_filtered_ms_without_predicate": round(1e3 * float(np.median(ftimes)), 2),
+                      "predicate_ms": round(1e3 * float(np.median(ptimes)), 2),
                       "host_pa_join_ms": round(host_ms, 2), "host_threads": pa.cpu_count(),
                       "speedup": round(host_ms / dev_ms, 1) if host else None}))
 
