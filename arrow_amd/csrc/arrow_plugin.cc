@@ -86,6 +86,7 @@ namespace {
 #include "plugin/selection.inc"
 #include "plugin/selection_nested.inc"
 #include "plugin/selection_meta.inc"
+#include "plugin/acero_common.inc"
 #include "plugin/scalar.inc"
 #include "plugin/sort.inc"
 #include "plugin/cast.inc"
@@ -96,6 +97,7 @@ namespace {
 #include "plugin/set_lookup.inc"
 #include "plugin/scalar_aggregate.inc"
 #include "plugin/coalesce.inc"
+#include "plugin/grouper_chain.inc"
 #include "plugin/acero_node.inc"
 #include "plugin/acero_node_general.inc"
 #include "plugin/sharded.inc"

@@ -7,15 +7,15 @@
 // (acero/source_node.cc:122-160) — over device-resident columns FilterNode / ProjectNode (filter_node.cc:73-108) then
 // pay a handful of launches and a count read-back 8192 times for 2^28 rows (1.8 s against 12 ms).  This node gathers its
 // input and hands it on as batches of at least `coalesce_rows` rows (2^26; arrow_amd_plugin_set_coalesce_rows), in the
-// order of the batch indices: Concatenate per column on the device (RocmOrderByNode::ConcatOnDevice — consecutive
+// order of the batch indices: Concatenate per column on the device (ConcatOnDevice — consecutive
 // slices of one device array, which is what table_source makes of a device table, are re-joined without a copy).
-// It waits for the end of its input (a pipeline breaker, like the order-by and aggregate nodes it usually feeds).
+// It waits for the end of its input (an AccumulatingNode, like the order-by and aggregate nodes it usually feeds).
 // Host-resident batches pass through untouched: coalescing them would move them to the device behind the caller's back.
 // No options of its own (any ExecNodeOptions object is accepted and ignored); registered under a NEW name.
-class RocmCoalesceNode : public ac::ExecNode {
+class RocmCoalesceNode : public AccumulatingNode {
  public:
   RocmCoalesceNode(ac::ExecPlan* plan, std::vector<ac::ExecNode*> inputs, std::shared_ptr<arrow::Schema> schema)
-      : ac::ExecNode(plan, std::move(inputs), {"input"}, std::move(schema)) {}
+      : AccumulatingNode(plan, std::move(inputs), {"input"}, std::move(schema)) {}
 
   static arrow::Result<ac::ExecNode*> Make(ac::ExecPlan* plan, std::vector<ac::ExecNode*> inputs, const ac::ExecNodeOptions&) {
     if (inputs.size() != 1) return Status::Invalid("coalesce_rocm takes exactly one input");
@@ -32,25 +32,6 @@ class RocmCoalesceNode : public ac::ExecNode {
   const char* kind_name() const override { return "RocmCoalesceNode"; }
   const cp::Ordering& ordering() const override { return inputs_[0]->ordering(); }
 
-  Status InputReceived(ac::ExecNode*, cp::ExecBatch batch) override {
-    {
-      std::lock_guard<std::mutex> lock(mu_);
-      batches_.push_back(std::move(batch));
-    }
-    if (counter_.Increment()) return Finish();
-    return Status::OK();
-  }
-  Status InputFinished(ac::ExecNode*, int total_batches) override {
-    if (counter_.SetTotal(total_batches)) return Finish();
-    return Status::OK();
-  }
-  Status StartProducing() override { return Status::OK(); }
-  void PauseProducing(ac::ExecNode*, int32_t) override {}
-  void ResumeProducing(ac::ExecNode*, int32_t) override {}
-
- protected:
-  Status StopProducingImpl() override { return Status::OK(); }
-
  private:
   static bool AllDeviceArrays(const cp::ExecBatch& b) {
     for (const auto& v : b.values) {
@@ -59,30 +40,27 @@ class RocmCoalesceNode : public ac::ExecNode {
     return !b.values.empty();
   }
 
-  Status Finish() {
-    std::lock_guard<std::mutex> lock(mu_);
+  Status Finish() override {
     hipStream_t st;
     ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
-    const bool indexed = std::all_of(batches_.begin(), batches_.end(), [](const cp::ExecBatch& b) { return b.index >= 0; });
-    if (indexed) {
-      std::stable_sort(batches_.begin(), batches_.end(), [](const cp::ExecBatch& a, const cp::ExecBatch& b) { return a.index < b.index; });
-    }
+    std::vector<cp::ExecBatch>& batches = batches_[0];
+    OrderBatchesByIndex(&batches);
     const int64_t target = std::max<int64_t>(g_coalesce_rows.load(), 1);
     const int ncols = output_schema()->num_fields();
     int emitted = 0;
     size_t i = 0;
-    while (i < batches_.size()) {
-      if (!AllDeviceArrays(batches_[i])) {   // host rows (or scalar columns): handed on as they came
-        cp::ExecBatch b = std::move(batches_[i++]);
+    while (i < batches.size()) {
+      if (!AllDeviceArrays(batches[i])) {   // host rows (or scalar columns): handed on as they came
+        cp::ExecBatch b = std::move(batches[i++]);
         b.index = emitted++;
         ARROW_RETURN_NOT_OK(output_->InputReceived(this, std::move(b)));
         continue;
       }
       size_t j = i;
       int64_t rows = 0;
-      while (j < batches_.size() && AllDeviceArrays(batches_[j]) && (rows < target || j == i)) rows += batches_[j++].length;
+      while (j < batches.size() && AllDeviceArrays(batches[j]) && (rows < target || j == i)) rows += batches[j++].length;
       if (j == i + 1) {
-        cp::ExecBatch b = std::move(batches_[i]);
+        cp::ExecBatch b = std::move(batches[i]);
         b.index = emitted++;
         ARROW_RETURN_NOT_OK(output_->InputReceived(this, std::move(b)));
       } else {
@@ -90,8 +68,8 @@ class RocmCoalesceNode : public ac::ExecNode {
         for (int c = 0; c < ncols; ++c) {
           std::vector<std::shared_ptr<ArrayData>> chunks;
           chunks.reserve(j - i);
-          for (size_t k = i; k < j; ++k) chunks.push_back(batches_[k].values[c].array());
-          ARROW_ASSIGN_OR_RAISE(auto joined, RocmOrderByNode::ConcatOnDevice(output_schema()->field(c)->type(), chunks, st));
+          for (size_t k = i; k < j; ++k) chunks.push_back(batches[k].values[c].array());
+          ARROW_ASSIGN_OR_RAISE(auto joined, ConcatOnDevice(output_schema()->field(c)->type(), chunks, st));
           columns[c] = arrow::Datum(std::move(joined));
         }
         cp::ExecBatch out(std::move(columns), rows);
@@ -101,11 +79,7 @@ class RocmCoalesceNode : public ac::ExecNode {
       }
       i = j;
     }
-    batches_.clear();
+    batches.clear();
     return output_->InputFinished(this, emitted);
   }
-
-  std::mutex mu_;
-  ac::AtomicCounter counter_;
-  std::vector<cp::ExecBatch> batches_;
 };

@@ -8,12 +8,10 @@
 // (acero/groupby_aggregate_node.cc:210-337) for `hash_sum(int64) GROUP BY int32`: instead of a CPU
 // Grouper feeding dense ids to the aggregate kernel, keys and values go to the fused device
 // operator (arx_groupby_*: hash partition -> LDS tables -> HBM table).  Batches without nulls are
-// appended to device staging buffers and consumed in ONE partitioned pass at InputFinished; a batch
-// with nulls is consumed on arrival.  Output = key column ++ aggregate column like
+// appended to device staging buffers and consumed in ONE partitioned pass when the input ends; a batch
+// with nulls is consumed on arrival (the node overrides AccumulatingNode::Accept and keeps no batch).  Output = key column ++ aggregate column like
 // GroupByNode::Finalize (:300-333), row order unspecified (as the reference with threads).
-namespace ac = arrow::acero;
-
-class RocmGroupBySumNode : public ac::ExecNode {
+class RocmGroupBySumNode : public AccumulatingNode {
  public:
   // one output column per requested aggregate; all of them read the same fused per-group state
   // (wrap-around sum, count of valid values, "a null value was seen")
@@ -26,7 +24,7 @@ class RocmGroupBySumNode : public ac::ExecNode {
   RocmGroupBySumNode(ac::ExecPlan* plan, std::vector<ac::ExecNode*> inputs,
                      std::shared_ptr<arrow::Schema> out_schema, int key_idx, int val_idx,
                      std::vector<AggSpec> aggs)
-      : ac::ExecNode(plan, std::move(inputs), {"input"}, std::move(out_schema)),
+      : AccumulatingNode(plan, std::move(inputs), {"input"}, std::move(out_schema)),
         key_idx_(key_idx), val_idx_(val_idx), aggs_(std::move(aggs)) {
     for (const auto& a : aggs_) needs_minmax_ = needs_minmax_ || a.kind == kMin || a.kind == kMax || a.kind == kMean;
   }
@@ -100,27 +98,13 @@ class RocmGroupBySumNode : public ac::ExecNode {
 
   const char* kind_name() const override { return "RocmGroupBySumNode"; }
 
-  Status InputReceived(ac::ExecNode*, cp::ExecBatch batch) override {
-    {
-      std::lock_guard<std::mutex> lock(mu_);
-      largest_input_batch_ = std::max(largest_input_batch_, batch.length);
-      ARROW_RETURN_NOT_OK(Consume(batch));
-    }
-    if (counter_.Increment()) return Finish();
-    return Status::OK();
-  }
-  Status InputFinished(ac::ExecNode*, int total_batches) override {
-    if (counter_.SetTotal(total_batches)) return Finish();
-    return Status::OK();
-  }
-  Status StartProducing() override { return Status::OK(); }
-  void PauseProducing(ac::ExecNode*, int32_t) override {}
-  void ResumeProducing(ac::ExecNode*, int32_t) override {}
-
- protected:
-  Status StopProducingImpl() override { return Status::OK(); }
-
  private:
+  // batches are consumed (or staged) as they arrive instead of being kept
+  Status Accept(int, cp::ExecBatch batch) override {
+    largest_input_batch_ = std::max(largest_input_batch_, batch.length);
+    return Consume(batch);
+  }
+
   static constexpr int64_t kMaxCapacity = int64_t(1) << 28;
 
   // {min, max} of the key slots of one device column folded into key_lo_ / key_hi_ (one pass over 4 B/row and an 8-byte
@@ -155,15 +139,13 @@ class RocmGroupBySumNode : public ac::ExecNode {
     hipStream_t st;
     ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
     // (pooled: a GB-sized hipMalloc per plan costs more than the whole aggregation)
-    ARROW_ASSIGN_OR_RAISE(auto fresh_buf, AllocDevice(static_cast<int64_t>(arx_groupby_state_bytes(cap)) + 256));
-    std::shared_ptr<Buffer> fresh_mm_buf;
-    void* fresh = reinterpret_cast<void*>((fresh_buf->mutable_address() + 255) & ~uintptr_t(255));
-    void* fresh_mm = nullptr;
+    ARROW_ASSIGN_OR_RAISE(auto fresh_table, AllocAligned(static_cast<int64_t>(arx_groupby_state_bytes(cap))));
+    AlignedDevice fresh_minmax{nullptr, nullptr};
+    void* const fresh = fresh_table.ptr;
     ARROW_RETURN_NOT_OK(FromArx(arx_groupby_init(fresh, cap, st)));
     if (needs_minmax_) {
-      ARROW_ASSIGN_OR_RAISE(fresh_mm_buf, AllocDevice(static_cast<int64_t>(arx_groupby_minmax_bytes(cap)) + 256));
-      fresh_mm = reinterpret_cast<void*>((fresh_mm_buf->mutable_address() + 255) & ~uintptr_t(255));
-      ARROW_RETURN_NOT_OK(FromArx(arx_groupby_minmax_init(fresh_mm, cap, st)));
+      ARROW_ASSIGN_OR_RAISE(fresh_minmax, AllocAligned(static_cast<int64_t>(arx_groupby_minmax_bytes(cap))));
+      ARROW_RETURN_NOT_OK(FromArx(arx_groupby_minmax_init(fresh_minmax.ptr, cap, st)));
     }
     if (state_ != nullptr) {  // rehash: export the old table's partial aggregates, merge them
       int64_t g = 0;
@@ -186,7 +168,7 @@ class RocmGroupBySumNode : public ac::ExecNode {
                                                               (const int64_t*)s, (const int64_t*)c,
                                                               (const uint8_t*)nn, g, st)));
         if (needs_minmax_) {
-          ARROW_RETURN_NOT_OK(FromArx(arx_groupby_minmax_merge(fresh, fresh_mm, cap, (const int32_t*)k,
+          ARROW_RETURN_NOT_OK(FromArx(arx_groupby_minmax_merge(fresh, fresh_minmax.ptr, cap, (const int32_t*)k,
                                                                (const uint8_t*)kv, (const int64_t*)mn,
                                                                (const int64_t*)mx, (const uint8_t*)nn, g, st)));
         }
@@ -194,10 +176,10 @@ class RocmGroupBySumNode : public ac::ExecNode {
       HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
       // (the old table goes back to the pool when its buffers are replaced below)
     }
-    state_buf_ = std::move(fresh_buf);
-    minmax_buf_ = std::move(fresh_mm_buf);
+    state_buf_ = std::move(fresh_table.buffer);
+    minmax_buf_ = std::move(fresh_minmax.buffer);
     state_ = fresh;
-    minmax_ = fresh_mm;
+    minmax_ = fresh_minmax.ptr;
     capacity_ = cap;
     return Status::OK();
   }
@@ -222,16 +204,14 @@ class RocmGroupBySumNode : public ac::ExecNode {
     return Status::OK();
   }
 
-  static int64_t ValidityBytes(int64_t rows) { return ((rows + 63) / 64) * 8 + 8; }
-
   // (re)allocate the two staged validity bitmaps for staged_cap_ rows, zeroed behind the first keep_rows rows
   Status AllocStagedValidity(int64_t keep_rows) {
     hipStream_t st;
     ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
     for (std::shared_ptr<Buffer>* buf : {&kvalid_buf_, &vvalid_buf_}) {
-      ARROW_ASSIGN_OR_RAISE(auto fresh, AllocDevice(ValidityBytes(staged_cap_)));
+      ARROW_ASSIGN_OR_RAISE(auto fresh, AllocDevice(BitmapBytes(staged_cap_)));
       HIP_RETURN_NOT_OK(hipMemsetAsync(reinterpret_cast<void*>(fresh->mutable_address()), 0,
-                                       static_cast<size_t>(ValidityBytes(staged_cap_)), st));
+                                       static_cast<size_t>(BitmapBytes(staged_cap_)), st));
       if (keep_rows > 0 && *buf != nullptr) {
         HIP_RETURN_NOT_OK(hipMemcpyAsync(reinterpret_cast<void*>(fresh->mutable_address()),
                                          reinterpret_cast<const void*>((*buf)->address()),
@@ -352,7 +332,7 @@ class RocmGroupBySumNode : public ac::ExecNode {
     void* ws = nullptr;
     if (ws_bytes > 0) {
       ARROW_RETURN_NOT_OK(t_scratch.Get(kWs, ws_bytes + 256, &ws));
-      ws = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
+      ws = Align256(ws);
     }
     ARROW_RETURN_NOT_OK(FromArx(arx_groupby_sum_i64_consume(state_, capacity_, &dk, &dv, ws, ws_bytes, st)));
     if (needs_minmax_) {
@@ -526,7 +506,7 @@ class RocmGroupBySumNode : public ac::ExecNode {
     HIP_RETURN_NOT_OK(hipMemsetAsync(blocks, 0, static_cast<size_t>(plan.state_bytes), st));
     void* ws = nullptr;
     ARROW_RETURN_NOT_OK(t_scratch.Get(kWs, static_cast<size_t>(plan.workspace_bytes) + 256, &ws));
-    ws = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
+    ws = Align256(ws);
     const int rc = arx_groupby_range_sum_i64_consume(blocks, &plan, &dk, &dv, ws, static_cast<size_t>(plan.workspace_bytes), st);
     if (rc == ARX_CAPACITY_ERROR || rc == ARX_NOT_IMPLEMENTED) {
       g_aggregate_range_declined.fetch_add(1);
@@ -543,7 +523,7 @@ class RocmGroupBySumNode : public ac::ExecNode {
     ARROW_RETURN_NOT_OK(t_scratch.Get(kArg2Validity, slots * 8 + 16, c));
     ARROW_RETURN_NOT_OK(t_scratch.Get(kValidity, slots + 16, ones));
     ARROW_RETURN_NOT_OK(t_scratch.Get(kBinWs, fws_bytes + 256, &fws));
-    fws = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(fws) + 255) & ~uintptr_t(255));
+    fws = Align256(fws);
     ARROW_RETURN_NOT_OK(t_scratch.Get(kCounter, 64, &count));
     HIP_RETURN_NOT_OK(hipMemsetAsync(count, 0, 8, st));
     ARROW_RETURN_NOT_OK(FromArx(arx_groupby_range_finalize(blocks, plan.key_min, plan.width, plan.partitions, 0, fws, fws_bytes,
@@ -563,8 +543,7 @@ class RocmGroupBySumNode : public ac::ExecNode {
     return Status::OK();
   }
 
-  Status Finish() {
-    std::lock_guard<std::mutex> lock(mu_);
+  Status Finish() override {
     PhaseTiming timing;
     hipStream_t st;
     ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
@@ -594,7 +573,7 @@ class RocmGroupBySumNode : public ac::ExecNode {
       void* ws = nullptr;
       if (ws_bytes > 0) {
         ARROW_RETURN_NOT_OK(t_scratch.Get(kWs, ws_bytes + 256, &ws));
-        ws = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
+        ws = Align256(ws);
       }
       ARROW_RETURN_NOT_OK(FromArx(arx_groupby_sum_i64_consume(state_, capacity_, &dk, &dv, ws, ws_bytes, st)));
       if (needs_minmax_) {
@@ -757,27 +736,20 @@ class RocmGroupBySumNode : public ac::ExecNode {
     HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
     std::vector<std::shared_ptr<Buffer>> kbufs{std::move(kbits), std::move(keys)};
     columns[0] = arrow::Datum(ArrayData::Make(arrow::int32(), g, std::move(kbufs), key_nulls));
-    cp::ExecBatch out(std::move(columns), g);
     // GroupByNode hands its result on in batches of ExecPlan::kMaxBatchSize rows (groupby_aggregate_node.cc OutputResult);
     // so does this node — unless the plan fed it larger batches (table_source_rocm), in which case every node in it
     // takes batches of that size and the result goes on at the same granularity (10M groups: 1 batch instead of 306)
     const int64_t batch_size = std::max<int64_t>(ac::ExecPlan::kMaxBatchSize, largest_input_batch_);
-    const int nb = static_cast<int>(std::max<int64_t>(1, (g + batch_size - 1) / batch_size));
     timing.Mark("results to host");
-    for (int i = 0; i < nb; ++i) {
-      ARROW_RETURN_NOT_OK(output_->InputReceived(this, out.Slice(i * batch_size, batch_size)));
-    }
+    ARROW_RETURN_NOT_OK(EmitResult(this, output_, std::move(columns), g, device_out, st, batch_size));
     timing.Mark("batches handed on");
-    return output_->InputFinished(this, nb);
+    return Status::OK();
   }
-
 
   const int key_idx_, val_idx_;
   const std::vector<AggSpec> aggs_;
   bool needs_minmax_ = false;
   void* minmax_ = nullptr;   // mins | maxes per slot (arx_groupby_minmax_bytes), only with hash_min / hash_max
-  std::mutex mu_;
-  ac::AtomicCounter counter_;
   void* state_ = nullptr;
   int64_t capacity_ = 0;
   std::shared_ptr<Buffer> keys_buf_, vals_buf_;   // the staging columns (pooled device buffers)

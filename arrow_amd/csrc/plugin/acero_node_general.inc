@@ -10,15 +10,11 @@
 //   aggregates  hash_sum / hash_mean / hash_min / hash_max over int64 columns (each its own column), hash_count (the
 //               three CountOptions modes) over any fixed-width column, hash_count_all, hash_any / hash_all over boolean
 //               columns (three dense counts per group, as plugin/hash_aggregate_bool.inc keeps them)
-// The batches are kept until the input ends (like OrderByNode, acero/order_by_node.cc:100-122), their columns
+// The batches are kept until the input ends (AccumulatingNode, plugin/acero_common.inc), their columns
 // concatenated into device staging columns — device-resident batches by ONE segment-copy launch per column, host batches
 // by arrow::Concatenate + one upload — then ONE Grouper consume and one dense consume per aggregate run over all rows.
 // Output = key columns ++ aggregate columns, groups in order of first appearance.
-// Concatenate of one column's chunks into one device-resident array (RocmOrderByNode::ConcatOnDevice, order_by_node.inc)
-arrow::Result<std::shared_ptr<ArrayData>> ConcatChunksOnDevice(const std::shared_ptr<arrow::DataType>& type,
-                                                               const std::vector<std::shared_ptr<ArrayData>>& chunks, hipStream_t st);
-
-class RocmGroupByGeneralNode : public ac::ExecNode {
+class RocmGroupByGeneralNode : public AccumulatingNode {
  public:
   enum Kind { kSum, kMean, kMin, kMax, kCount, kCountAll, kAny, kAll, kCountDistinct, kFirst, kLast, kOne, kProduct, kFirstLast, kList, kDistinct,
               kVariance, kStddev, kSkew, kKurtosis };
@@ -36,7 +32,7 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
 
   RocmGroupByGeneralNode(ac::ExecPlan* plan, std::vector<ac::ExecNode*> inputs, std::shared_ptr<arrow::Schema> out_schema,
                          std::vector<int> key_cols, std::vector<int> key_widths, std::vector<Agg> aggs)
-      : ac::ExecNode(plan, std::move(inputs), {"input"}, std::move(out_schema)), key_cols_(std::move(key_cols)),
+      : AccumulatingNode(plan, std::move(inputs), {"input"}, std::move(out_schema)), key_cols_(std::move(key_cols)),
         key_widths_(std::move(key_widths)), aggs_(std::move(aggs)) {}
 
   // nullptr result = "not this node's case" is expressed as NotImplemented with the reason
@@ -245,36 +241,20 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
 
   const char* kind_name() const override { return "RocmGroupByGeneralNode"; }
 
-  Status InputReceived(ac::ExecNode*, cp::ExecBatch batch) override {
-    {
-      std::lock_guard<std::mutex> lock(mu_);
-      if (batch.length > 0) {
-        rows_ += batch.length;
-        batches_.push_back(std::move(batch));
-      }
-    }
-    if (counter_.Increment()) return Finish();
-    return Status::OK();
-  }
-  Status InputFinished(ac::ExecNode*, int total_batches) override {
-    if (counter_.SetTotal(total_batches)) return Finish();
-    return Status::OK();
-  }
-  Status StartProducing() override { return Status::OK(); }
-  void PauseProducing(ac::ExecNode*, int32_t) override {}
-  void ResumeProducing(ac::ExecNode*, int32_t) override {}
-
- protected:
-  Status StopProducingImpl() override { return Status::OK(); }
-
  private:
+  Status Accept(int, cp::ExecBatch batch) override {
+    if (batch.length > 0) {
+      rows_ += batch.length;
+      batches_[0].push_back(std::move(batch));
+    }
+    return Status::OK();
+  }
+
   struct Staged {
     std::shared_ptr<Buffer> data, valid;   // valid == nullptr: no nulls
     int width = 0;                         // 0: boolean (`data` = its value bits, staged only when an aggregate reads them)
     bool want_bool_values = false;
   };
-
-  static int64_t BitmapBytes(int64_t rows) { return ((rows + 63) / 64) * 8 + 8; }
 
   // column `col` of every batch, concatenated into device buffers
   Status StageColumn(int col, hipStream_t st, Staged* out) {
@@ -282,7 +262,7 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
     out->width = FixedByteWidth(type);
     const int64_t n = rows_;
     bool any_device = false, any_host = false, any_nulls = false;
-    for (const auto& b : batches_) {
+    for (const auto& b : batches_[0]) {
       if (!b[col].is_array()) return Status::NotImplemented("aggregate_rocm: scalar columns");
       const ArrayData& a = *b[col].array();
       const bool dev = DataOnRocm(a);
@@ -307,7 +287,7 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
     if (any_host) {
       // host batches: the reference's Concatenate, then one upload per buffer
       arrow::ArrayVector chunks;
-      for (const auto& b : batches_) chunks.push_back(b[col].make_array());
+      for (const auto& b : batches_[0]) chunks.push_back(b[col].make_array());
       ARROW_ASSIGN_OR_RAISE(auto whole, arrow::Concatenate(chunks, plan_->query_context()->memory_pool()));
       const ArrayData& w = *whole->data();
       if (out->width > 0) {
@@ -335,7 +315,7 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
     std::vector<ArxBitSeg> bit_segs, value_bit_segs;
     uint64_t longest = 0;
     int64_t longest_rows = 0, at = 0;
-    for (const auto& b : batches_) {
+    for (const auto& b : batches_[0]) {
       const ArrayData& a = *b[col].array();
       if (out->width > 0) {
         const auto* src = reinterpret_cast<const uint8_t*>(a.buffers[1]->address()) + a.offset * out->width;
@@ -471,8 +451,8 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
     return arrow::Datum(ArrayData::Make(arrow::boolean(), g, {std::move(bitmap), std::move(values)}, null_count));
   }
 
-  Status Finish() {
-    std::lock_guard<std::mutex> lock(mu_);
+  Status Finish() override {
+    std::vector<cp::ExecBatch>& batches = batches_[0];
     hipStream_t st;
     ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
     const int64_t n = rows_;
@@ -484,11 +464,7 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
       // row order = batch.index order (the order of the source, whichever thread delivered a batch first): the ordered
       // aggregates (hash_first / hash_last / hash_one) and the row-order float sums mean THAT order; group ids then also
       // come out in order of first appearance in the table, as the reference's single-threaded Grouper numbers them
-      bool sequenced = true;
-      for (const auto& b : batches_) sequenced = sequenced && b.index >= 0;
-      if (sequenced) {
-        std::stable_sort(batches_.begin(), batches_.end(), [](const cp::ExecBatch& a, const cp::ExecBatch& b) { return a.index < b.index; });
-      } else {
+      if (!OrderBatchesByIndex(&batches)) {
         for (const Agg& a : aggs_) {
           if (a.kind == kFirst || a.kind == kLast || a.kind == kFirstLast || a.kind == kList) {
             return Status::NotImplemented("aggregate_rocm: hash_first / hash_last / hash_list over batches without an order (ExecBatch::index unset)");
@@ -507,40 +483,35 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
       for (int j = 0; j < nk; ++j) {
         if (key_widths_[j] != 0 || var_keys.count(j) != 0) continue;
         std::vector<std::shared_ptr<ArrayData>> chunks;
-        for (const auto& b : batches_) {
+        for (const auto& b : batches) {
           if (!b[key_cols_[j]].is_array()) return Status::NotImplemented("aggregate_rocm: scalar key columns");
           chunks.push_back(b[key_cols_[j]].array());
         }
-        ARROW_ASSIGN_OR_RAISE(var_keys[j], ConcatChunksOnDevice(inputs_[0]->output_schema()->field(key_cols_[j])->type(), chunks, st));
+        ARROW_ASSIGN_OR_RAISE(var_keys[j], ConcatOnDevice(inputs_[0]->output_schema()->field(key_cols_[j])->type(), chunks, st));
       }
       for (const Agg& a : aggs_) {
         if (a.col >= 0) staged.emplace(a.col, Staged{});
         if (a.kind == kAny || a.kind == kAll) staged[a.col].want_bool_values = true;
       }
       for (auto& kv : staged) ARROW_RETURN_NOT_OK(StageColumn(kv.first, st, &kv.second));
-      std::vector<cp::ExecBatch>().swap(batches_);   // the input may go
-      // ---- Grouper: key rows -> dense ids in order of first appearance.  One device table holds rows of up to 16 bytes /
-      // 8 columns (32-byte slots, csrc/grouper.hip); wider rows go through a CHAIN of tables instead of wider slots: level
-      // 0 maps the first columns to ids, level s maps (id of level s-1, the next columns) — a 4-byte id stands for
-      // everything to its left, and a row's tuple (prefix id, columns) appears first exactly where the row does, so the
-      // last level's ids are the ids of the whole row in order of first appearance (the reference encodes the whole row,
-      // row/grouper.cc:559-611; any number of fixed-width columns).
+      std::vector<cp::ExecBatch>().swap(batches);   // the input may go
+      // ---- Grouper: key rows -> dense ids in order of first appearance, through the chain of tables that
+      // PlanGrouperLevels lays out (plugin/grouper_chain.inc); ONE table, initialised again for every level, since the
+      // uniques of a level are read before the next level runs.
       const int64_t max_groups = n + 16;
-      ARROW_ASSIGN_OR_RAISE(auto table_buf, AllocDevice(static_cast<int64_t>(arx_grouper_state_bytes(max_groups)) + 256));
-      void* table = reinterpret_cast<void*>((table_buf->mutable_address() + 255) & ~uintptr_t(255));
+      ARROW_ASSIGN_OR_RAISE(auto table_mem, AllocAligned(static_cast<int64_t>(arx_grouper_state_bytes(max_groups))));
+      void* const table = table_mem.ptr;
       const size_t ws_bytes = arx_grouper_consume_workspace_bytes(n);
-      ARROW_ASSIGN_OR_RAISE(auto ws_buf, AllocDevice(static_cast<int64_t>(ws_bytes) + 256));
-      void* ws = reinterpret_cast<void*>((ws_buf->mutable_address() + 255) & ~uintptr_t(255));
-      // virtual key columns: a fixed-width key is one; a utf8 / binary key is its length (uint32, 0xFFFFFFFF = null) and
-      // then 12 bytes of the string per chunk as a uint64 and a uint32 column (arx_binary_key_lengths / _chunk) — equal
-      // strings agree in all of them, different strings differ in the length or in some chunk
-      // Round 4: ONE pass whatever the lengths — the string's stand-in is its length and a 64-bit hash of its bytes (kind
-      // 4; arx_binary_key_hash), the groups are verified against their first rows' bytes (arx_binary_key_verify), and only a
-      // batch in which different strings of one length share a hash takes the exact chunk columns (second attempt).
-      struct VCol { int key; int width; int kind; int64_t chunk; };   // kind 0: the key column itself, 1: length, 2 / 3: chunk lo / hi, 4: hash
-      std::vector<VCol> vcols;
+      ARROW_ASSIGN_OR_RAISE(auto ws_mem, AllocAligned(static_cast<int64_t>(ws_bytes)));
+      void* const ws = ws_mem.ptr;
+      // The Grouper's columns: a fixed-width key is one; a utf8 / binary key is its length and, first attempt, a 64-bit hash of
+      // its bytes (arx_binary_key_hash) — ONE pass whatever the lengths; the groups are verified against their first rows'
+      // bytes (arx_binary_key_verify), and only a batch in which different strings of one length share a hash takes the exact
+      // chunk columns (BinaryKeyColumns; second attempt).
+      std::vector<KeyColumn> cols;
+      std::vector<int> key_of;   // per Grouper column: the key it is, -1 for a string's stand-ins
       std::map<int, ArxBinarySpan> var_spans;
-      std::map<int, std::shared_ptr<Buffer>> var_lengths;
+      std::map<int, KeyColumn> var_lengths;
       std::map<int, int64_t> var_max_len;
       for (int j = 0; j < nk; ++j) {
         if (key_widths_[j] != 0) continue;
@@ -553,14 +524,11 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
         bs.length = n;
         bs.null_count = bs.validity != nullptr ? arrow::kUnknownNullCount : 0;
         var_spans[j] = bs;
-        ARROW_ASSIGN_OR_RAISE(var_lengths[j], AllocDevice(n * 4 + 64));
-        int64_t max_len = 0;
-        ARROW_RETURN_NOT_OK(FromArx(arx_binary_key_lengths(&bs, Ptr<uint32_t>(var_lengths[j]), &max_len, ws, st)));
-        var_max_len[j] = max_len;
+        ARROW_ASSIGN_OR_RAISE(var_lengths[j], BinaryKeyLengths(bs, n, st, &var_max_len[j]));
       }
       std::vector<std::vector<int>> levels;
       struct LevelUniques {
-        std::vector<std::shared_ptr<Buffer>> vals, bits;   // one per virtual column of the level (nullptr: not a key column itself)
+        std::vector<std::shared_ptr<Buffer>> vals, bits;   // one per Grouper column of the level (nullptr: not a key column itself)
         std::vector<int64_t> nulls;
         std::shared_ptr<Buffer> prev_ids;                  // [groups of this level] id at the level before (levels >= 1)
         int64_t groups = 0;
@@ -570,45 +538,28 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
       const int hash_bits = static_cast<int>(g_string_key_hash_bits.load());
       for (int attempt = (var_keys.empty() || hash_bits <= 0) ? 1 : 0; attempt < 2; ++attempt) {
       const bool hashed = attempt == 0;
-      vcols.clear();
+      cols.clear();
+      key_of.clear();
       for (int j = 0; j < nk; ++j) {
         if (key_widths_[j] != 0) {
-          vcols.push_back({j, key_widths_[j], 0, 0});
-          continue;
+          cols.push_back(KeyColumn{SpanOf(staged[key_cols_[j]], n), key_widths_[j], false, {}});
+        } else if (hashed) {
+          cols.push_back(var_lengths[j]);
+          ARROW_ASSIGN_OR_RAISE(auto hash, AllocDevice(n * 8 + 64));
+          ARROW_RETURN_NOT_OK(FromArx(arx_binary_key_hash(&var_spans[j], hash_bits, Ptr<uint64_t>(hash), st)));
+          cols.push_back(KeyColumn{ArxSpan{nullptr, Ptr<void>(hash), 0, n, 0}, 8, false, {hash}});
+        } else {
+          ARROW_RETURN_NOT_OK(BinaryKeyColumns(var_spans[j], n, var_lengths[j], var_max_len[j], st, &cols));
         }
-        vcols.push_back({j, 4, 1, 0});
-        if (hashed) {
-          vcols.push_back({j, 8, 4, 0});
-          continue;
-        }
-        for (int64_t c = 0; c * 12 < var_max_len[j]; ++c) {
-          vcols.push_back({j, 8, 2, c});
-          vcols.push_back({j, 4, 3, c});
-        }
+        key_of.resize(cols.size(), key_widths_[j] != 0 ? j : -1);
       }
-      levels.assign(1, {});   // positions into vcols
-      {
-        int used = 0;
-        for (int v = 0; v < static_cast<int>(vcols.size()); ++v) {
-          const bool later = levels.size() > 1;
-          // (a chunk's two halves stay in one table: its lo half opens a new level when both do not fit)
-          const int need = vcols[v].kind == 2 ? 12 : vcols[v].width;
-          const int cols = vcols[v].kind == 2 ? 2 : 1;
-          if (!levels.back().empty() && (used + need > 16 || static_cast<int>(levels.back().size()) + (later ? 1 : 0) + cols > 8)) {
-            levels.emplace_back();
-            used = 4;
-          }
-          levels.back().push_back(v);
-          used += vcols[v].width;
-        }
-      }
+      levels = PlanGrouperLevels(cols);
       uniq.assign(levels.size(), LevelUniques{});
       ids_buf = nullptr;
       for (size_t s = 0; s < levels.size(); ++s) {
         ARROW_RETURN_NOT_OK(FromArx(arx_grouper_init(table, max_groups, st)));
         std::vector<ArxSpan> key_spans;
         std::vector<int> widths;
-        std::vector<std::shared_ptr<Buffer>> chunk_bufs;   // this level's string chunks (freed when the level is done)
         if (s > 0) {
           ArxSpan prev{};
           prev.data = Ptr<void>(ids_buf);
@@ -617,30 +568,8 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
           widths.push_back(4);
         }
         for (int v : levels[s]) {
-          const VCol& vc = vcols[v];
-          ArxSpan sp{};
-          sp.length = n;
-          if (vc.kind == 0) {
-            sp = SpanOf(staged[key_cols_[vc.key]], n);
-          } else if (vc.kind == 1) {
-            sp.data = Ptr<void>(var_lengths[vc.key]);
-          } else if (vc.kind == 4) {
-            ARROW_ASSIGN_OR_RAISE(auto hash, AllocDevice(n * 8 + 64));
-            ARROW_RETURN_NOT_OK(FromArx(arx_binary_key_hash(&var_spans[vc.key], hash_bits, Ptr<uint64_t>(hash), st)));
-            sp.data = Ptr<void>(hash);
-            chunk_bufs.push_back(std::move(hash));
-          } else if (vc.kind == 2) {
-            ARROW_ASSIGN_OR_RAISE(auto lo, AllocDevice(n * 8 + 64));
-            ARROW_ASSIGN_OR_RAISE(auto hi, AllocDevice(n * 4 + 64));
-            ARROW_RETURN_NOT_OK(FromArx(arx_binary_key_chunk(&var_spans[vc.key], vc.chunk, Ptr<uint64_t>(lo), Ptr<uint32_t>(hi), st)));
-            sp.data = Ptr<void>(lo);
-            chunk_bufs.push_back(std::move(lo));
-            chunk_bufs.push_back(std::move(hi));
-          } else {
-            sp.data = Ptr<void>(chunk_bufs.back());   // the hi half written with the lo half just before
-          }
-          key_spans.push_back(sp);
-          widths.push_back(vc.width);
+          key_spans.push_back(cols[v].span);
+          widths.push_back(cols[v].width);
         }
         const int lk = static_cast<int>(widths.size());
         ARROW_ASSIGN_OR_RAISE(auto next_ids, AllocDevice(n * 4 + 64));
@@ -652,7 +581,7 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
         for (int c = 0; c < lk; ++c) {
           const bool prev_col = s > 0 && c == 0;
           const int v = prev_col ? -1 : levels[s][c - (s > 0 ? 1 : 0)];
-          if (!prev_col && vcols[v].kind != 0) {   // a string's length / chunks: its uniques come from the first rows below
+          if (!prev_col && key_of[v] < 0) {   // a string's stand-in: its uniques come from the first rows below
             u.vals.push_back(nullptr);
             u.bits.push_back(nullptr);
             u.nulls.push_back(0);
@@ -671,7 +600,7 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
             u.nulls.push_back(nulls);
           }
         }
-        HIP_RETURN_NOT_OK(hipStreamSynchronize(st));   // chunk_bufs go back to the pool here
+        HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
       }
       if (!hashed) break;
       // the hashed groups are the exact groups unless some row's bytes differ from its group's first row's
@@ -689,6 +618,7 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
         g_string_key_hash_collisions.fetch_add(1, std::memory_order_relaxed);
       }
       }   // attempts
+      cols.clear();   // (the strings' stand-ins go back to the pool)
       g = uniq.back().groups;
       const uint32_t* ids = Ptr<uint32_t>(ids_buf);
       CountGpu(kFnHashSum);
@@ -703,7 +633,7 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
         map.length = g;
         for (size_t c = 0; c < levels[s].size(); ++c) {
           if (u.vals[c] == nullptr) continue;
-          const int j = vcols[levels[s][c]].key;
+          const int j = key_of[levels[s][c]];
           const int w = key_widths_[j];
           const auto& type = in_schema.field(key_cols_[j])->type();
           if (to_level == nullptr) {
@@ -784,12 +714,12 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
           // pair belongs to and whether its value is null (GroupedCountDistinctImpl::Finalize :1441-1468)
           const Staged& col = staged[a.col];
           const int64_t max_pairs = n + 16;
-          ARROW_ASSIGN_OR_RAISE(auto pair_table_buf, AllocDevice(static_cast<int64_t>(arx_grouper_state_bytes(max_pairs)) + 256));
-          void* pair_table = reinterpret_cast<void*>((pair_table_buf->mutable_address() + 255) & ~uintptr_t(255));
+          ARROW_ASSIGN_OR_RAISE(auto pair_table_buf, AllocAligned(static_cast<int64_t>(arx_grouper_state_bytes(max_pairs))));
+          void* pair_table = pair_table_buf.ptr;
           ARROW_RETURN_NOT_OK(FromArx(arx_grouper_init(pair_table, max_pairs, st)));
           const size_t pws_bytes = arx_grouper_consume_workspace_bytes(n);
-          ARROW_ASSIGN_OR_RAISE(auto pws_buf, AllocDevice(static_cast<int64_t>(pws_bytes) + 256));
-          void* pws = reinterpret_cast<void*>((pws_buf->mutable_address() + 255) & ~uintptr_t(255));
+          ARROW_ASSIGN_OR_RAISE(auto pws_buf, AllocAligned(static_cast<int64_t>(pws_bytes)));
+          void* pws = pws_buf.ptr;
           ArxSpan pair_cols[2] = {SpanOf(col, n), ArxSpan{nullptr, ids, 0, n, 0}};
           const int32_t pair_widths[2] = {col.width, 4};
           ARROW_ASSIGN_OR_RAISE(auto pair_ids, AllocDevice(n * 4 + 64));
@@ -817,11 +747,11 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
             if (pairs > 0) {
               ARROW_RETURN_NOT_OK(FromArx(arx_hash_count_consume(nullptr, 0, 0, ARX_COUNT_ALL, Ptr<uint32_t>(pair_groups), pairs, Ptr<int64_t>(counts), st)));
               const size_t sws_bytes = arx_sort_indices_workspace_bytes(pairs);
-              ARROW_ASSIGN_OR_RAISE(auto sws, AllocDevice(static_cast<int64_t>(sws_bytes) + 256));
+              ARROW_ASSIGN_OR_RAISE(auto sws, AllocAligned(static_cast<int64_t>(sws_bytes)));
               ARROW_ASSIGN_OR_RAISE(auto perm, AllocDevice(pairs * 8 + 64));
               const ArxSpan gkeys{nullptr, Ptr<void>(pair_groups), 0, pairs, 0};
               ARROW_RETURN_NOT_OK(FromArx(arx_sort_indices(&gkeys, ARX_KEY_UINT32, ARX_SORT_ASCENDING, ARX_NULLS_AT_END,
-                                                           reinterpret_cast<void*>((sws->mutable_address() + 255) & ~uintptr_t(255)), sws_bytes,
+                                                           sws.ptr, sws_bytes,
                                                            Ptr<uint64_t>(perm), st)));
               ARROW_ASSIGN_OR_RAISE(auto dvals, AllocDevice(pairs * col.width + 64));
               std::shared_ptr<Buffer> dbits;
@@ -892,11 +822,11 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
           const Staged& col = staged[a.col];
           const int w = col.width;
           const size_t sws_bytes = arx_sort_indices_workspace_bytes(n);
-          ARROW_ASSIGN_OR_RAISE(auto sws, AllocDevice(static_cast<int64_t>(sws_bytes) + 256));
+          ARROW_ASSIGN_OR_RAISE(auto sws, AllocAligned(static_cast<int64_t>(sws_bytes)));
           ARROW_ASSIGN_OR_RAISE(auto perm, AllocDevice(n * 8 + 64));
           const ArxSpan gkeys{nullptr, ids, 0, n, 0};
           ARROW_RETURN_NOT_OK(FromArx(arx_sort_indices(&gkeys, ARX_KEY_UINT32, ARX_SORT_ASCENDING, ARX_NULLS_AT_END,
-                                                       reinterpret_cast<void*>((sws->mutable_address() + 255) & ~uintptr_t(255)), sws_bytes,
+                                                       sws.ptr, sws_bytes,
                                                        Ptr<uint64_t>(perm), st)));
           ARROW_ASSIGN_OR_RAISE(auto lvals, AllocDevice(n * w + 64));
           std::shared_ptr<Buffer> lbits;
@@ -1105,11 +1035,11 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
           ARROW_ASSIGN_OR_RAISE(sums, ZeroedDevice<int64_t>(g, st));
           ARROW_ASSIGN_OR_RAISE(counts, ZeroedDevice<int64_t>(g, st));
           const size_t ws_bytes = arx_hash_sum_consume_workspace_bytes(n, g);
-          std::shared_ptr<Buffer> ws_buf;
+          AlignedDevice ws_buf{nullptr, nullptr};
           void* ws = nullptr;
           if (ws_bytes > 0) {
-            ARROW_ASSIGN_OR_RAISE(ws_buf, AllocDevice(static_cast<int64_t>(ws_bytes) + 256));
-            ws = reinterpret_cast<void*>((ws_buf->mutable_address() + 255) & ~uintptr_t(255));
+            ARROW_ASSIGN_OR_RAISE(ws_buf, AllocAligned(static_cast<int64_t>(ws_bytes)));
+            ws = ws_buf.ptr;
           }
           ARROW_RETURN_NOT_OK(FromArx(arx_hash_sum_i64_consume_ws(&vals, 0, 0, ids, n, g, Ptr<int64_t>(sums), Ptr<int64_t>(counts),
                                                                   Ptr<uint32_t>(seen), ws, ws_bytes, st)));
@@ -1212,20 +1142,11 @@ class RocmGroupByGeneralNode : public ac::ExecNode {
       }
       columns = std::move(joined);
     }
-    cp::ExecBatch out(std::move(columns), g);
-    const int64_t batch_size = 32768;
-    const int nb = static_cast<int>(std::max<int64_t>(1, (g + batch_size - 1) / batch_size));
-    for (int i = 0; i < nb; ++i) {
-      ARROW_RETURN_NOT_OK(output_->InputReceived(this, out.Slice(i * batch_size, batch_size)));
-    }
-    return output_->InputFinished(this, nb);
+    return EmitResult(this, output_, std::move(columns), g, /*any_device=*/false, st);   // (every column was made on the host)
   }
 
   const std::vector<int> key_cols_, key_widths_;
   const std::vector<Agg> aggs_;
-  std::mutex mu_;
-  ac::AtomicCounter counter_;
-  std::vector<cp::ExecBatch> batches_;
   int64_t rows_ = 0;
 };
 

@@ -303,7 +303,7 @@ Status HashSumConsume(cp::KernelContext* ctx, const cp::ExecSpan& batch) {
   void* ws = nullptr;
   if (ws_bytes > 0 && n >= (int64_t(1) << 17)) {
     ARROW_RETURN_NOT_OK(t_scratch.Get(kWs, ws_bytes + 256, &ws));
-    ws = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
+    ws = Align256(ws);
   }
   ARROW_RETURN_NOT_OK(FromArx(arx_hash_sum_i64_consume_ws(&dv, is_scalar, scalar_value, d_gids, n, s->num_groups, s->sums,
                                                           s->counts, s->null_seen, ws, ws != nullptr ? ws_bytes : 0, st)));

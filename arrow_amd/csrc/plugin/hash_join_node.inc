@@ -4,8 +4,8 @@
 // ---------------------------------------------------------------- Acero: hash join node
 // HashJoinNode (acero/hash_join_node.cc) row-encodes keys and payload on the CPU, so over device-resident batches it
 // reads HBM through host pointers.  This node is the C++ form of the mirror's compute.hash_join_indices / hash_join
-// (DESIGN 4.17): input 0 is the probe (left) side, input 1 the build (right) side; both are accumulated whole (a
-// pipeline breaker on both inputs, nothing streams), concatenated per column in HBM, and joined by
+// (DESIGN 4.17): input 0 is the probe (left) side, input 1 the build (right) side; both are accumulated whole (an
+// AccumulatingNode over two inputs, plugin/acero_common.inc: nothing streams), concatenated per column in HBM, and joined by
 //   key columns -> Grouper columns (booleans as bytes, utf8 / binary as length + 12-byte chunks), the chain of Grouper
 //   tables (consume the build rows, look the probe rows up), arx_hash_join_key_validity, group offsets, the stable sort
 //   of the build ids, probe count (the one read-back), expand, build mask and right-only tail;
@@ -16,12 +16,12 @@
 // in HBM when any input batch was device-resident; host-only inputs are uploaded and the result copied back, as
 // order_by_rocm does.  The schema, the validation and the filter's binding are the reference's own HashJoinSchema.
 // Row order: the contract of include/arrow_amd.h.  Registered under a NEW name.
-class RocmHashJoinNode : public ac::ExecNode {
+class RocmHashJoinNode : public AccumulatingNode {
  public:
   RocmHashJoinNode(ac::ExecPlan* plan, std::vector<ac::ExecNode*> inputs, std::shared_ptr<arrow::Schema> schema,
                    ac::JoinType join_type, std::vector<ac::JoinKeyCmp> key_cmp, std::unique_ptr<ac::HashJoinSchema> maps,
                    cp::Expression filter)
-      : ac::ExecNode(plan, std::move(inputs), {"left", "right"}, std::move(schema)),
+      : AccumulatingNode(plan, std::move(inputs), {"left", "right"}, std::move(schema)),
         join_type_(join_type), key_cmp_(std::move(key_cmp)), maps_(std::move(maps)), filter_(std::move(filter)) {}
 
   static bool IsKeyType(const arrow::DataType& t) {
@@ -90,69 +90,10 @@ class RocmHashJoinNode : public ac::ExecNode {
 
   const char* kind_name() const override { return "RocmHashJoinNode"; }
 
-  Status InputReceived(ac::ExecNode* input, cp::ExecBatch batch) override {
-    const int side = input == inputs_[0] ? 0 : 1;
-    {
-      std::lock_guard<std::mutex> lock(mu_);
-      batches_[side].push_back(std::move(batch));
-    }
-    return counter_[side].Increment() ? SideDone() : Status::OK();
-  }
-  Status InputFinished(ac::ExecNode* input, int total_batches) override {
-    const int side = input == inputs_[0] ? 0 : 1;
-    return counter_[side].SetTotal(total_batches) ? SideDone() : Status::OK();
-  }
-  Status StartProducing() override { return Status::OK(); }
-  void PauseProducing(ac::ExecNode*, int32_t) override {}
-  void ResumeProducing(ac::ExecNode*, int32_t) override {}
-
- protected:
-  Status StopProducingImpl() override { return Status::OK(); }
-
  private:
   using BufferPtr = std::shared_ptr<Buffer>;
-  template <typename T>
-  static T* P(const BufferPtr& b) { return b == nullptr ? nullptr : reinterpret_cast<T*>(b->mutable_address()); }
-  static int64_t BitmapBytes(int64_t n) { return ((n + 63) / 64) * 8 + 8; }
   static bool EmitsLeft(ac::JoinType t) { return t != ac::JoinType::RIGHT_SEMI && t != ac::JoinType::RIGHT_ANTI; }
   static bool EmitsRight(ac::JoinType t) { return t != ac::JoinType::LEFT_SEMI && t != ac::JoinType::LEFT_ANTI; }
-
-  Status SideDone() {
-    if (sides_done_.fetch_add(1) + 1 < 2) return Status::OK();
-    return Finish();
-  }
-
-  // a Grouper key column: the span the table reads and the buffers that keep it alive
-  struct KeyColumn {
-    ArxSpan span;
-    int32_t width;
-    std::vector<BufferPtr> keep;
-  };
-
-  static arrow::Result<BufferPtr> ZeroedDevice(int64_t bytes, hipStream_t st) {
-    ARROW_ASSIGN_OR_RAISE(auto buf, AllocDevice(std::max<int64_t>(bytes, 8)));
-    HIP_RETURN_NOT_OK(hipMemsetAsync(P<void>(buf), 0, static_cast<size_t>(std::max<int64_t>(bytes, 8)), st));
-    return buf;
-  }
-
-  // one column of one side, all batches, as one device array (an input without batches: an empty array)
-  arrow::Result<std::shared_ptr<ArrayData>> WholeColumn(int side, int column, hipStream_t st, bool* any_device) {
-    const auto& type = inputs_[side]->output_schema()->field(column)->type();
-    std::vector<std::shared_ptr<ArrayData>> chunks;
-    for (const auto& b : batches_[side]) {
-      if (!b[column].is_array()) return Status::NotImplemented("arrow_amd: hashjoin_rocm: scalar columns");
-      if (b.length == 0) continue;
-      chunks.push_back(b[column].array());
-      *any_device = *any_device || DataOnRocm(*b[column].array());
-    }
-    if (chunks.empty()) {
-      ARROW_ASSIGN_OR_RAISE(auto data, ZeroedDevice(8, st));
-      std::vector<BufferPtr> bufs{nullptr, data};
-      if (IsInt32Binary(*type)) bufs.push_back(data);
-      return ArrayData::Make(type, 0, std::move(bufs), 0);
-    }
-    return ConcatChunksOnDevice(type, chunks, st);
-  }
 
   // Key columns of both sides as the Grouper's fixed-width columns, the same widths on both sides (the mirror's
   // _join_key_columns): strings as (length, 12-byte chunks), the shorter side's missing chunks zero.
@@ -163,27 +104,13 @@ class RocmHashJoinNode : public ac::ExecNode {
       if (IsInt32Binary(t)) {
         int64_t max_len[2] = {0, 0};
         ArxBinarySpan bs[2];
+        KeyColumn lengths[2];
         for (int s = 0; s < 2; ++s) {
           ARROW_RETURN_NOT_OK(DeviceBinarySpan(ArraySpan(*keys[s][k]), &bs[s]));
-          ARROW_ASSIGN_OR_RAISE(auto lens, AllocDevice(std::max<int64_t>(n[s], 1) * 4));
-          if (n[s] > 0) {
-            void* ws = nullptr;
-            ARROW_RETURN_NOT_OK(t_scratch.Get(kCounter, 256, &ws));
-            ARROW_RETURN_NOT_OK(FromArx(arx_binary_key_lengths(&bs[s], P<uint32_t>(lens), &max_len[s], ws, st)));
-          }
-          out[s].push_back(KeyColumn{ArxSpan{nullptr, P<void>(lens), 0, n[s], 0}, 4, {lens}});
+          ARROW_ASSIGN_OR_RAISE(lengths[s], BinaryKeyLengths(bs[s], n[s], st, &max_len[s]));
         }
-        const int64_t chunks = (std::max(max_len[0], max_len[1]) + 11) / 12;
-        for (int64_t c = 0; c < chunks; ++c) {
-          for (int s = 0; s < 2; ++s) {
-            ARROW_ASSIGN_OR_RAISE(auto lo, ZeroedDevice(std::max<int64_t>(n[s], 1) * 8, st));
-            ARROW_ASSIGN_OR_RAISE(auto hi, ZeroedDevice(std::max<int64_t>(n[s], 1) * 4, st));
-            if (n[s] > 0 && c * 12 < max_len[s]) {
-              ARROW_RETURN_NOT_OK(FromArx(arx_binary_key_chunk(&bs[s], c, P<uint64_t>(lo), P<uint32_t>(hi), st)));
-            }
-            out[s].push_back(KeyColumn{ArxSpan{nullptr, P<void>(lo), 0, n[s], 0}, 8, {lo}});
-            out[s].push_back(KeyColumn{ArxSpan{nullptr, P<void>(hi), 0, n[s], 0}, 4, {hi}});
-          }
+        for (int s = 0; s < 2; ++s) {
+          ARROW_RETURN_NOT_OK(BinaryKeyColumns(bs[s], n[s], std::move(lengths[s]), std::max(max_len[0], max_len[1]), st, &out[s]));
         }
       } else {
         for (int s = 0; s < 2; ++s) {
@@ -191,87 +118,16 @@ class RocmHashJoinNode : public ac::ExecNode {
           ARROW_RETURN_NOT_OK(DeviceSpan(ArraySpan(*keys[s][k]), &sp));
           if (t.id() == Type::BOOL) {
             ARROW_ASSIGN_OR_RAISE(auto bytes, AllocDevice(std::max<int64_t>(sp.offset + n[s], 1)));
-            ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_bool_key(&sp, P<uint8_t>(bytes) + sp.offset, st)));
-            sp.data = P<void>(bytes);
-            out[s].push_back(KeyColumn{sp, 1, {bytes}});
+            ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_bool_key(&sp, DevPtr<uint8_t>(bytes) + sp.offset, st)));
+            sp.data = DevPtr<void>(bytes);
+            out[s].push_back(KeyColumn{sp, 1, false, {bytes}});
           } else {
-            out[s].push_back(KeyColumn{sp, FixedByteWidth(t), {}});
+            out[s].push_back(KeyColumn{sp, FixedByteWidth(t), false, {}});
           }
         }
       }
     }
     if (out[0].size() > 32) return Status::NotImplemented("arrow_amd: hashjoin_rocm: key rows of more than 32 Grouper columns on device-resident data");
-    return Status::OK();
-  }
-
-  // The chain of Grouper tables (compute.Grouper): level 0 takes columns while they fit 16 bytes / 8 columns, every later
-  // level the previous level's id (4 bytes) and the columns that fit beside it.  consume: ids, never null; lookup: ids
-  // and their validity (an unseen prefix is a null id, which no consumed row has).
-  struct GrouperChain {
-    std::vector<std::vector<int>> level_columns;
-    std::vector<BufferPtr> states;
-    int64_t max_groups = 1;
-    int64_t num_groups = 0;
-  };
-  static void* Align256(void* p) { return reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(p) + 255) & ~uintptr_t(255)); }
-
-  Status MakeChain(const std::vector<KeyColumn>& cols, int64_t max_groups, hipStream_t st, GrouperChain* chain) {
-    chain->max_groups = std::max<int64_t>(max_groups, 1);
-    std::vector<int> cur;
-    int used = 0;
-    for (size_t j = 0; j < cols.size(); ++j) {
-      const bool later = !chain->level_columns.empty();
-      if (!cur.empty() && (used + cols[j].width > 16 || static_cast<int>(cur.size()) + (later ? 1 : 0) >= 8)) {
-        chain->level_columns.push_back(cur);
-        cur.clear();
-        used = 4;
-      }
-      cur.push_back(static_cast<int>(j));
-      used += cols[j].width;
-    }
-    chain->level_columns.push_back(cur);
-    for (size_t s = 0; s < chain->level_columns.size(); ++s) {
-      ARROW_ASSIGN_OR_RAISE(auto state, AllocDevice(static_cast<int64_t>(arx_grouper_state_bytes(chain->max_groups)) + 256));
-      ARROW_RETURN_NOT_OK(FromArx(arx_grouper_init(Align256(P<void>(state)), chain->max_groups, st)));
-      chain->states.push_back(std::move(state));
-    }
-    return Status::OK();
-  }
-
-  Status RunChain(GrouperChain* chain, const std::vector<KeyColumn>& cols, int64_t n, bool lookup, hipStream_t st,
-                  BufferPtr* out_ids, BufferPtr* out_valid) {
-    BufferPtr ids, valid;
-    const size_t ws_bytes = arx_grouper_consume_workspace_bytes(n);
-    ARROW_ASSIGN_OR_RAISE(auto ws_buf, AllocDevice(static_cast<int64_t>(ws_bytes) + 256));
-    for (size_t s = 0; s < chain->level_columns.size(); ++s) {
-      std::vector<ArxSpan> spans;
-      std::vector<int32_t> widths;
-      if (s > 0) {
-        spans.push_back(ArxSpan{P<void>(valid), P<void>(ids), 0, n, valid != nullptr ? arrow::kUnknownNullCount : 0});
-        widths.push_back(4);
-      }
-      for (int j : chain->level_columns[s]) {
-        spans.push_back(cols[j].span);
-        widths.push_back(cols[j].width);
-      }
-      ARROW_ASSIGN_OR_RAISE(auto next_ids, AllocDevice(std::max<int64_t>(n, 1) * 4));
-      void* state = Align256(P<void>(chain->states[s]));
-      if (lookup) {
-        ARROW_ASSIGN_OR_RAISE(auto next_valid, ZeroedDevice(BitmapBytes(n), st));
-        ARROW_RETURN_NOT_OK(FromArx(arx_grouper_lookup(state, chain->max_groups, spans.data(), widths.data(), static_cast<int>(spans.size()),
-                                                       Align256(P<void>(ws_buf)), ws_bytes, P<uint32_t>(next_ids), P<uint8_t>(next_valid), st)));
-        valid = std::move(next_valid);
-      } else {
-        ARROW_RETURN_NOT_OK(FromArx(arx_grouper_consume(state, chain->max_groups, spans.data(), widths.data(), static_cast<int>(spans.size()),
-                                                        Align256(P<void>(ws_buf)), ws_bytes, P<uint32_t>(next_ids), st)));
-      }
-      ids = std::move(next_ids);
-      if (!lookup && s + 1 == chain->level_columns.size()) {
-        ARROW_RETURN_NOT_OK(FromArx(arx_grouper_num_groups(state, &chain->num_groups, st)));
-      }
-    }
-    *out_ids = std::move(ids);
-    if (out_valid != nullptr) *out_valid = std::move(valid);
     return Status::OK();
   }
 
@@ -287,8 +143,7 @@ class RocmHashJoinNode : public ac::ExecNode {
     return rows.array();
   }
 
-  Status Finish() {
-    std::lock_guard<std::mutex> lock(mu_);
+  Status Finish() override {
     hipStream_t st;
     ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
     cp::ExecContext* ctx = plan_->query_context()->exec_context();
@@ -297,9 +152,7 @@ class RocmHashJoinNode : public ac::ExecNode {
     int64_t n[2] = {0, 0};
     bool any_device = false;
     for (int s = 0; s < 2; ++s) {
-      if (std::all_of(batches_[s].begin(), batches_[s].end(), [](const cp::ExecBatch& b) { return b.index >= 0; })) {
-        std::stable_sort(batches_[s].begin(), batches_[s].end(), [](const cp::ExecBatch& a, const cp::ExecBatch& b) { return a.index < b.index; });
-      }
+      OrderBatchesByIndex(&batches_[s]);
       for (const auto& b : batches_[s]) n[s] += b.length;
     }
     // every input column that the keys, the filter or the output read, concatenated once
@@ -307,7 +160,8 @@ class RocmHashJoinNode : public ac::ExecNode {
     auto column = [&](int side, int input_col) -> arrow::Result<std::shared_ptr<ArrayData>> {
       auto it = whole[side].find(input_col);
       if (it != whole[side].end()) return it->second;
-      ARROW_ASSIGN_OR_RAISE(auto col, WholeColumn(side, input_col, st, &any_device));
+      ARROW_ASSIGN_OR_RAISE(auto col, WholeColumn(batches_[side], inputs_[side]->output_schema()->field(input_col)->type(), input_col, st,
+                                                  &any_device, "arrow_amd: hashjoin_rocm"));
       whole[side][input_col] = col;
       return col;
     };
@@ -322,17 +176,16 @@ class RocmHashJoinNode : public ac::ExecNode {
     const int64_t nl = n[0], nb = n[1];
     std::vector<KeyColumn> key_cols[2];
     ARROW_RETURN_NOT_OK(KeyColumns(keys, n, st, key_cols));
-    GrouperChain chain;
-    ARROW_RETURN_NOT_OK(MakeChain(key_cols[1], nb, st, &chain));
+    ARROW_ASSIGN_OR_RAISE(GrouperChain chain, GrouperChain::Make(PlanGrouperLevels(key_cols[1]), nb, st));
     BufferPtr build_ids, probe_ids, probe_found;
-    ARROW_RETURN_NOT_OK(RunChain(&chain, key_cols[1], nb, /*lookup=*/false, st, &build_ids, nullptr));
-    ARROW_RETURN_NOT_OK(RunChain(&chain, key_cols[0], nl, /*lookup=*/true, st, &probe_ids, &probe_found));
+    ARROW_RETURN_NOT_OK(chain.Run(key_cols[1], nb, /*lookup=*/false, st, &build_ids, nullptr));
+    ARROW_RETURN_NOT_OK(chain.Run(key_cols[0], nl, /*lookup=*/true, st, &probe_ids, &probe_found));
     const int64_t num_groups = chain.num_groups;
     // JoinKeyCmp::EQ: a null key matches nothing; IS: null is the Grouper's key value of its own
     BufferPtr valid[2];
     for (int s = 0; s < 2; ++s) {
       std::vector<ArxSpan> spans;
-      if (s == 0) spans.push_back(ArxSpan{P<void>(probe_found), P<void>(probe_ids), 0, nl, arrow::kUnknownNullCount});
+      if (s == 0) spans.push_back(ArxSpan{DevPtr<void>(probe_found), DevPtr<void>(probe_ids), 0, nl, arrow::kUnknownNullCount});
       for (size_t k = 0; k < keys[s].size(); ++k) {
         if (key_cmp_[k] != ac::JoinKeyCmp::EQ || keys[s][k]->buffers[0] == nullptr) continue;
         spans.push_back(ArxSpan{reinterpret_cast<const void*>(keys[s][k]->buffers[0]->address()), nullptr, keys[s][k]->offset, n[s],
@@ -340,15 +193,15 @@ class RocmHashJoinNode : public ac::ExecNode {
       }
       if (spans.empty() || n[s] == 0) continue;
       ARROW_ASSIGN_OR_RAISE(valid[s], AllocDevice(BitmapBytes(n[s])));
-      ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_key_validity(spans.data(), static_cast<int>(spans.size()), n[s], P<void>(valid[s]), st)));
+      ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_key_validity(spans.data(), static_cast<int>(spans.size()), n[s], DevPtr<void>(valid[s]), st)));
     }
     const BufferPtr &probe_valid = valid[0], &build_valid = valid[1];
 
     const size_t ws_bytes = arx_hash_join_workspace_bytes(std::max<int64_t>({num_groups, nl, 1}));
     ARROW_ASSIGN_OR_RAISE(auto ws, AllocDevice(static_cast<int64_t>(ws_bytes) + 64));
     ARROW_ASSIGN_OR_RAISE(auto group_offsets, AllocDevice((num_groups + 1) * 8));
-    ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_group_offsets(P<uint32_t>(build_ids), P<void>(build_valid), nb, num_groups,
-                                                            P<int64_t>(group_offsets), P<void>(ws), ws_bytes, st)));
+    ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_group_offsets(DevPtr<uint32_t>(build_ids), DevPtr<void>(build_valid), nb, num_groups,
+                                                            DevPtr<int64_t>(group_offsets), DevPtr<void>(ws), ws_bytes, st)));
     ARROW_ASSIGN_OR_RAISE(auto offsets, AllocDevice((nl + 1) * 8));
     // rows the output (and, under a filter, the candidate pairs) may have before the join is refused with a
     // CapacityError: 2^33 rows are 146 GB of row pairs and bitmap, half of the MI355X's HBM before a column is gathered
@@ -363,31 +216,49 @@ class RocmHashJoinNode : public ac::ExecNode {
       if (sorted.array()->offset != 0) return Status::Invalid("arrow_amd: hashjoin_rocm: sorted build rows with an offset");
       return sorted.array()->buffers[1];
     };
-    auto append_tail = [&](const ArrayData& tail, int64_t total, int64_t n_out, const BufferPtr& out_left, const BufferPtr& out_right,
-                           const BufferPtr& right_valid, BufferPtr* left_valid) -> Status {
-      if (tail.length == 0) return Status::OK();
-      ARROW_ASSIGN_OR_RAISE(*left_valid, AllocDevice(BitmapBytes(n_out)));
-      return FromArx(arx_hash_join_append_build_rows(reinterpret_cast<const uint64_t*>(tail.buffers[1]->address()) + tail.offset, tail.length, total,
-                                                     P<int64_t>(out_left), P<void>(*left_valid), P<int64_t>(out_right), P<void>(right_valid), st));
-    };
     auto too_many = [&](int64_t n_out) {
       return Status::CapacityError("hash join: the output would have ", n_out, " rows, more than the ", limit, " that can be allocated");
     };
 
     arrow::Datum left_rows, right_rows;   // the row pairs: int64 with validity, or uint64 rows of one side (semi / anti)
     int64_t n_out = 0;
+    // the row pairs of the joins that emit probe rows: size the output, allocate the pair and validity buffers, `fill` them
+    // (expand, or compact under a filter), append the right-only tail, wrap as index Datums (compute.py _PreparedJoin.finish)
+    using Fill = std::function<Status(const BufferPtr& out_left, const BufferPtr& out_right, const BufferPtr& right_valid)>;
+    auto row_pairs = [&](int64_t total, const std::shared_ptr<ArrayData>& tail, const Fill& fill) -> Status {
+      n_out = total + (tail != nullptr ? tail->length : 0);
+      if (n_out > limit) return too_many(n_out);
+      BufferPtr out_left, out_right, right_valid, left_valid;
+      ARROW_ASSIGN_OR_RAISE(out_left, AllocDevice(std::max<int64_t>(n_out, 1) * 8));
+      if (pairs) {
+        ARROW_ASSIGN_OR_RAISE(out_right, AllocDevice(std::max<int64_t>(n_out, 1) * 8));
+      }
+      if (jt == 5 || jt == 7) {
+        ARROW_ASSIGN_OR_RAISE(right_valid, AllocDevice(BitmapBytes(n_out)));
+      }
+      ARROW_RETURN_NOT_OK(fill(out_left, out_right, right_valid));
+      if (tail != nullptr && tail->length > 0) {
+        ARROW_ASSIGN_OR_RAISE(left_valid, AllocDevice(BitmapBytes(n_out)));
+        ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_append_build_rows(reinterpret_cast<const uint64_t*>(tail->buffers[1]->address()) + tail->offset, tail->length,
+                                                                    total, DevPtr<int64_t>(out_left), DevPtr<void>(left_valid), DevPtr<int64_t>(out_right),
+                                                                    DevPtr<void>(right_valid), st)));
+      }
+      left_rows = IndexDatum(arrow::int64(), n_out, left_valid, out_left);
+      if (pairs) right_rows = IndexDatum(arrow::int64(), n_out, right_valid, out_right);
+      return Status::OK();
+    };
     if (!filtered) {
       BufferPtr matched;
       if (right_side) {
         ARROW_ASSIGN_OR_RAISE(matched, ZeroedDevice(std::max<int64_t>(num_groups, 1), st));
       }
       int64_t total = 0;
-      ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_probe_count(P<uint32_t>(probe_ids), P<void>(probe_valid), nl, P<int64_t>(group_offsets), num_groups, jt,
-                                                            P<uint8_t>(matched), limit, P<int64_t>(offsets), P<void>(ws), ws_bytes, &total, st)));
+      ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_probe_count(DevPtr<uint32_t>(probe_ids), DevPtr<void>(probe_valid), nl, DevPtr<int64_t>(group_offsets), num_groups, jt,
+                                                            DevPtr<uint8_t>(matched), limit, DevPtr<int64_t>(offsets), DevPtr<void>(ws), ws_bytes, &total, st)));
       auto build_rows = [&](int want_matched) -> arrow::Result<std::shared_ptr<ArrayData>> {
         ARROW_ASSIGN_OR_RAISE(auto mask, ZeroedDevice(BitmapBytes(nb), st));
-        ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_build_mask(P<uint32_t>(build_ids), P<void>(build_valid), nb, P<uint8_t>(matched), want_matched,
-                                                             P<void>(mask), st)));
+        ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_build_mask(DevPtr<uint32_t>(build_ids), DevPtr<void>(build_valid), nb, DevPtr<uint8_t>(matched), want_matched,
+                                                             DevPtr<void>(mask), st)));
         return RowsOfMask(std::move(mask), nb, ctx);
       };
       if (jt == 1 || jt == 3) {
@@ -399,31 +270,21 @@ class RocmHashJoinNode : public ac::ExecNode {
         if (jt == 6 || jt == 7) {
           ARROW_ASSIGN_OR_RAISE(tail, build_rows(0));
         }
-        n_out = total + (tail != nullptr ? tail->length : 0);
-        if (n_out > limit) return too_many(n_out);
-        BufferPtr sorted_rows, out_left, out_right, right_valid, left_valid;
-        if (pairs && total > 0) {
-          ARROW_ASSIGN_OR_RAISE(sorted_rows, sorted_build_rows());
-        }
-        ARROW_ASSIGN_OR_RAISE(out_left, AllocDevice(std::max<int64_t>(n_out, 1) * 8));
-        if (pairs) {
-          ARROW_ASSIGN_OR_RAISE(out_right, AllocDevice(std::max<int64_t>(n_out, 1) * 8));
-        }
-        if (jt == 5 || jt == 7) {
-          ARROW_ASSIGN_OR_RAISE(right_valid, AllocDevice(BitmapBytes(n_out)));
-        }
-        ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_expand(P<int64_t>(offsets), P<uint32_t>(probe_ids), P<void>(probe_valid), nl, P<int64_t>(group_offsets),
-                                                         P<uint64_t>(sorted_rows), jt, total, P<int64_t>(out_left), P<int64_t>(out_right),
-                                                         P<void>(right_valid), st)));
-        if (tail != nullptr) ARROW_RETURN_NOT_OK(append_tail(*tail, total, n_out, out_left, out_right, right_valid, &left_valid));
-        left_rows = IndexDatum(arrow::int64(), n_out, left_valid, out_left);
-        if (pairs) right_rows = IndexDatum(arrow::int64(), n_out, right_valid, out_right);
+        ARROW_RETURN_NOT_OK(row_pairs(total, tail, [&](const BufferPtr& out_left, const BufferPtr& out_right, const BufferPtr& right_valid) -> Status {
+          BufferPtr sorted_rows;
+          if (pairs && total > 0) {
+            ARROW_ASSIGN_OR_RAISE(sorted_rows, sorted_build_rows());
+          }
+          return FromArx(arx_hash_join_expand(DevPtr<int64_t>(offsets), DevPtr<uint32_t>(probe_ids), DevPtr<void>(probe_valid), nl, DevPtr<int64_t>(group_offsets),
+                                              DevPtr<uint64_t>(sorted_rows), jt, total, DevPtr<int64_t>(out_left), DevPtr<int64_t>(out_right),
+                                              DevPtr<void>(right_valid), st));
+        }));
       }
     } else {
       // the candidates as an inner join
       int64_t T = 0;
-      ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_probe_count(P<uint32_t>(probe_ids), P<void>(probe_valid), nl, P<int64_t>(group_offsets), num_groups, 4,
-                                                            nullptr, limit, P<int64_t>(offsets), P<void>(ws), ws_bytes, &T, st)));
+      ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_probe_count(DevPtr<uint32_t>(probe_ids), DevPtr<void>(probe_valid), nl, DevPtr<int64_t>(group_offsets), num_groups, 4,
+                                                            nullptr, limit, DevPtr<int64_t>(offsets), DevPtr<void>(ws), ws_bytes, &T, st)));
       ARROW_ASSIGN_OR_RAISE(auto cand_left, AllocDevice(std::max<int64_t>(T, 1) * 8));
       ARROW_ASSIGN_OR_RAISE(auto cand_right, AllocDevice(std::max<int64_t>(T, 1) * 8));
       ArxSpan pass{nullptr, nullptr, 0, 0, 0};
@@ -431,8 +292,8 @@ class RocmHashJoinNode : public ac::ExecNode {
       BufferPtr constant_pass;
       if (T > 0) {
         ARROW_ASSIGN_OR_RAISE(auto sorted_rows, sorted_build_rows());
-        ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_expand(P<int64_t>(offsets), P<uint32_t>(probe_ids), P<void>(probe_valid), nl, P<int64_t>(group_offsets),
-                                                         P<uint64_t>(sorted_rows), 4, T, P<int64_t>(cand_left), P<int64_t>(cand_right), nullptr, st)));
+        ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_expand(DevPtr<int64_t>(offsets), DevPtr<uint32_t>(probe_ids), DevPtr<void>(probe_valid), nl, DevPtr<int64_t>(group_offsets),
+                                                         DevPtr<uint64_t>(sorted_rows), 4, T, DevPtr<int64_t>(cand_left), DevPtr<int64_t>(cand_right), nullptr, st)));
         // the fields the filter reads, gathered at the candidate pairs: left fields, then right fields (BindFilter's schema)
         const cp::TakeOptions no_check = cp::TakeOptions::NoBoundsCheck();
         std::vector<arrow::Datum> values;
@@ -450,8 +311,8 @@ class RocmHashJoinNode : public ac::ExecNode {
         if (result.is_scalar()) {   // a constant filter: every candidate passes, or none
           const auto& flag = result.scalar_as<arrow::BooleanScalar>();
           ARROW_ASSIGN_OR_RAISE(constant_pass, AllocDevice(BitmapBytes(T)));
-          HIP_RETURN_NOT_OK(hipMemsetAsync(P<void>(constant_pass), flag.is_valid && flag.value ? 0xFF : 0, static_cast<size_t>(BitmapBytes(T)), st));
-          pass = ArxSpan{nullptr, P<void>(constant_pass), 0, T, 0};
+          HIP_RETURN_NOT_OK(hipMemsetAsync(DevPtr<void>(constant_pass), flag.is_valid && flag.value ? 0xFF : 0, static_cast<size_t>(BitmapBytes(T)), st));
+          pass = ArxSpan{nullptr, DevPtr<void>(constant_pass), 0, T, 0};
         } else {
           pass_data = result.array();
           if (pass_data->length != T) return Status::Invalid("arrow_amd: hashjoin_rocm: the filter's result has the wrong length");
@@ -473,12 +334,12 @@ class RocmHashJoinNode : public ac::ExecNode {
       const size_t fws_bytes = arx_hash_join_workspace_bytes(std::max<int64_t>({nl, words, 1}));
       ARROW_ASSIGN_OR_RAISE(auto fws, AllocDevice(static_cast<int64_t>(fws_bytes) + 64));
       int64_t total = 0;
-      ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_filter_count(&pass, P<int64_t>(offsets), P<int64_t>(cand_right), nl, jt, P<uint8_t>(build_hit),
-                                                             P<uint8_t>(probe_hit), limit, P<void>(pass_bits), P<int64_t>(prefix),
-                                                             P<int64_t>(new_offsets), P<void>(fws), fws_bytes, &total, st)));
+      ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_filter_count(&pass, DevPtr<int64_t>(offsets), DevPtr<int64_t>(cand_right), nl, jt, DevPtr<uint8_t>(build_hit),
+                                                             DevPtr<uint8_t>(probe_hit), limit, DevPtr<void>(pass_bits), DevPtr<int64_t>(prefix),
+                                                             DevPtr<int64_t>(new_offsets), DevPtr<void>(fws), fws_bytes, &total, st)));
       auto rows_of_flags = [&](const BufferPtr& flags, int64_t count, int want_set) -> arrow::Result<std::shared_ptr<ArrayData>> {
         ARROW_ASSIGN_OR_RAISE(auto mask, ZeroedDevice(BitmapBytes(count), st));
-        ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_flags_to_mask(P<uint8_t>(flags), count, want_set, P<void>(mask), st)));
+        ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_flags_to_mask(DevPtr<uint8_t>(flags), count, want_set, DevPtr<void>(mask), st)));
         return RowsOfMask(std::move(mask), count, ctx);
       };
       if (jt == 0 || jt == 2) {
@@ -494,20 +355,11 @@ class RocmHashJoinNode : public ac::ExecNode {
         if (jt == 6 || jt == 7) {
           ARROW_ASSIGN_OR_RAISE(tail, rows_of_flags(build_hit, nb, 0));
         }
-        n_out = total + (tail != nullptr ? tail->length : 0);
-        if (n_out > limit) return too_many(n_out);
-        BufferPtr right_valid, left_valid;
-        ARROW_ASSIGN_OR_RAISE(auto out_left, AllocDevice(std::max<int64_t>(n_out, 1) * 8));
-        ARROW_ASSIGN_OR_RAISE(auto out_right, AllocDevice(std::max<int64_t>(n_out, 1) * 8));
-        if (jt == 5 || jt == 7) {
-          ARROW_ASSIGN_OR_RAISE(right_valid, AllocDevice(BitmapBytes(n_out)));
-        }
-        ARROW_RETURN_NOT_OK(FromArx(arx_hash_join_filter_compact(P<void>(pass_bits), P<int64_t>(prefix), T, P<int64_t>(offsets), P<int64_t>(new_offsets), nl,
-                                                                 P<int64_t>(cand_left), P<int64_t>(cand_right), jt, total, P<int64_t>(out_left),
-                                                                 P<int64_t>(out_right), P<void>(right_valid), st)));
-        if (tail != nullptr) ARROW_RETURN_NOT_OK(append_tail(*tail, total, n_out, out_left, out_right, right_valid, &left_valid));
-        left_rows = IndexDatum(arrow::int64(), n_out, left_valid, out_left);
-        right_rows = IndexDatum(arrow::int64(), n_out, right_valid, out_right);
+        ARROW_RETURN_NOT_OK(row_pairs(total, tail, [&](const BufferPtr& out_left, const BufferPtr& out_right, const BufferPtr& right_valid) -> Status {
+          return FromArx(arx_hash_join_filter_compact(DevPtr<void>(pass_bits), DevPtr<int64_t>(prefix), T, DevPtr<int64_t>(offsets), DevPtr<int64_t>(new_offsets), nl,
+                                                      DevPtr<int64_t>(cand_left), DevPtr<int64_t>(cand_right), jt, total, DevPtr<int64_t>(out_left),
+                                                      DevPtr<int64_t>(out_right), DevPtr<void>(right_valid), st));
+        }));
       }
       HIP_RETURN_NOT_OK(hipStreamSynchronize(st));   // (pass_data and the candidates are released below)
     }
@@ -522,10 +374,6 @@ class RocmHashJoinNode : public ac::ExecNode {
       for (int c = 0; c < maps_->proj_maps[s].num_cols(Proj::OUTPUT); ++c) {
         ARROW_ASSIGN_OR_RAISE(auto col, column(s, to_input.get(c)));
         ARROW_ASSIGN_OR_RAISE(arrow::Datum taken, cp::CallFunction("array_take", {arrow::Datum(col), rows}, &no_check, ctx));
-        if (!any_device) {   // host in, host out
-          ARROW_ASSIGN_OR_RAISE(auto host, CopyDataToHost(*taken.array()));
-          taken = arrow::Datum(std::move(host));
-        }
         out_columns.push_back(std::move(taken));
       }
     }
@@ -537,37 +385,11 @@ class RocmHashJoinNode : public ac::ExecNode {
     whole[0].clear();
     whole[1].clear();
     CountGpu(kFnHashJoin);
-    if (n_out == 0) return output_->InputFinished(this, 0);
-    cp::ExecBatch out(std::move(out_columns), n_out);
-    const int64_t batch_size = ac::ExecPlan::kMaxBatchSize;
-    const int num_batches = static_cast<int>((n_out + batch_size - 1) / batch_size);
-    for (int i = 0; i < num_batches; ++i) {
-      cp::ExecBatch slice = out.Slice(i * batch_size, batch_size);
-      slice.index = i;
-      if (any_device) {
-        // a slice of a device array carries its exact null count: nobody may popcount HBM from the CPU
-        for (auto& value : slice.values) {
-          ArrayData* a = value.mutable_array();
-          if (a->null_count.load() != arrow::kUnknownNullCount || a->buffers[0] == nullptr) continue;
-          void* cws = nullptr;
-          ARROW_RETURN_NOT_OK(t_scratch.Get(kCounter, 64, &cws));
-          int64_t set_bits = 0;
-          ARROW_RETURN_NOT_OK(FromArx(arx_bitmap_popcount(reinterpret_cast<const void*>(a->buffers[0]->address()), a->offset, a->length, cws, 64,
-                                                          &set_bits, st)));
-          a->null_count = a->length - set_bits;
-        }
-      }
-      ARROW_RETURN_NOT_OK(output_->InputReceived(this, std::move(slice)));
-    }
-    return output_->InputFinished(this, num_batches);
+    return EmitResult(this, output_, std::move(out_columns), n_out, any_device, st);
   }
 
   const ac::JoinType join_type_;
   const std::vector<ac::JoinKeyCmp> key_cmp_;
   const std::unique_ptr<ac::HashJoinSchema> maps_;
   const cp::Expression filter_;
-  std::mutex mu_;
-  ac::AtomicCounter counter_[2];
-  std::atomic<int> sides_done_{0};
-  std::vector<cp::ExecBatch> batches_[2];
 };

@@ -16,6 +16,7 @@
 //   3. array_take of every column by the permutation.
 // Steps 2 and 3 go through CallFunction, i.e. through the kernels this shim registered.  Host batches are
 // uploaded by step 1 and the result is copied back, so the node is a drop-in for "order_by" either way.
+// Step 1 and the way out (slices, numbers, exact null counts) are WholeColumn / EmitResult of plugin/acero_common.inc.
 // Registered under a NEW name (duplicates are rejected, acero/exec_plan.cc:1132-1142).
 // Lexicographic stable sort over several device-resident key columns (what TableSorter / MultipleKeyRecordBatchSorter,
 // kernels/vector_sort.cc:850-954, compute on the CPU): least-significant key first, one stable device sort per key,
@@ -202,7 +203,7 @@ Status BooleanSortOnDevice(const ArraySpan& values, const cp::ArraySortOptions& 
   if (options.null_placement != cp::NullPlacement::AtStart) parts.push_back(nulls.array());
   hipStream_t st;
   ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
-  ARROW_ASSIGN_OR_RAISE(auto whole, ConcatChunksOnDevice(arrow::uint64(), parts, st));
+  ARROW_ASSIGN_OR_RAISE(auto whole, ConcatOnDevice(arrow::uint64(), parts, st));
   HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
   if (whole->length != values.length) return Status::Invalid("arrow_amd: boolean sort lost rows");
   if (whole->offset != 0) return Status::Invalid("arrow_amd: boolean sort: concatenation with an offset");
@@ -254,34 +255,11 @@ Status StructSortOnDevice(const ArraySpan& values, const cp::ArraySortOptions& o
   if (options.null_placement != cp::NullPlacement::AtStart) parts.push_back(null_rows.array());
   hipStream_t st;
   ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
-  ARROW_ASSIGN_OR_RAISE(auto whole, ConcatChunksOnDevice(arrow::uint64(), parts, st));
+  ARROW_ASSIGN_OR_RAISE(auto whole, ConcatOnDevice(arrow::uint64(), parts, st));
   HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
   if (whole->length != n || whole->offset != 0) return Status::Invalid("arrow_amd: struct sort lost rows");
   out->buffers[1] = whole->buffers[1];
   return Status::OK();
-}
-
-// array data, children and dictionary included, copied to host memory (dictionaries: small by nature)
-arrow::Result<std::shared_ptr<ArrayData>> CopyDataToHost(const ArrayData& d) {
-  std::vector<std::shared_ptr<Buffer>> bufs(d.buffers.size());
-  for (size_t i = 0; i < bufs.size(); ++i) {
-    if (d.buffers[i] == nullptr) continue;
-    if (d.buffers[i]->is_cpu()) {
-      bufs[i] = d.buffers[i];
-    } else {
-      ARROW_ASSIGN_OR_RAISE(bufs[i], arrow::MemoryManager::CopyBuffer(d.buffers[i], arrow::default_cpu_memory_manager()));
-    }
-  }
-  // (a device array's null count is not to be trusted when a validity buffer exists: see DeviceSpan)
-  auto host = ArrayData::Make(d.type, d.length, std::move(bufs), bufs.empty() || d.buffers[0] == nullptr ? 0 : arrow::kUnknownNullCount, d.offset);
-  for (const auto& child : d.child_data) {
-    ARROW_ASSIGN_OR_RAISE(auto hc, CopyDataToHost(*child));
-    host->child_data.push_back(std::move(hc));
-  }
-  if (d.dictionary != nullptr) {
-    ARROW_ASSIGN_OR_RAISE(host->dictionary, CopyDataToHost(*d.dictionary));
-  }
-  return host;
 }
 
 // array_sort_indices of a device-resident dictionary array (declared in plugin/sort.inc, slot 20) — the reference's algorithm
@@ -369,7 +347,7 @@ class RocmSortIndicesMetaFunction : public cp::MetaFunction {
       ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
       std::vector<std::shared_ptr<ArrayData>> chunks;
       for (const auto& chunk : c.chunks()) chunks.push_back(chunk->data());
-      ARROW_ASSIGN_OR_RAISE(auto whole, ConcatChunksOnDevice(c.type(), chunks, st));
+      ARROW_ASSIGN_OR_RAISE(auto whole, ConcatOnDevice(c.type(), chunks, st));
       HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
       return arrow::Datum(whole);
     };
@@ -424,12 +402,7 @@ class RocmSortIndicesMetaFunction : public cp::MetaFunction {
   std::shared_ptr<cp::Function> stock_;
 };
 
-class RocmCoalesceNode;
-class RocmOrderByNode : public ac::ExecNode {
-  friend class RocmCoalesceNode;   // (shares ConcatOnDevice)
-  friend arrow::Result<std::shared_ptr<ArrayData>> ConcatChunksOnDevice(const std::shared_ptr<arrow::DataType>&,
-                                                                        const std::vector<std::shared_ptr<ArrayData>>&, hipStream_t);
-
+class RocmOrderByNode : public AccumulatingNode {
  public:
   struct Key {
     int column;
@@ -439,7 +412,7 @@ class RocmOrderByNode : public ac::ExecNode {
 
   RocmOrderByNode(ac::ExecPlan* plan, std::vector<ac::ExecNode*> inputs, std::shared_ptr<arrow::Schema> schema,
                   cp::Ordering ordering, std::vector<Key> keys)
-      : ac::ExecNode(plan, std::move(inputs), {"input"}, std::move(schema)),
+      : AccumulatingNode(plan, std::move(inputs), {"input"}, std::move(schema)),
         ordering_(std::move(ordering)), keys_(std::move(keys)) {}
 
   static arrow::Result<ac::ExecNode*> Make(ac::ExecPlan* plan, std::vector<ac::ExecNode*> inputs,
@@ -474,208 +447,24 @@ class RocmOrderByNode : public ac::ExecNode {
   const char* kind_name() const override { return "RocmOrderByNode"; }
   const cp::Ordering& ordering() const override { return ordering_; }
 
-  Status InputReceived(ac::ExecNode*, cp::ExecBatch batch) override {
-    {
-      std::lock_guard<std::mutex> lock(mu_);
-      batches_.push_back(std::move(batch));
-    }
-    if (counter_.Increment()) return Finish();
-    return Status::OK();
-  }
-  Status InputFinished(ac::ExecNode*, int total_batches) override {
-    if (counter_.SetTotal(total_batches)) return Finish();
-    return Status::OK();
-  }
-  Status StartProducing() override { return Status::OK(); }
-  void PauseProducing(ac::ExecNode*, int32_t) override {}
-  void ResumeProducing(ac::ExecNode*, int32_t) override {}
-
- protected:
-  Status StopProducingImpl() override { return Status::OK(); }
-
  private:
-  static const uint8_t* HostBytes(const std::shared_ptr<Buffer>& b) { return b ? b->data() : nullptr; }
-  static const uint8_t* DeviceBytes(const std::shared_ptr<Buffer>& b) {
-    return b ? reinterpret_cast<const uint8_t*>(b->address()) : nullptr;
-  }
-
-  // bits [offset, offset+length) of a host or device bitmap (nullptr = all ones) appended at `dst_bit`
-  static Status AppendBits(const std::shared_ptr<Buffer>& src, bool on_device, int64_t offset, int64_t length,
-                           uint8_t* dst, int64_t dst_bit, hipStream_t st) {
-    if (length == 0) return Status::OK();
-    const void* bits = nullptr;
-    int64_t bit_offset = offset;
-    if (src != nullptr && !on_device) {
-      const int64_t first = offset / 8, last = (offset + length + 7) / 8;
-      void* staged = nullptr;
-      ARROW_RETURN_NOT_OK(t_scratch.Get(kValidity, static_cast<size_t>(last - first) + 16, &staged));
-      HIP_RETURN_NOT_OK(hipMemcpyAsync(staged, src->data() + first, last - first, hipMemcpyHostToDevice, st));
-      HIP_RETURN_NOT_OK(hipStreamSynchronize(st));   // (pageable source; the slot is reused by the next chunk)
-      bits = staged;
-      bit_offset = offset % 8;
-    } else if (src != nullptr) {
-      bits = DeviceBytes(src);
-    }
-    return FromArx(arx_bitmap_copy_at(bits, bit_offset, length, dst, dst_bit, st));
-  }
-
-  // Concatenate (array/concatenate.cc) of one column's chunks into one device-resident array
-  static arrow::Result<std::shared_ptr<ArrayData>> ConcatOnDevice(const std::shared_ptr<arrow::DataType>& type,
-                                                                  const std::vector<std::shared_ptr<ArrayData>>& chunks,
-                                                                  hipStream_t st) {
-    int64_t n = 0;
-    bool any_validity = false;
-    for (const auto& c : chunks) {
-      n += c->length;
-      any_validity = any_validity || (c->buffers[0] != nullptr && c->null_count.load() != 0);
-    }
-    // consecutive slices of one device array (what table_source cuts a device table into): nothing to copy
-    bool contiguous = !chunks.empty() && DataOnRocm(*chunks[0]);
-    for (size_t i = 1; contiguous && i < chunks.size(); ++i) {
-      const auto &a = *chunks[i - 1], &b = *chunks[i];
-      contiguous = a.buffers.size() == b.buffers.size() && a.offset + a.length == b.offset;
-      for (size_t j = 0; contiguous && j < a.buffers.size(); ++j) contiguous = a.buffers[j] == b.buffers[j];
-    }
-    if (contiguous) {
-      const auto& first = *chunks[0];
-      int64_t null_count = 0;
-      if (first.buffers[0] != nullptr) {
-        void* ws = nullptr;
-        ARROW_RETURN_NOT_OK(t_scratch.Get(kCounter, 64, &ws));
-        int64_t set_bits = 0;
-        ARROW_RETURN_NOT_OK(FromArx(arx_bitmap_popcount(DeviceBytes(first.buffers[0]), first.offset, n, ws, 64, &set_bits, st)));
-        null_count = n - set_bits;
-      }
-      return ArrayData::Make(type, n, first.buffers, null_count, first.offset);
-    }
-    const int64_t bitmap_bytes = ((n + 63) / 64) * 8;
-    std::shared_ptr<Buffer> validity;
-    if (any_validity) {
-      ARROW_ASSIGN_OR_RAISE(validity, AllocDevice(bitmap_bytes));
-      HIP_RETURN_NOT_OK(hipMemsetAsync(reinterpret_cast<void*>(validity->mutable_address()), 0, bitmap_bytes, st));
-      int64_t pos = 0;
-      for (const auto& c : chunks) {
-        const bool has = c->buffers[0] != nullptr && c->null_count.load() != 0;
-        ARROW_RETURN_NOT_OK(AppendBits(has ? c->buffers[0] : nullptr, DataOnRocm(*c), c->offset, c->length,
-                                       reinterpret_cast<uint8_t*>(validity->mutable_address()), pos, st));
-        pos += c->length;
-      }
-    }
-    std::vector<std::shared_ptr<Buffer>> bufs{validity};
-    if (type->id() == Type::BOOL) {
-      ARROW_ASSIGN_OR_RAISE(auto data, AllocDevice(bitmap_bytes));
-      HIP_RETURN_NOT_OK(hipMemsetAsync(reinterpret_cast<void*>(data->mutable_address()), 0, bitmap_bytes, st));
-      int64_t pos = 0;
-      for (const auto& c : chunks) {
-        ARROW_RETURN_NOT_OK(AppendBits(c->buffers[1], DataOnRocm(*c), c->offset, c->length,
-                                       reinterpret_cast<uint8_t*>(data->mutable_address()), pos, st));
-        pos += c->length;
-      }
-      bufs.push_back(std::move(data));
-    } else if (IsInt32Binary(*type)) {
-      // where each chunk's bytes start and end (two offsets per chunk; read back for device chunks)
-      std::vector<std::pair<int32_t, int32_t>> range(chunks.size(), {0, 0});
-      int64_t total = 0;
-      for (size_t i = 0; i < chunks.size(); ++i) {
-        const auto& c = *chunks[i];
-        if (c.length == 0) continue;
-        if (DataOnRocm(c)) {
-          const uint8_t* off = DeviceBytes(c.buffers[1]);
-          HIP_RETURN_NOT_OK(hipMemcpyAsync(&range[i].first, off + c.offset * 4, 4, hipMemcpyDeviceToHost, st));
-          HIP_RETURN_NOT_OK(hipMemcpyAsync(&range[i].second, off + (c.offset + c.length) * 4, 4, hipMemcpyDeviceToHost, st));
-          HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
-        } else {
-          const int32_t* off = reinterpret_cast<const int32_t*>(c.buffers[1]->data());
-          range[i] = {off[c.offset], off[c.offset + c.length]};
-        }
-        total += range[i].second - range[i].first;
-      }
-      if (total > INT32_MAX) return Status::Invalid("offset overflow while concatenating arrays");   // concatenate.cc PutOffsets
-      ARROW_ASSIGN_OR_RAISE(auto offsets, AllocDevice((n + 1) * 4));
-      ARROW_ASSIGN_OR_RAISE(auto data, AllocDevice(total));
-      HIP_RETURN_NOT_OK(hipMemsetAsync(reinterpret_cast<void*>(offsets->mutable_address()), 0, (n + 1) * 4, st));
-      int64_t pos = 0;
-      int32_t base = 0;
-      for (size_t i = 0; i < chunks.size(); ++i) {
-        const auto& c = *chunks[i];
-        if (c.length == 0) continue;
-        const bool dev = DataOnRocm(c);
-        const int32_t* src_off = nullptr;
-        if (dev) {
-          src_off = reinterpret_cast<const int32_t*>(DeviceBytes(c.buffers[1])) + c.offset;
-        } else {
-          void* staged = nullptr;
-          ARROW_RETURN_NOT_OK(t_scratch.Get(kArg2, static_cast<size_t>(c.length + 1) * 4, &staged));
-          HIP_RETURN_NOT_OK(hipMemcpyAsync(staged, c.buffers[1]->data() + c.offset * 4, (c.length + 1) * 4,
-                                           hipMemcpyHostToDevice, st));
-          HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
-          src_off = static_cast<const int32_t*>(staged);
-        }
-        ARROW_RETURN_NOT_OK(FromArx(arx_binary_rebase_offsets(
-            src_off, c.length, base, reinterpret_cast<int32_t*>(offsets->mutable_address()) + pos, st)));
-        const int64_t nbytes = range[i].second - range[i].first;
-        if (nbytes > 0) {
-          const uint8_t* src = (dev ? DeviceBytes(c.buffers[2]) : c.buffers[2]->data()) + range[i].first;
-          HIP_RETURN_NOT_OK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(data->mutable_address()) + base, src, nbytes,
-                                           dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-          if (!dev) HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
-        }
-        pos += c.length;
-        base += static_cast<int32_t>(nbytes);
-      }
-      bufs.push_back(std::move(offsets));
-      bufs.push_back(std::move(data));
-    } else {
-      const int w = FixedByteWidth(*type);
-      ARROW_ASSIGN_OR_RAISE(auto data, AllocDevice(n * w));
-      int64_t pos = 0;
-      for (const auto& c : chunks) {
-        if (c->length == 0) continue;
-        const bool dev = DataOnRocm(*c);
-        const uint8_t* src = (dev ? DeviceBytes(c->buffers[1]) : c->buffers[1]->data()) + c->offset * w;
-        HIP_RETURN_NOT_OK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(data->mutable_address()) + pos * w, src,
-                                         c->length * w, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-        if (!dev) HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
-        pos += c->length;
-      }
-      bufs.push_back(std::move(data));
-    }
-    int64_t null_count = 0;
-    if (any_validity) {
-      ARROW_ASSIGN_OR_RAISE(null_count, DeviceNullCount(*validity, n, st));   // exact: nothing may popcount it on the CPU
-    }
-    HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
-    return ArrayData::Make(type, n, std::move(bufs), null_count, 0);
-  }
-
-  Status Finish() {
-    std::lock_guard<std::mutex> lock(mu_);
+  Status Finish() override {
     hipStream_t st;
     ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
     cp::ExecContext* ctx = plan_->query_context()->exec_context();
-    // arrival order is the tie-break in the reference (its queue is filled as batches arrive); with batch
-    // indices present (an ordered source) use them, so that the result does not depend on the thread schedule
-    const bool indexed = std::all_of(batches_.begin(), batches_.end(), [](const cp::ExecBatch& b) { return b.index >= 0; });
-    if (indexed) {
-      std::stable_sort(batches_.begin(), batches_.end(),
-                       [](const cp::ExecBatch& a, const cp::ExecBatch& b) { return a.index < b.index; });
-    }
+    // (arrival order is the tie-break in the reference: its queue is filled as batches arrive)
+    std::vector<cp::ExecBatch>& batches = batches_[0];
+    OrderBatchesByIndex(&batches);
     const int ncols = output_schema_->num_fields();
     int64_t n = 0;
     bool any_device = false;
-    for (const auto& b : batches_) n += b.length;
+    for (const auto& b : batches) n += b.length;
     std::vector<arrow::Datum> whole(ncols);
     for (int c = 0; c < ncols; ++c) {
-      std::vector<std::shared_ptr<ArrayData>> chunks;
-      for (const auto& b : batches_) {
-        if (!b[c].is_array()) return Status::NotImplemented("order_by_rocm: scalar columns");
-        chunks.push_back(b[c].array());
-        any_device = any_device || DataOnRocm(*b[c].array());
-      }
-      ARROW_ASSIGN_OR_RAISE(auto col, ConcatOnDevice(output_schema_->field(c)->type(), chunks, st));
+      ARROW_ASSIGN_OR_RAISE(auto col, WholeColumn(batches, output_schema_->field(c)->type(), c, st, &any_device, "order_by_rocm"));
       whole[c] = arrow::Datum(std::move(col));
     }
-    batches_.clear();
+    batches.clear();
     if (n == 0) return output_->InputFinished(this, 0);
     const cp::TakeOptions no_check = cp::TakeOptions::NoBoundsCheck();
     std::vector<DeviceSortKey> chain;
@@ -685,50 +474,11 @@ class RocmOrderByNode : public ac::ExecNode {
     for (int c = 0; c < ncols; ++c) {
       ARROW_ASSIGN_OR_RAISE(sorted[c], cp::CallFunction("array_take", {whole[c], perm}, &no_check, ctx));
       whole[c] = arrow::Datum();      // (release the concatenated input as we go)
-      if (!any_device) {              // host in, host out
-        auto data = sorted[c].array()->Copy();
-        for (auto& b : data->buffers) {
-          if (b != nullptr) {
-            ARROW_ASSIGN_OR_RAISE(b, arrow::MemoryManager::CopyBuffer(b, arrow::default_cpu_memory_manager()));
-          }
-        }
-        sorted[c] = arrow::Datum(std::move(data));
-      }
     }
     CountGpu(kFnOrderBy);
-    cp::ExecBatch out(std::move(sorted), n);
-    const int64_t batch_size = ac::ExecPlan::kMaxBatchSize;
-    const int nb = static_cast<int>((n + batch_size - 1) / batch_size);
-    for (int i = 0; i < nb; ++i) {
-      cp::ExecBatch slice = out.Slice(i * batch_size, batch_size);
-      slice.index = i;
-      if (any_device) {
-        // a slice of a device array must carry its exact null count: whoever asks (Table::FromRecordBatches,
-        // ChunkedArray's constructor) would otherwise popcount HBM from the CPU
-        for (auto& value : slice.values) {
-          ArrayData* a = value.mutable_array();
-          if (a->null_count.load() != arrow::kUnknownNullCount || a->buffers[0] == nullptr) continue;
-          void* ws = nullptr;
-          ARROW_RETURN_NOT_OK(t_scratch.Get(kCounter, 64, &ws));
-          int64_t set_bits = 0;
-          ARROW_RETURN_NOT_OK(FromArx(arx_bitmap_popcount(DeviceBytes(a->buffers[0]), a->offset, a->length, ws, 64,
-                                                          &set_bits, st)));
-          a->null_count = a->length - set_bits;
-        }
-      }
-      ARROW_RETURN_NOT_OK(output_->InputReceived(this, std::move(slice)));
-    }
-    return output_->InputFinished(this, nb);
+    return EmitResult(this, output_, std::move(sorted), n, any_device, st);
   }
 
   const cp::Ordering ordering_;
   const std::vector<Key> keys_;
-  std::mutex mu_;
-  ac::AtomicCounter counter_;
-  std::vector<cp::ExecBatch> batches_;
 };
-
-arrow::Result<std::shared_ptr<ArrayData>> ConcatChunksOnDevice(const std::shared_ptr<arrow::DataType>& type,
-                                                               const std::vector<std::shared_ptr<ArrayData>>& chunks, hipStream_t st) {
-  return RocmOrderByNode::ConcatOnDevice(type, chunks, st);
-}

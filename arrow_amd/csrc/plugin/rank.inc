@@ -47,7 +47,7 @@ arrow::Result<std::shared_ptr<ArrayData>> OneDeviceArray(const arrow::Datum& d) 
   ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
   std::vector<std::shared_ptr<ArrayData>> chunks;
   for (const auto& chunk : c.chunks()) chunks.push_back(chunk->data());
-  ARROW_ASSIGN_OR_RAISE(auto whole, ConcatChunksOnDevice(c.type(), chunks, st));
+  ARROW_ASSIGN_OR_RAISE(auto whole, ConcatOnDevice(c.type(), chunks, st));
   HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
   return whole;
 }
@@ -87,7 +87,7 @@ arrow::Result<arrow::Datum> RankOnDevice(const arrow::Datum& input, cp::SortOrde
   void* ws = nullptr;
   const size_t ws_bytes = arx_rank_workspace_bytes(n);
   ARROW_RETURN_NOT_OK(t_scratch.Get(kWs, ws_bytes + 256, &ws));
-  ws = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
+  ws = Align256(ws);
   const auto* rows = reinterpret_cast<const uint64_t*>(perm.array()->buffers[1]->address()) + perm.array()->offset;
   ARROW_RETURN_NOT_OK(FromArx(arx_rank(&dv, key_type, rows, tiebreaker, ws, ws_bytes, reinterpret_cast<void*>(out->mutable_address()), st)));
   HIP_RETURN_NOT_OK(hipStreamSynchronize(st));

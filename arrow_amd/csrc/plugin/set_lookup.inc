@@ -110,8 +110,9 @@ Status SetLookupBuild(DeviceSetLookupState* s, cp::ExecContext* exec_ctx, hipStr
   }
   s->set = dev;
   const int64_t m = dev->length;
-  ARROW_ASSIGN_OR_RAISE(s->table_buf, AllocDevice(static_cast<int64_t>(arx_set_lookup_state_bytes(m, s->key_width)) + 256));
-  s->table = Align256(s->table_buf);
+  ARROW_ASSIGN_OR_RAISE(auto table, AllocAligned(static_cast<int64_t>(arx_set_lookup_state_bytes(m, s->key_width))));
+  s->table_buf = std::move(table.buffer);
+  s->table = table.ptr;
   const ArraySpan span(*dev);
   if (s->key_width == -1) {
     ArxBinarySpan bs{};

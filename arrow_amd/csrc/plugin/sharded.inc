@@ -163,8 +163,8 @@ Status TryShardedRangeGroupBySum(const ShardedComm& c, const RcclApi* api, const
   HIP_RETURN_NOT_OK(hipMemsetAsync(dev_ptr(state), 0, static_cast<size_t>(plan.state_bytes), st));
   int64_t ok = 1;
   if (n > 0) {
-    ARROW_ASSIGN_OR_RAISE(auto ws_buf, AllocDevice(static_cast<int64_t>(probe.workspace_bytes) + 256));
-    void* ws = reinterpret_cast<void*>((ws_buf->mutable_address() + 255) & ~uintptr_t(255));
+    ARROW_ASSIGN_OR_RAISE(auto ws_buf, AllocAligned(static_cast<int64_t>(probe.workspace_bytes)));
+    void* ws = ws_buf.ptr;
     const int rc = arx_groupby_range_sum_i64_consume(dev_ptr(state), &plan, &dk, &dv, ws, static_cast<size_t>(probe.workspace_bytes), st);
     if (rc == ARX_CAPACITY_ERROR || rc == ARX_NOT_IMPLEMENTED) {
       ok = 0;
@@ -232,8 +232,8 @@ Status TryShardedRangeGroupBySum(const ShardedComm& c, const RcclApi* api, const
   int64_t g = 0;
   if (mine > 0) {
     const size_t fws_bytes = arx_groupby_range_finalize_workspace_bytes(slots);
-    ARROW_ASSIGN_OR_RAISE(auto fws_buf, AllocDevice(static_cast<int64_t>(fws_bytes) + 256));
-    void* fws = reinterpret_cast<void*>((fws_buf->mutable_address() + 255) & ~uintptr_t(255));
+    ARROW_ASSIGN_OR_RAISE(auto fws_buf, AllocAligned(static_cast<int64_t>(fws_bytes)));
+    void* fws = fws_buf.ptr;
     ARROW_RETURN_NOT_OK(FromArx(arx_groupby_range_finalize(blocks + (world > 1 ? 0 : first * pb), static_cast<int32_t>(plan.key_min + first * plan.width),
                                                            plan.width, mine, min_count, fws, fws_bytes, static_cast<int32_t*>(dev_ptr(o_keys)),
                                                            static_cast<int64_t*>(dev_ptr(o_sums)), nullptr, static_cast<uint8_t*>(dev_ptr(svalid_bytes)),
@@ -286,17 +286,18 @@ Status ShardedGroupBySum(const ShardedComm& c, const ArrayData& keys, const Arra
 
   auto make_table = [&](int64_t groups_bound, std::shared_ptr<Buffer>* buf, void** state, int64_t* cap) -> Status {
     *cap = Pow2AtLeast(std::min<int64_t>(2 * groups_bound + 2, int64_t(1) << 30));
-    ARROW_ASSIGN_OR_RAISE(*buf, AllocDevice(static_cast<int64_t>(arx_groupby_state_bytes(*cap)) + 256));
-    *state = reinterpret_cast<void*>(((*buf)->mutable_address() + 255) & ~uintptr_t(255));
+    ARROW_ASSIGN_OR_RAISE(auto table, AllocAligned(static_cast<int64_t>(arx_groupby_state_bytes(*cap))));
+    *buf = std::move(table.buffer);
+    *state = table.ptr;
     return FromArx(arx_groupby_init(*state, *cap, st));
   };
   auto consume = [&](void* state, int64_t cap, const ArxSpan& k, const ArxSpan& v) -> Status {
     const size_t ws_bytes = arx_groupby_consume_workspace_bytes(k.length, cap);
-    std::shared_ptr<Buffer> ws_buf;
+    AlignedDevice ws_buf{nullptr, nullptr};
     void* ws = nullptr;
     if (ws_bytes > 0) {
-      ARROW_ASSIGN_OR_RAISE(ws_buf, AllocDevice(static_cast<int64_t>(ws_bytes) + 256));
-      ws = reinterpret_cast<void*>((ws_buf->mutable_address() + 255) & ~uintptr_t(255));
+      ARROW_ASSIGN_OR_RAISE(ws_buf, AllocAligned(static_cast<int64_t>(ws_bytes)));
+      ws = ws_buf.ptr;
     }
     ARROW_RETURN_NOT_OK(FromArx(arx_groupby_sum_i64_consume(state, cap, &k, &v, ws, ws_bytes, st)));
     HIP_RETURN_NOT_OK(hipStreamSynchronize(st));   // (the workspace goes back to the pool)
@@ -331,8 +332,8 @@ Status ShardedGroupBySum(const ShardedComm& c, const ArrayData& keys, const Arra
     if (dk.null_count == 0 && dv.null_count == 0 && world <= 64) {
       const size_t ws_bytes = arx_groupby_consume_workspace_bytes(n, plan_cap);
       if (ws_bytes > 0) {
-        ARROW_ASSIGN_OR_RAISE(auto ws_buf, AllocDevice(static_cast<int64_t>(ws_bytes) + 256));
-        void* ws = reinterpret_cast<void*>((ws_buf->mutable_address() + 255) & ~uintptr_t(255));
+        ARROW_ASSIGN_OR_RAISE(auto ws_buf, AllocAligned(static_cast<int64_t>(ws_bytes)));
+        void* ws = ws_buf.ptr;
         region_records = arx_groupby_partials_capacity(n, plan_cap, world);
         ARROW_ASSIGN_OR_RAISE(records, AllocDevice(region_records * world * 24));
         const int rc = arx_groupby_sum_i64_consume_partials(nullptr, plan_cap, &dk, &dv, ws, ws_bytes, world,

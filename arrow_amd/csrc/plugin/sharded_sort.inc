@@ -176,8 +176,8 @@ Status ShardedSortIndices(const ShardedComm& c, const ArrayData& values, bool de
     ARROW_ASSIGN_OR_RAISE(auto result, AllocDevice(std::max<int64_t>(m, 1) * 8));
     if (m > 0) {
       const size_t sort_ws_bytes = arx_sort_indices_workspace_bytes(m);
-      ARROW_ASSIGN_OR_RAISE(auto sort_ws_buf, AllocDevice(static_cast<int64_t>(sort_ws_bytes) + 256));
-      void* sort_ws = reinterpret_cast<void*>((sort_ws_buf->mutable_address() + 255) & ~uintptr_t(255));
+      ARROW_ASSIGN_OR_RAISE(auto sort_ws_buf, AllocAligned(static_cast<int64_t>(sort_ws_bytes)));
+      void* sort_ws = sort_ws_buf.ptr;
       ARROW_RETURN_NOT_OK(FromArx(arx_sort_records(static_cast<const ArxSortRecord*>(dev_ptr(inbox)), m, sort_ws, sort_ws_bytes,
                                                    static_cast<uint64_t*>(dev_ptr(result)), st)));
     }
@@ -192,8 +192,8 @@ Status ShardedSortIndices(const ShardedComm& c, const ArrayData& values, bool de
 
   // ---- 2. stable partition by destination, packed records (+ this shard's null rows)
   const size_t ws_bytes = arx_sort_indices_workspace_bytes(std::max<int64_t>(n, 1));
-  ARROW_ASSIGN_OR_RAISE(auto ws_buf, AllocDevice(static_cast<int64_t>(ws_bytes) + 256));
-  void* ws = reinterpret_cast<void*>((ws_buf->mutable_address() + 255) & ~uintptr_t(255));
+  ARROW_ASSIGN_OR_RAISE(auto ws_buf, AllocAligned(static_cast<int64_t>(ws_bytes)));
+  void* ws = ws_buf.ptr;
   ARROW_ASSIGN_OR_RAISE(auto records, AllocDevice(std::max<int64_t>(n, 1) * 12));
   ARROW_ASSIGN_OR_RAISE(auto d_counts, AllocDevice(world * 8));
   HIP_RETURN_NOT_OK(hipMemsetAsync(dev_ptr(d_counts), 0, static_cast<size_t>(world) * 8, st));
@@ -266,8 +266,8 @@ Status ShardedSortIndices(const ShardedComm& c, const ArrayData& values, bool de
   if (m_valid > 0) {
     // the received keys are already order-transformed: plain ascending unsigned sort, then rows[perm]
     const size_t sort_ws_bytes = arx_sort_indices_workspace_bytes(m_valid);
-    ARROW_ASSIGN_OR_RAISE(auto sort_ws_buf, AllocDevice(static_cast<int64_t>(sort_ws_bytes) + 256));
-    void* sort_ws = reinterpret_cast<void*>((sort_ws_buf->mutable_address() + 255) & ~uintptr_t(255));
+    ARROW_ASSIGN_OR_RAISE(auto sort_ws_buf, AllocAligned(static_cast<int64_t>(sort_ws_bytes)));
+    void* sort_ws = sort_ws_buf.ptr;
     ARROW_ASSIGN_OR_RAISE(auto perm, AllocDevice(m_valid * 8));
     const ArxSpan dkeys{nullptr, dev_ptr(keys_recv), 0, m_valid, 0};
     ARROW_RETURN_NOT_OK(FromArx(arx_sort_indices_64(&dkeys, 0, ARX_SORT_ASCENDING, ARX_NULLS_AT_END, sort_ws, sort_ws_bytes,

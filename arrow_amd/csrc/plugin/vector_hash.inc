@@ -36,10 +36,6 @@ const StockKernel& StockHashKernel() {
   return KIND == kHashUnique ? g_stock_unique : KIND == kHashValueCounts ? g_stock_value_counts : g_stock_dict_encode;
 }
 
-void* Align256(const std::shared_ptr<Buffer>& b) {
-  return reinterpret_cast<void*>((b->mutable_address() + 255) & ~uintptr_t(255));
-}
-
 // column `col` of the Grouper's unique key rows as device buffers (+ its null count)
 Status HashUniques(DeviceHashState* s, hipStream_t st, std::shared_ptr<Buffer>* values, std::shared_ptr<Buffer>* validity,
                    int64_t* null_count) {
@@ -59,8 +55,8 @@ Status HashEnsureCapacity(DeviceHashState* s, int64_t more, hipStream_t st) {
   const int64_t need = s->num_groups + more + 16;
   if (s->table != nullptr && need <= s->max_groups) return Status::OK();
   const int64_t fresh_max = std::max<int64_t>({need, 2 * s->max_groups, 1 << 12});
-  ARROW_ASSIGN_OR_RAISE(auto fresh_buf, AllocDevice(static_cast<int64_t>(arx_grouper_state_bytes(fresh_max)) + 256));
-  void* fresh = Align256(fresh_buf);
+  ARROW_ASSIGN_OR_RAISE(auto fresh_table, AllocAligned(static_cast<int64_t>(arx_grouper_state_bytes(fresh_max))));
+  void* const fresh = fresh_table.ptr;
   ARROW_RETURN_NOT_OK(FromArx(arx_grouper_init(fresh, fresh_max, st)));
   if (s->table != nullptr && s->num_groups > 0) {
     std::shared_ptr<Buffer> values, validity;
@@ -72,11 +68,11 @@ Status HashEnsureCapacity(DeviceHashState* s, int64_t more, hipStream_t st) {
     const size_t ws_bytes = arx_grouper_consume_workspace_bytes(s->num_groups);
     void *ws = nullptr, *ids = nullptr;
     ARROW_RETURN_NOT_OK(t_scratch.Get(kWs, ws_bytes + 256, &ws));
-    ws = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
+    ws = Align256(ws);
     ARROW_RETURN_NOT_OK(t_scratch.Get(kArg2, static_cast<size_t>(s->num_groups) * 4 + 64, &ids));
     ARROW_RETURN_NOT_OK(FromArx(arx_grouper_consume(fresh, fresh_max, &sp, &w, 1, ws, ws_bytes, static_cast<uint32_t*>(ids), st)));
   }
-  s->table_buf = std::move(fresh_buf);
+  s->table_buf = std::move(fresh_table.buffer);
   s->table = fresh;
   s->max_groups = fresh_max;
   return Status::OK();
@@ -116,7 +112,7 @@ Status HashVectorExec(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::Exe
   const size_t ws_bytes = arx_grouper_consume_workspace_bytes(n);
   void *ws = nullptr, *ids = nullptr;
   ARROW_RETURN_NOT_OK(t_scratch.Get(kWs, ws_bytes + 256, &ws));
-  ws = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~uintptr_t(255));
+  ws = Align256(ws);
   if (KIND == kHashDictEncode) {
     ids = reinterpret_cast<void*>(out_arr->buffers[1]->mutable_address());
   } else {
