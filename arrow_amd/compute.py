@@ -86,6 +86,14 @@ class ScalarAggregateOptions(FunctionOptions):
         self.min_count = int(min_count)
 
 
+class MatchSubstringOptions(FunctionOptions):
+    """api_scalar.h MatchSubstringOptions: the literal `pattern` (str, UTF-8 encoded, or bytes) and ignore_case."""
+
+    def __init__(self, pattern="", ignore_case: bool = False):
+        self.pattern = pattern
+        self.ignore_case = bool(ignore_case)
+
+
 # --------------------------------------------------------------------------- scratch space
 _tls = threading.local()
 
@@ -1014,6 +1022,11 @@ def _build_registry() -> FunctionRegistry:
     f.add_kernel(Kernel((bool_,), _exec_array_sort_indices_bool, uint64))
     reg.add_function(f)
     reg.add_function(Function("sort_indices", Function.META, 1, SortOptions(), _sort_indices_meta))
+
+    for name in _MATCH_OPS:
+        f = Function(name, Function.SCALAR, 1, MatchSubstringOptions())
+        f.add_kernel(Kernel((_BASE_BINARY,), _exec_match_substring(name), bool_))
+        reg.add_function(f)
 
     f = Function("hash_sum", Function.HASH_AGGREGATE, 2, ScalarAggregateOptions())
     f.add_kernel(HashAggregateKernel((int64, uint32), _hash_sum_init, _hash_sum_resize,
@@ -2312,6 +2325,88 @@ def index_in(values: Array, value_set, *, skip_nulls: bool = False) -> Array:
     """compute::IndexIn (scalar_set_lookup.cc): int32, the index of the row's value's first occurrence in `value_set`
     (chunks counted one after the other), null where the value is absent.  The result stays on the device."""
     return _set_lookup(values, value_set, skip_nulls, True)
+
+
+# --------------------------------------------------------------------------- substring predicates
+# match_substring / starts_with / ends_with with a literal pattern (compute/kernels/scalar_string_ascii.cc, MatchSubstring
+# under MatchSubstringOptions{pattern, ignore_case}): csrc/match_substring.hip.  The `path` handed to
+# arx_match_substring: 0 = the library chooses (rows, or bytes from a mean row size on), 1 = one lane per row, 2 = the
+# lanes walk the bytes (match_substring only).  Tests set it to reach either kernel.
+MATCH_SUBSTRING_PATH = 0
+_MATCH_OPS = {"match_substring": 0, "starts_with": 1, "ends_with": 2}
+
+
+def _exec_match_substring(name: str):
+    def run(args, options):
+        return _match_substring(name, args[0], options.pattern, options.ignore_case)
+    return run
+
+
+def _call_match_substring(name: str, values, pattern, ignore_case: bool) -> Array:
+    import pyarrow as pa
+    import pyarrow.compute as pc
+
+    if not isinstance(values, Array):
+        raise TypeError(f"{name}: values must be an arrow_amd.Array")
+    if not is_base_binary(values.type):
+        # the reference's own "has no kernel matching input types" error, from a zero-length call
+        getattr(pc, name)(pa.array([], _pa_type(values.type)), "")
+    return call_function(name, [values], MatchSubstringOptions(pattern, ignore_case))
+
+
+def _match_substring(name: str, values: Array, pattern, ignore_case: bool) -> Array:
+    if isinstance(pattern, str):
+        pattern = pattern.encode("utf-8")
+    elif not isinstance(pattern, (bytes, bytearray, memoryview)):
+        raise TypeError(f"{name}: pattern must be str or bytes, not {type(pattern).__name__}")
+    pattern = bytes(pattern)
+    if ignore_case:
+        raise ArrowNotImplementedError(f"arrow_amd: {name} with ignore_case=True on device-resident arrays")
+    dev = values.device
+    lib, stream = _lib_and_stream(dev)
+    n = values.length
+    words = alloc(max(1, (n + 63) // 64) * 8, dev)
+    m = len(pattern)
+    dpat = alloc(max(m, 1), dev)
+    if m:
+        dpat[:m].copy_(torch.frombuffer(bytearray(pattern), dtype=torch.uint8))
+    vspan = values.binary_span()
+    hint = int(values.buffers[2].numel()) if values.buffers[2] is not None else -1
+    check(lib.arx_match_substring(C.byref(vspan), 4, _MATCH_OPS[name], dpat.data_ptr(), m, hint, int(MATCH_SUBSTRING_PATH),
+                                  words.data_ptr(), stream))
+    # (dpat is dropped on return while the kernel may still be queued: torch's caching allocator hands a freed block out
+    # again only to work queued behind this call on the same stream)
+    if values.validity is None:
+        return Array(bool_, n, [None, words], 0, 0)
+    valid = alloc(bitmap_nbytes(n), dev)
+    check(lib.arx_bitmap_copy(values.validity.data_ptr(), values.offset, n, valid.data_ptr(), stream))
+    known = values._null_count
+    out = Array(bool_, n, [valid, words], kUnknownNullCount, 0)
+    if not callable(known) and known != kUnknownNullCount:
+        out._null_count = int(known)
+    else:
+        nbytes = (n + 7) // 8
+        out.set_lazy_null_count(
+            lambda: n - int(np.unpackbits(valid[:nbytes].cpu().numpy(), bitorder="little")[:n].sum()) if n else 0)
+    return out
+
+
+def match_substring(values: Array, pattern, *, ignore_case: bool = False) -> Array:
+    """compute::MatchSubstring (scalar_string_ascii.cc): a boolean array, true where the row contains `pattern` (str,
+    UTF-8 encoded, or bytes) as a run of bytes; null where the row is null.  The empty pattern matches every valid row.
+    utf8 / binary values; ignore_case=True raises ArrowNotImplementedError (there is no CPU fallback).  The result stays
+    on the device."""
+    return _call_match_substring("match_substring", values, pattern, ignore_case)
+
+
+def starts_with(values: Array, pattern, *, ignore_case: bool = False) -> Array:
+    """compute::StartsWith: true where the row's first bytes are `pattern`.  See match_substring."""
+    return _call_match_substring("starts_with", values, pattern, ignore_case)
+
+
+def ends_with(values: Array, pattern, *, ignore_case: bool = False) -> Array:
+    """compute::EndsWith: true where the row's last bytes are `pattern`.  See match_substring."""
+    return _call_match_substring("ends_with", values, pattern, ignore_case)
 
 
 # --------------------------------------------------------------------------- hash join

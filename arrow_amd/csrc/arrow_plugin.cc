@@ -95,6 +95,7 @@ namespace {
 #include "plugin/hash_aggregate_bool.inc"
 #include "plugin/vector_hash.inc"
 #include "plugin/set_lookup.inc"
+#include "plugin/match_substring.inc"
 #include "plugin/scalar_aggregate.inc"
 #include "plugin/coalesce.inc"
 #include "plugin/grouper_chain.inc"

@@ -83,6 +83,7 @@ CounterTable groupby_counters();
 CounterTable groupby_lines_counters();
 CounterTable sort_counters();
 CounterTable set_lookup_counters();
+CounterTable match_substring_counters();
 
 #define ARX_HIP(call)                                          \
   do {                                                         \

@@ -1,0 +1,175 @@
+// match_substring / starts_with / ends_with on device-resident arrays (csrc/match_substring.hip).
+// Part of the Arrow registration shim: included by ../arrow_plugin.cc inside its anonymous
+// namespace (one translation unit; the split is for reading, not for linkage).
+// ---------------------------------------------------------------- substring predicates
+// The reference's kernels (kernels/scalar_string_ascii.cc: MatchSubstring with the Plain*Matcher of each function) keep
+// MatchSubstringOptions in their state.  The added kernels — one per type: utf8, binary, large_utf8, large_binary — run
+// the reference's init first, so its state serves host batches and its option errors stay its own, and keep a copy of
+// the options.  The pattern goes to the device on the first device-resident batch (an init cannot know where the
+// batches will live), once per kernel state: an Acero filter reuses it for every batch.  Outputs stay in HBM: the bitmap
+// of matches, and the input's validity copied to offset 0.  ignore_case has no device kernel: a Status, not a CPU read
+// of device memory.  Host batches run the reference's exec on buffers allocated here (the reference's kernels are
+// INTERSECTION / PREALLOCATE: the executor would have handed them the input's validity and a values bitmap).
+struct MatchSubstringKernelData : public cp::KernelState {
+  int op = ARX_MATCH_SUBSTRING;   // ARX_MATCH_*; also the index into g_stock_match_substring
+  Fn fn = kFnMatchSubstring;
+};
+// the reference's kernels of match_substring [0] / starts_with [1] / ends_with [2] as registered before the shim's
+std::vector<cp::ScalarKernel> g_stock_match_substring[3];
+
+struct DeviceMatchSubstringState : public cp::KernelState {
+  std::unique_ptr<cp::KernelState> stock;
+  cp::ArrayKernelExec stock_exec = nullptr;
+  cp::MatchSubstringOptions options;
+  std::mutex mu;
+  bool uploaded = false;
+  std::shared_ptr<Buffer> pattern;   // options.pattern on the device
+};
+
+const MatchSubstringKernelData* MatchSubstringDataOf(const cp::Kernel* k) {
+  return k != nullptr ? dynamic_cast<const MatchSubstringKernelData*>(k->data.get()) : nullptr;
+}
+
+arrow::Result<std::unique_ptr<cp::KernelState>> MatchSubstringInit(cp::KernelContext* ctx, const cp::KernelInitArgs& args) {
+  const MatchSubstringKernelData* data = MatchSubstringDataOf(args.kernel);
+  if (data == nullptr) return Status::Invalid("arrow_amd: substring kernel without its data");
+  auto state = std::make_unique<DeviceMatchSubstringState>();
+  const cp::ScalarKernel* stock = nullptr;
+  for (const cp::ScalarKernel& k : g_stock_match_substring[data->op]) {
+    if (k.signature->MatchesInputs(args.inputs)) stock = &k;   // (the last match, as DispatchExact picks)
+  }
+  if (stock == nullptr || !stock->init) {
+    return Status::Invalid("arrow_amd: no reference ", kFnNames[data->fn], " kernel for ", args.inputs[0].ToString());
+  }
+  state->stock_exec = stock->exec;
+  ARROW_ASSIGN_OR_RAISE(state->stock, stock->init(ctx, args));   // the reference's state and its option checks
+  if (args.options == nullptr) return Status::Invalid("arrow_amd: ", kFnNames[data->fn], " without MatchSubstringOptions");
+  state->options = *static_cast<const cp::MatchSubstringOptions*>(args.options);
+  return state;
+}
+
+// a host batch (or a scalar): the reference's exec on the buffers the executor would have preallocated for it
+Status MatchSubstringStock(cp::KernelContext* ctx, const MatchSubstringKernelData& kd, DeviceMatchSubstringState* s,
+                           const cp::ExecSpan& batch, cp::ExecResult* out) {
+  const int64_t n = batch.length;
+  ArrayData* out_arr = out->array_data().get();
+  ARROW_ASSIGN_OR_RAISE(std::shared_ptr<Buffer> data, ctx->AllocateBitmap(n));
+  std::memset(data->mutable_data(), 0, static_cast<size_t>(data->size()));
+  std::shared_ptr<Buffer> validity;
+  int64_t nulls = 0;
+  if (batch[0].is_array()) {
+    const ArraySpan& in = batch[0].array;
+    if (in.MayHaveNulls()) {
+      ARROW_ASSIGN_OR_RAISE(validity, ctx->AllocateBitmap(n));
+      arrow::internal::CopyBitmap(in.buffers[0].data, in.offset, n, validity->mutable_data(), 0);
+      nulls = in.GetNullCount();
+    }
+  } else if (!batch[0].scalar->is_valid) {
+    ARROW_ASSIGN_OR_RAISE(validity, ctx->AllocateBitmap(n));
+    std::memset(validity->mutable_data(), 0, static_cast<size_t>(validity->size()));
+    nulls = n;
+  }
+  cp::ExecResult tmp;
+  ArraySpan span;
+  span.type = out_arr->type.get();
+  span.length = n;
+  span.offset = 0;
+  span.null_count = nulls;
+  if (validity != nullptr) {
+    span.buffers[0].data = validity->mutable_data();
+    span.buffers[0].size = validity->size();
+  }
+  span.buffers[1].data = data->mutable_data();
+  span.buffers[1].size = data->size();
+  tmp.value = std::move(span);
+  CountStock(kd.fn);
+  cp::KernelState* mine = ctx->state();
+  ctx->SetState(s->stock.get());
+  const Status status = s->stock_exec(ctx, batch, &tmp);
+  ctx->SetState(mine);
+  ARROW_RETURN_NOT_OK(status);
+  out_arr->buffers = {validity, data};
+  out_arr->null_count = nulls;
+  return Status::OK();
+}
+
+Status MatchSubstringExec(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecResult* out) {
+  const MatchSubstringKernelData* kd = MatchSubstringDataOf(ctx->kernel());
+  auto* s = static_cast<DeviceMatchSubstringState*>(ctx->state());
+  if (kd == nullptr || s == nullptr) return Status::Invalid("arrow_amd: substring kernel ran without its data or state");
+  if (!batch[0].is_array() || !SpanTouchesRocm(batch[0].array)) return MatchSubstringStock(ctx, *kd, s, batch, out);
+  if (s->options.ignore_case) {
+    return Status::NotImplemented("arrow_amd: ", kFnNames[kd->fn], " with ignore_case on device-resident arrays");
+  }
+  hipStream_t st;
+  ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
+  const int64_t m = static_cast<int64_t>(s->options.pattern.size());
+  {
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (!s->uploaded) {
+      ARROW_ASSIGN_OR_RAISE(s->pattern, AllocDevice(std::max<int64_t>(m, 1)));
+      if (m > 0) {
+        HIP_RETURN_NOT_OK(hipMemcpyAsync(reinterpret_cast<void*>(s->pattern->mutable_address()), s->options.pattern.data(),
+                                         static_cast<size_t>(m), hipMemcpyHostToDevice, st));
+        HIP_RETURN_NOT_OK(hipStreamSynchronize(st));   // (other threads' streams read it next)
+      }
+      s->uploaded = true;
+    }
+  }
+  const ArraySpan& rows = batch[0].array;
+  const int64_t n = rows.length;
+  const Type::type id = rows.type->id();
+  const int offset_width = (id == Type::LARGE_STRING || id == Type::LARGE_BINARY) ? 8 : 4;
+  ArxBinarySpan vs{};
+  ARROW_RETURN_NOT_OK(DeviceBinarySpan(rows, &vs));
+  ArrayData* out_arr = out->array_data().get();
+  out_arr->buffers.assign(2, nullptr);
+  ARROW_ASSIGN_OR_RAISE(auto bits, AllocDevice(((n + 63) / 64) * 8 + 8));
+  ARROW_RETURN_NOT_OK(FromArx(arx_match_substring(&vs, offset_width, kd->op, reinterpret_cast<const void*>(s->pattern->address()), m,
+                                                  rows.buffers[2].size, ARX_MATCH_PATH_AUTO,
+                                                  reinterpret_cast<void*>(bits->mutable_address()), st)));
+  out_arr->buffers[1] = bits;
+  out_arr->null_count = 0;
+  if (vs.validity != nullptr && vs.null_count != 0) {
+    ARROW_ASSIGN_OR_RAISE(auto valid, AllocDevice(((n + 63) / 64) * 8 + 8));
+    ARROW_RETURN_NOT_OK(FromArx(arx_bitmap_copy(vs.validity, vs.offset, n, reinterpret_cast<void*>(valid->mutable_address()), st)));
+    if (vs.null_count > 0) {
+      out_arr->null_count = vs.null_count;
+    } else {
+      ARROW_ASSIGN_OR_RAISE(out_arr->null_count, DeviceNullCount(*valid, n, st));
+    }
+    if (out_arr->null_count != 0) out_arr->buffers[0] = valid;
+  }
+  HIP_RETURN_NOT_OK(hipStreamSynchronize(st));   // (this thread's scratch may be released after return)
+  CountGpu(kd->fn);
+  return Status::OK();
+}
+
+// the added kernels: one per type, appended after the reference's (dispatch takes the last match); the reference's own
+// kernels stay behind the device guard (plugin/device_guard.inc)
+Status RegisterMatchSubstring(cp::FunctionRegistry* reg, const char* name, int op, Fn fn_id) {
+  ARROW_ASSIGN_OR_RAISE(auto fn, reg->GetFunction(name));
+  if (fn->kind() != cp::Function::SCALAR) return Status::Invalid(name, " is not a scalar function");
+  auto* sfn = static_cast<cp::ScalarFunction*>(fn.get());
+  auto& stock = g_stock_match_substring[op];
+  stock.clear();
+  for (const cp::ScalarKernel* k : sfn->kernels()) stock.push_back(*k);
+  for (const auto& type : {arrow::utf8(), arrow::binary(), arrow::large_utf8(), arrow::large_binary()}) {
+    ARROW_ASSIGN_OR_RAISE(const cp::Kernel* k0, sfn->DispatchExact({type}));
+    cp::ScalarKernel copy = *static_cast<const cp::ScalarKernel*>(k0);
+    if (copy.data != nullptr || !copy.init) {
+      return Status::Invalid("arrow_amd: the reference's ", name, " kernel of ", type->ToString(), " is not of the expected shape");
+    }
+    auto data = std::make_shared<MatchSubstringKernelData>();
+    data->op = op;
+    data->fn = fn_id;
+    copy.data = std::move(data);
+    copy.signature = cp::KernelSignature::Make({cp::InputType(type)}, copy.signature->out_type());
+    copy.init = MatchSubstringInit;
+    copy.exec = MatchSubstringExec;
+    copy.null_handling = cp::NullHandling::COMPUTED_NO_PREALLOCATE;
+    copy.mem_allocation = cp::MemAllocation::NO_PREALLOCATE;
+    ARROW_RETURN_NOT_OK(sfn->AddKernel(std::move(copy)));
+  }
+  return Status::OK();
+}

@@ -345,6 +345,10 @@ Status RegisterAll() {
   // is_in / index_in against a device hash table of the value set (plugin/set_lookup.inc)
   ARROW_RETURN_NOT_OK(RegisterSetLookup(reg, "is_in", false));
   ARROW_RETURN_NOT_OK(RegisterSetLookup(reg, "index_in", true));
+  // match_substring / starts_with / ends_with with a literal pattern on utf8 / binary columns (plugin/match_substring.inc)
+  ARROW_RETURN_NOT_OK(RegisterMatchSubstring(reg, "match_substring", ARX_MATCH_SUBSTRING, kFnMatchSubstring));
+  ARROW_RETURN_NOT_OK(RegisterMatchSubstring(reg, "starts_with", ARX_MATCH_STARTS_WITH, kFnStartsWith));
+  ARROW_RETURN_NOT_OK(RegisterMatchSubstring(reg, "ends_with", ARX_MATCH_ENDS_WITH, kFnEndsWith));
   // the reference's kernels of the functions extended above refuse device-resident arrays instead of reading them
   ARROW_RETURN_NOT_OK(InstallDeviceGuards(reg, stock_kernel_counts));
   ARROW_RETURN_NOT_OK(RefreshMinMaxKernels(reg));   // (the guards re-added kernels: pointers into min_max's list moved)

@@ -1243,6 +1243,36 @@ int arx_set_lookup_index_in_binary(const void* state, const ArxBinarySpan* value
                                    const ArxBinarySpan* values, int offset_width, int skip_nulls, int32_t* out_index,
                                    void* out_validity, void* stream);
 
+/* Substring predicates — match_substring / starts_with / ends_with with a literal pattern (MatchSubstring with
+ * PlainSubstringMatcher / PlainStartsWithMatcher / PlainEndsWithMatcher, compute/kernels/scalar_string_ascii.cc;
+ * MatchSubstringOptions::ignore_case = false).  Bytes compare as bytes (no UTF-8 awareness, a '\0' is an ordinary byte);
+ * the empty pattern matches every valid row; a pattern longer than the row never matches.
+ * values: utf8 / binary (offset_width 4) or large_utf8 / large_binary (offset_width 8), any offset.  pattern: a DEVICE
+ * pointer to pattern_length >= 0 bytes, alive until the stream reaches the call's end.
+ * out_bits: ceil(length / 64) 64-bit words at offset 0; bit i = row i matches; the bit of a null row is 0.  The result's
+ * validity is the input's: the caller copies it (arx_bitmap_copy).
+ * path: ARX_MATCH_PATH_ROWS = one lane per row (the only path of starts_with / ends_with and of the empty pattern),
+ * ARX_MATCH_PATH_BYTES = the lanes walk the bytes of data[offsets[0], offsets[length]) and hits are resolved to their
+ * rows (match_substring only; for columns of long or skewed rows), ARX_MATCH_PATH_AUTO = bytes when
+ * data_bytes_hint / length reaches a fixed threshold.  data_bytes_hint: the size of the values' data buffer (an upper
+ * bound of the referenced bytes) or -1 if unknown (auto then takes rows); only used to choose a path and a grid.
+ * A load touches only aligned 16-byte granules that hold at least one referenced byte.
+ * ARX_INVALID for an op, path or offset_width outside the above, a negative length and NULL values / out_bits;
+ * length == 0 succeeds and writes nothing.  Asynchronous; no read-back.
+ * arx_get_counter("match_substring_row_launches" / "match_substring_byte_launches") counts the launches of each path. */
+enum {
+  ARX_MATCH_SUBSTRING = 0,
+  ARX_MATCH_STARTS_WITH = 1,
+  ARX_MATCH_ENDS_WITH = 2
+};
+enum {
+  ARX_MATCH_PATH_AUTO = 0,
+  ARX_MATCH_PATH_ROWS = 1,
+  ARX_MATCH_PATH_BYTES = 2
+};
+int arx_match_substring(const ArxBinarySpan* values, int offset_width, int op, const void* pattern, int64_t pattern_length,
+                        int64_t data_bytes_hint, int path, void* out_bits, void* stream);
+
 /* Hash join — the equi-join of HashJoinNode (acero/hash_join_node.cc; SwissJoin, acero/swiss_join.cc) after the Grouper:
  * the right (build) input's key rows are consumed (arx_grouper_consume: dense uint32 ids, G groups), the left (probe)
  * input's are looked up (arx_grouper_lookup: an id or null).  Under JoinKeyCmp::EQ a null in any key column matches
