@@ -1028,6 +1028,11 @@ def _build_registry() -> FunctionRegistry:
         f.add_kernel(Kernel((_BASE_BINARY,), _exec_match_substring(name), bool_))
         reg.add_function(f)
 
+    # if_else(cond, left, right): left / right of ONE type, boolean or 1 / 2 / 4 / 8 bytes wide (csrc/if_else.hip)
+    f = Function("if_else", Function.SCALAR, 3)
+    f.add_kernel(Kernel((bool_, _IF_ELSE_VALUE, _IF_ELSE_VALUE), _exec_if_else))
+    reg.add_function(f)
+
     f = Function("hash_sum", Function.HASH_AGGREGATE, 2, ScalarAggregateOptions())
     f.add_kernel(HashAggregateKernel((int64, uint32), _hash_sum_init, _hash_sum_resize,
                                      _hash_sum_consume, _hash_sum_merge, _hash_sum_finalize, int64))
@@ -2407,6 +2412,77 @@ def starts_with(values: Array, pattern, *, ignore_case: bool = False) -> Array:
 def ends_with(values: Array, pattern, *, ignore_case: bool = False) -> Array:
     """compute::EndsWith: true where the row's last bytes are `pattern`.  See match_substring."""
     return _call_match_substring("ends_with", values, pattern, ignore_case)
+
+
+# --------------------------------------------------------------------------- if_else
+# if_else(cond, left, right) (compute/kernels/scalar_if_else.cc, IfElseFunctor): csrc/if_else.hip.  The reference's
+# DispatchBest casts the operands to a common type; the mirror has no implicit casts: both sides are of one type.
+_IF_ELSE_VALUE = lambda t: t == bool_ or (t.np_dtype is not None and t.byte_width in (1, 2, 4, 8))  # noqa: E731
+
+
+def _exec_if_else(args, options):
+    cond, left, right = args
+    if not isinstance(cond, Array):
+        raise ArrowNotImplementedError("arrow_amd: if_else with a scalar cond on device-resident arrays")
+    t = left.type
+    if right.type != t:
+        raise ArrowNotImplementedError(f"if_else: left is {t.name}, right is {right.type.name}; the device kernel takes both sides "
+                                       "of one type (no implicit casts)")
+    n = cond.length
+    if any(isinstance(a, Array) and a.length != n for a in (left, right)):
+        raise ArrowInvalid("Array arguments must all be the same length")
+    dev = cond.device
+    lib, stream = _lib_and_stream(dev)
+    width = 0 if t == bool_ else t.byte_width
+    keep = []
+
+    def operand(x):
+        """(span pointer | None, host scalar pointer | None) as arx_if_else takes an operand."""
+        if isinstance(x, Array):
+            keep.append(x.span())
+            return C.byref(keep[-1]), None
+        if not x.is_valid:
+            return None, None
+        holder = np.zeros(1, dtype=np.uint8 if width == 0 else t.np_dtype)
+        holder[0] = bool(x.value) if width == 0 else t.np_dtype.type(x.value)
+        keep.append(holder)
+        return None, holder.ctypes.data
+
+    null_scalars = [isinstance(a, Scalar) and not a.is_valid for a in (left, right)]
+    nulls = any(null_scalars) or any(isinstance(a, Array) and a.may_have_nulls() for a in args)
+    out = alloc(bitmap_nbytes(n) if width == 0 else n * width, dev)
+    valid = alloc(bitmap_nbytes(n), dev) if nulls else None
+    cspan = cond.span()
+    (lspan, lsc), (rspan, rsc) = operand(left), operand(right)
+    with tracing.span("arx_if_else"):
+        check(lib.arx_if_else(width, C.byref(cspan), lspan, lsc, rspan, rsc, n, out.data_ptr(), _ptr_or_none(valid), stream))
+    if not nulls:
+        return Array(t, n, [None, out], 0, 0)
+    res = Array(t, n, [valid, out], kUnknownNullCount, 0)
+    if all(null_scalars):
+        res._null_count = n
+    else:
+        nbytes = (n + 7) // 8
+        res.set_lazy_null_count(
+            lambda: n - int(np.unpackbits(valid[:nbytes].cpu().numpy(), bitorder="little")[:n].sum()) if n else 0)
+    return res
+
+
+def if_else(cond: Array, left, right) -> Array:
+    """compute::IfElse (scalar_if_else.cc): out[i] = left[i] where cond[i] is true, right[i] where it is false, null where
+    cond is null; a slot takes the validity of the side it comes from.  cond: a boolean Array.  left / right: an Array, an
+    arrow_amd.Scalar, a Python number or bool (it takes the other side's type) or None (a null scalar); both of one type —
+    boolean or 1 / 2 / 4 / 8 bytes wide, temporal types included — since the mirror casts nothing implicitly.  The result
+    stays on the device and has no validity buffer when no operand can be null."""
+    if not isinstance(cond, Array) or cond.type != bool_:
+        got = cond.type.name if isinstance(cond, (Array, Scalar)) else type(cond).__name__
+        raise ArrowNotImplementedError(f"if_else: cond must be a boolean arrow_amd.Array, not {got}")
+    typed = [x.type for x in (left, right) if isinstance(x, (Array, Scalar))]
+    if not typed:
+        raise ArrowNotImplementedError(f"if_else: neither left ({left!r}) nor right ({right!r}) carries a type; pass an Array or an "
+                                       "arrow_amd.Scalar on one side")
+    wrap = lambda x: x if isinstance(x, (Array, Scalar)) else Scalar(x, typed[0], x is not None)  # noqa: E731
+    return call_function("if_else", [cond, wrap(left), wrap(right)])
 
 
 # --------------------------------------------------------------------------- hash join

@@ -84,6 +84,7 @@ CounterTable groupby_lines_counters();
 CounterTable sort_counters();
 CounterTable set_lookup_counters();
 CounterTable match_substring_counters();
+CounterTable if_else_counters();
 
 #define ARX_HIP(call)                                          \
   do {                                                         \

@@ -232,7 +232,7 @@ const char* const kGuardedFunctions[] = {
     "and_kleene", "or_kleene", "invert", "unique", "value_counts", "dictionary_encode", "indices_nonzero",
     "sum", "mean", "min_max", "min", "max", "coalesce", "is_in", "index_in", "match_substring", "starts_with", "ends_with",
     "match_like", "match_substring_regex", "find_substring", "find_substring_regex", "count_substring",
-    "count_substring_regex"};
+    "count_substring_regex", "if_else"};
 
 // before the shim registers anything: how many kernels of each guarded function are the reference's
 arrow::Result<std::vector<int>> CountStockKernels(cp::FunctionRegistry* reg) {

@@ -1272,6 +1272,22 @@ enum {
 };
 int arx_match_substring(const ArxBinarySpan* values, int offset_width, int op, const void* pattern, int64_t pattern_length,
                         int64_t data_bytes_hint, int path, void* out_bits, void* stream);
+/* if_else(cond, left, right) of ONE fixed-width type or boolean (IfElseFunctor, compute/kernels/scalar_if_else.cc; csrc/if_else.hip):
+ * out[i] = cond[i] ? left[i] : right[i]; out is null where cond is null (whatever its data bit says), else it takes the
+ * validity of the chosen operand: valid = cv & ((c & lv) | (~c & rv)), booleans data = (c & l) | (~c & r).
+ * byte_width 1 / 2 / 4 / 8 / 16, or 0 for booleans (bitmaps).  cond: a boolean array (data = bitmap, offset = bit offset).
+ * left / right, each one of three forms as in arx_coalesce2: an array (span != NULL, scalar == NULL), a valid scalar
+ * (span == NULL, scalar -> byte_width host bytes; booleans: one byte 0 / 1), a null scalar (both NULL); every operand
+ * carries its own offset.  The output starts at offset 0; a null result slot is written as zero.
+ * out_validity: ceil(length / 64) whole words; it may be NULL exactly when no operand has a bitmap (validity != NULL and
+ * null_count != 0) and no scalar is null — the result then has no nulls and no bitmap is written.  Nothing is written past
+ * length * byte_width data bytes (booleans: past the last data word) or past the last validity word.
+ * ARX_INVALID for a byte_width outside the above, a negative length, a span whose length is not `length`, a NULL cond /
+ * out_data and a NULL out_validity that is required; length == 0 succeeds, launches nothing and writes nothing.
+ * Asynchronous; no read-back.  arx_get_counter("if_else_launches" / "if_else_packed_launches" / "if_else_bool_launches")
+ * counts the launches of the kernel of widths 8 and 16, of widths 1, 2 and 4 (8 / width rows a lane) and of booleans. */
+int arx_if_else(int byte_width, const ArxSpan* cond, const ArxSpan* left, const void* left_scalar, const ArxSpan* right,
+                const void* right_scalar, int64_t length, void* out_data, void* out_validity, void* stream);
 
 /* Hash join — the equi-join of HashJoinNode (acero/hash_join_node.cc; SwissJoin, acero/swiss_join.cc) after the Grouper:
  * the right (build) input's key rows are consumed (arx_grouper_consume: dense uint32 ids, G groups), the left (probe)
