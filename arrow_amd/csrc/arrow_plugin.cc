@@ -64,6 +64,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <set>
 #include <string>
 #include <thread>
@@ -87,6 +88,7 @@ namespace {
 #include "plugin/selection_nested.inc"
 #include "plugin/selection_meta.inc"
 #include "plugin/acero_common.inc"
+#include "plugin/twin.inc"
 #include "plugin/scalar.inc"
 #include "plugin/sort.inc"
 #include "plugin/cast.inc"

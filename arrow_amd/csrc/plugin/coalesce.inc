@@ -33,19 +33,12 @@ Status CoalesceExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::Exe
       ARROW_RETURN_NOT_OK(DeviceSpan(batch[1].array, &b));
       fill = &b;
     } else if (batch[1].scalar->is_valid) {
-      const arrow::Scalar& sc = *batch[1].scalar;
-      if (width == 0) {
-        scalar_bits = static_cast<const arrow::BooleanScalar&>(sc).value ? 1 : 0;
-      } else {
-        const auto bytes = static_cast<const arrow::internal::PrimitiveScalarBase&>(sc).view();
-        if (static_cast<int>(bytes.size()) != width) return Status::Invalid("arrow_amd: coalesce: a fill scalar of ", bytes.size(), " bytes for ", type.ToString());
-        std::memcpy(&scalar_bits, bytes.data(), static_cast<size_t>(width));
-      }
+      const int64_t got = FixedWidthScalarBytes(*batch[1].scalar, width, &scalar_bits);
+      if (got != width) return Status::Invalid("arrow_amd: coalesce: a fill scalar of ", got, " bytes for ", type.ToString());
       fill_scalar = &scalar_bits;
     }
-    const int64_t words = (n + 63) / 64;
-    ARROW_ASSIGN_OR_RAISE(out_arr->buffers[1], AllocDevice(width == 0 ? words * 8 + 8 : std::max<int64_t>(n * width, 8)));
-    ARROW_ASSIGN_OR_RAISE(out_arr->buffers[0], AllocDevice(words * 8 + 8));
+    ARROW_ASSIGN_OR_RAISE(out_arr->buffers[1], AllocDevice(width == 0 ? BitmapBytes(n) : std::max<int64_t>(n * width, 8)));
+    ARROW_ASSIGN_OR_RAISE(out_arr->buffers[0], AllocDevice(BitmapBytes(n)));
     ARROW_RETURN_NOT_OK(FromArx(arx_coalesce2(width, &a, fill, fill_scalar, n, reinterpret_cast<void*>(out_arr->buffers[1]->mutable_address()),
                                               reinterpret_cast<void*>(out_arr->buffers[0]->mutable_address()), st)));
     const bool no_nulls = n == 0 || fill_scalar != nullptr || a.validity == nullptr || a.null_count == 0;
@@ -62,52 +55,18 @@ Status CoalesceExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::Exe
   // ---- host operands: the executor's preallocation, then the reference kernel
   const cp::ArrayKernelExec stock = g_stock_coalesce[type.id()];
   if (stock == nullptr) return Status::Invalid("arrow_amd: no reference coalesce kernel recorded for ", type.ToString());
-  std::shared_ptr<Buffer> data, validity;
-  if (width == 0) {
-    ARROW_ASSIGN_OR_RAISE(data, ctx->AllocateBitmap(n));
-  } else {
-    ARROW_ASSIGN_OR_RAISE(data, ctx->Allocate(n * width));
-  }
-  ARROW_ASSIGN_OR_RAISE(validity, ctx->AllocateBitmap(n));
-  cp::ExecResult tmp;
-  ArraySpan span;
-  span.type = out_arr->type.get();
-  span.length = n;
-  span.offset = 0;
-  span.null_count = arrow::kUnknownNullCount;
-  span.buffers[0].data = validity->mutable_data();
-  span.buffers[0].size = validity->size();
-  span.buffers[1].data = data->mutable_data();
-  span.buffers[1].size = data->size();
-  tmp.value = std::move(span);
-  CountStock(kFnCoalesce);
-  ARROW_RETURN_NOT_OK(stock(ctx, batch, &tmp));
-  out_arr->buffers[0] = std::move(validity);
-  out_arr->buffers[1] = std::move(data);
-  out_arr->null_count = arrow::kUnknownNullCount;
-  return Status::OK();
+  return RunStockPrepared(kFnCoalesce, stock, std::nullopt, width, TwinValidity::kAllocate, ctx, batch, out);
 }
 
 Status RegisterCoalesce(cp::FunctionRegistry* reg) {
-  ARROW_ASSIGN_OR_RAISE(auto fn, reg->GetFunction("coalesce"));
-  auto* sfn = static_cast<cp::ScalarFunction*>(fn.get());
-  const std::vector<std::shared_ptr<arrow::DataType>> types = {
-      arrow::boolean(), arrow::int8(), arrow::uint8(), arrow::int16(), arrow::uint16(), arrow::int32(), arrow::uint32(), arrow::int64(),
-      arrow::uint64(), arrow::float32(), arrow::float64(), arrow::date32(), arrow::date64(), arrow::time32(arrow::TimeUnit::SECOND),
-      arrow::time64(arrow::TimeUnit::MICRO), arrow::timestamp(arrow::TimeUnit::SECOND), arrow::duration(arrow::TimeUnit::SECOND)};
-  for (const auto& t : types) {
-    ARROW_ASSIGN_OR_RAISE(const cp::Kernel* k0, sfn->DispatchExact({t, t}));
-    cp::ScalarKernel copy = *static_cast<const cp::ScalarKernel*>(k0);
-    if (copy.data != nullptr) continue;   // (none of the reference's coalesce kernels carries data)
-    g_stock_coalesce[t->id()] = copy.exec;
-    const bool parametric = arrow::is_temporal(t->id()) || t->id() == Type::DURATION;   // (unit / time zone: matched by id)
-    const cp::InputType in = parametric ? cp::InputType(t->id()) : cp::InputType(t);
-    copy.signature = cp::KernelSignature::Make({in}, copy.signature->out_type(), /*is_varargs=*/true);
-    copy.exec = CoalesceExecNP;
-    copy.null_handling = cp::NullHandling::COMPUTED_NO_PREALLOCATE;
-    copy.mem_allocation = cp::MemAllocation::NO_PREALLOCATE;
-    copy.can_write_into_slices = false;
-    ARROW_RETURN_NOT_OK(sfn->AddKernel(std::move(copy)));
-  }
-  return Status::OK();
+  return AppendTwins(reg, "coalesce", FixedWidthTwinTypes(/*with_decimal128=*/false),
+                     [](const auto& t) { return std::vector<arrow::TypeHolder>{t, t}; },
+                     [](const ValueType& vt, cp::ScalarKernel* twin) -> arrow::Result<bool> {
+                       if (twin->data != nullptr) return false;   // (none of the reference's coalesce kernels carries data)
+                       g_stock_coalesce[vt.probe->id()] = twin->exec;
+                       twin->signature = cp::KernelSignature::Make({vt.match}, twin->signature->out_type(), /*is_varargs=*/true);
+                       twin->exec = CoalesceExecNP;
+                       twin->can_write_into_slices = false;
+                       return true;
+                     });
 }

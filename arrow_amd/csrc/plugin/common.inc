@@ -293,13 +293,20 @@ struct StockKernel {
   cp::VectorKernel::ChunkedExec exec_chunked = nullptr;
 };
 
-// run the stock exec with the stock state installed
-Status RunStock(Fn fn, const StockKernel& k, cp::KernelState* stock_state, cp::KernelContext* ctx,
-                const cp::ExecSpan& batch, cp::ExecResult* out) {
+// count and run a stock exec (an ArrayKernelExec or a ChunkedExec); a stock state, when given, is installed around the
+// call and ours restored whatever the call returns
+template <class Exec, class Batch, class Out>
+Status RunStock(Fn fn, Exec exec, std::optional<cp::KernelState*> stock_state, cp::KernelContext* ctx, const Batch& batch,
+                Out* out) {
   CountStock(fn);
+  if (!stock_state.has_value()) return exec(ctx, batch, out);
   cp::KernelState* mine = ctx->state();
-  ctx->SetState(stock_state);
-  Status st = k.exec(ctx, batch, out);
+  ctx->SetState(*stock_state);
+  Status st = exec(ctx, batch, out);
   ctx->SetState(mine);
   return st;
+}
+Status RunStock(Fn fn, const StockKernel& k, cp::KernelState* stock_state, cp::KernelContext* ctx,
+                const cp::ExecSpan& batch, cp::ExecResult* out) {
+  return RunStock(fn, k.exec, std::optional<cp::KernelState*>(stock_state), ctx, batch, out);
 }

@@ -22,15 +22,8 @@ Status IfElseOperand(const cp::ExecValue& v, int width, const arrow::DataType& t
     return Status::OK();
   }
   if (!v.scalar->is_valid) return Status::OK();
-  if (width == 0) {
-    scalar_bytes[0] = static_cast<const arrow::BooleanScalar&>(*v.scalar).value ? 1 : 0;
-  } else {
-    const auto bytes = static_cast<const arrow::internal::PrimitiveScalarBase&>(*v.scalar).view();
-    if (static_cast<int>(bytes.size()) != width) {
-      return Status::Invalid("arrow_amd: if_else: a scalar of ", bytes.size(), " bytes for ", type.ToString());
-    }
-    std::memcpy(scalar_bytes, bytes.data(), static_cast<size_t>(width));
-  }
+  const int64_t got = FixedWidthScalarBytes(*v.scalar, width, scalar_bytes);
+  if (got != width) return Status::Invalid("arrow_amd: if_else: a scalar of ", got, " bytes for ", type.ToString());
   *scalar = scalar_bytes;
   return Status::OK();
 }
@@ -65,11 +58,10 @@ Status IfElseExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecR
       ARROW_RETURN_NOT_OK(IfElseOperand(batch[1 + i], width, type, &storage[i], scalar_bytes[i], &span[i], &scalar[i]));
       may_have_nulls = may_have_nulls || (span[i] != nullptr ? (span[i]->validity != nullptr && span[i]->null_count != 0) : scalar[i] == nullptr);
     }
-    const int64_t words = (n + 63) / 64;
-    ARROW_ASSIGN_OR_RAISE(out_arr->buffers[1], AllocDevice(width == 0 ? words * 8 + 8 : std::max<int64_t>(n * width, 8)));
+    ARROW_ASSIGN_OR_RAISE(out_arr->buffers[1], AllocDevice(width == 0 ? BitmapBytes(n) : std::max<int64_t>(n * width, 8)));
     out_arr->buffers[0] = nullptr;
     if (may_have_nulls) {
-      ARROW_ASSIGN_OR_RAISE(out_arr->buffers[0], AllocDevice(words * 8 + 8));
+      ARROW_ASSIGN_OR_RAISE(out_arr->buffers[0], AllocDevice(BitmapBytes(n)));
     }
     ARROW_RETURN_NOT_OK(FromArx(arx_if_else(width, &c, span[0], scalar[0], span[1], scalar[1], n,
                                             reinterpret_cast<void*>(out_arr->buffers[1]->mutable_address()),
@@ -86,30 +78,7 @@ Status IfElseExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecR
   // ---- host operands: the executor's preallocation, then the reference kernel
   const cp::ArrayKernelExec stock = g_stock_if_else[type.id()];
   if (stock == nullptr) return Status::Invalid("arrow_amd: no reference if_else kernel recorded for ", type.ToString());
-  std::shared_ptr<Buffer> data, validity;
-  if (width == 0) {
-    ARROW_ASSIGN_OR_RAISE(data, ctx->AllocateBitmap(n));
-  } else {
-    ARROW_ASSIGN_OR_RAISE(data, ctx->Allocate(n * width));
-  }
-  ARROW_ASSIGN_OR_RAISE(validity, ctx->AllocateBitmap(n));
-  cp::ExecResult tmp;
-  ArraySpan span;
-  span.type = out_arr->type.get();
-  span.length = n;
-  span.offset = 0;
-  span.null_count = arrow::kUnknownNullCount;
-  span.buffers[0].data = validity->mutable_data();
-  span.buffers[0].size = validity->size();
-  span.buffers[1].data = data->mutable_data();
-  span.buffers[1].size = data->size();
-  tmp.value = std::move(span);
-  CountStock(kFnIfElse);
-  ARROW_RETURN_NOT_OK(stock(ctx, batch, &tmp));
-  out_arr->buffers[0] = std::move(validity);
-  out_arr->buffers[1] = std::move(data);
-  out_arr->null_count = arrow::kUnknownNullCount;
-  return Status::OK();
+  return RunStockPrepared(kFnIfElse, stock, std::nullopt, width, TwinValidity::kAllocate, ctx, batch, out);
 }
 
 // the result's type is the operands' (the reference's kernel of a probe type may state that very type: time32[s])
@@ -118,27 +87,15 @@ arrow::Result<arrow::TypeHolder> ResolveIfElseType(cp::KernelContext*, const std
 }
 
 Status RegisterIfElse(cp::FunctionRegistry* reg) {
-  ARROW_ASSIGN_OR_RAISE(auto fn, reg->GetFunction("if_else"));
-  auto* sfn = static_cast<cp::ScalarFunction*>(fn.get());
-  const std::vector<std::shared_ptr<arrow::DataType>> types = {
-      arrow::boolean(), arrow::int8(), arrow::uint8(), arrow::int16(), arrow::uint16(), arrow::int32(), arrow::uint32(), arrow::int64(),
-      arrow::uint64(), arrow::float32(), arrow::float64(), arrow::date32(), arrow::date64(), arrow::time32(arrow::TimeUnit::SECOND),
-      arrow::time64(arrow::TimeUnit::MICRO), arrow::timestamp(arrow::TimeUnit::SECOND), arrow::duration(arrow::TimeUnit::SECOND),
-      arrow::decimal128(38, 9)};
-  for (const auto& t : types) {
-    ARROW_ASSIGN_OR_RAISE(const cp::Kernel* k0, sfn->DispatchExact({arrow::boolean(), t, t}));
-    cp::ScalarKernel copy = *static_cast<const cp::ScalarKernel*>(k0);
-    if (copy.data != nullptr) continue;   // (none of the reference's if_else kernels carries data)
-    g_stock_if_else[t->id()] = copy.exec;
-    // (unit / time zone / precision and scale: matched by id)
-    const bool parametric = arrow::is_temporal(t->id()) || t->id() == Type::DURATION || t->id() == Type::DECIMAL128;
-    const cp::InputType in = parametric ? cp::InputType(t->id()) : cp::InputType(t);
-    copy.signature = cp::KernelSignature::Make({cp::InputType(arrow::boolean()), in, in}, cp::OutputType(ResolveIfElseType));
-    copy.exec = IfElseExecNP;
-    copy.null_handling = cp::NullHandling::COMPUTED_NO_PREALLOCATE;
-    copy.mem_allocation = cp::MemAllocation::NO_PREALLOCATE;
-    copy.can_write_into_slices = false;
-    ARROW_RETURN_NOT_OK(sfn->AddKernel(std::move(copy)));
-  }
-  return Status::OK();
+  return AppendTwins(reg, "if_else", FixedWidthTwinTypes(/*with_decimal128=*/true),
+                     [](const auto& t) { return std::vector<arrow::TypeHolder>{arrow::boolean(), t, t}; },
+                     [](const ValueType& vt, cp::ScalarKernel* twin) -> arrow::Result<bool> {
+                       if (twin->data != nullptr) return false;   // (none of the reference's if_else kernels carries data)
+                       g_stock_if_else[vt.probe->id()] = twin->exec;
+                       twin->signature = cp::KernelSignature::Make({cp::InputType(arrow::boolean()), vt.match, vt.match},
+                                                                   cp::OutputType(ResolveIfElseType));
+                       twin->exec = IfElseExecNP;
+                       twin->can_write_into_slices = false;
+                       return true;
+                     });
 }

@@ -51,45 +51,11 @@ arrow::Result<std::unique_ptr<cp::KernelState>> MatchSubstringInit(cp::KernelCon
 // a host batch (or a scalar): the reference's exec on the buffers the executor would have preallocated for it
 Status MatchSubstringStock(cp::KernelContext* ctx, const MatchSubstringKernelData& kd, DeviceMatchSubstringState* s,
                            const cp::ExecSpan& batch, cp::ExecResult* out) {
-  const int64_t n = batch.length;
+  ARROW_RETURN_NOT_OK(RunStockPrepared(kd.fn, s->stock_exec, s->stock.get(), 0, TwinValidity::kIntersection, ctx, batch, out));
   ArrayData* out_arr = out->array_data().get();
-  ARROW_ASSIGN_OR_RAISE(std::shared_ptr<Buffer> data, ctx->AllocateBitmap(n));
-  std::memset(data->mutable_data(), 0, static_cast<size_t>(data->size()));
-  std::shared_ptr<Buffer> validity;
-  int64_t nulls = 0;
-  if (batch[0].is_array()) {
-    const ArraySpan& in = batch[0].array;
-    if (in.MayHaveNulls()) {
-      ARROW_ASSIGN_OR_RAISE(validity, ctx->AllocateBitmap(n));
-      arrow::internal::CopyBitmap(in.buffers[0].data, in.offset, n, validity->mutable_data(), 0);
-      nulls = in.GetNullCount();
-    }
-  } else if (!batch[0].scalar->is_valid) {
-    ARROW_ASSIGN_OR_RAISE(validity, ctx->AllocateBitmap(n));
-    std::memset(validity->mutable_data(), 0, static_cast<size_t>(validity->size()));
-    nulls = n;
+  if (out_arr->null_count < 0) {   // (this twin reports an exact count)
+    out_arr->null_count = batch.length - arrow::internal::CountSetBits(out_arr->buffers[0]->data(), 0, batch.length);
   }
-  cp::ExecResult tmp;
-  ArraySpan span;
-  span.type = out_arr->type.get();
-  span.length = n;
-  span.offset = 0;
-  span.null_count = nulls;
-  if (validity != nullptr) {
-    span.buffers[0].data = validity->mutable_data();
-    span.buffers[0].size = validity->size();
-  }
-  span.buffers[1].data = data->mutable_data();
-  span.buffers[1].size = data->size();
-  tmp.value = std::move(span);
-  CountStock(kd.fn);
-  cp::KernelState* mine = ctx->state();
-  ctx->SetState(s->stock.get());
-  const Status status = s->stock_exec(ctx, batch, &tmp);
-  ctx->SetState(mine);
-  ARROW_RETURN_NOT_OK(status);
-  out_arr->buffers = {validity, data};
-  out_arr->null_count = nulls;
   return Status::OK();
 }
 
@@ -124,14 +90,14 @@ Status MatchSubstringExec(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp:
   ARROW_RETURN_NOT_OK(DeviceBinarySpan(rows, &vs));
   ArrayData* out_arr = out->array_data().get();
   out_arr->buffers.assign(2, nullptr);
-  ARROW_ASSIGN_OR_RAISE(auto bits, AllocDevice(((n + 63) / 64) * 8 + 8));
+  ARROW_ASSIGN_OR_RAISE(auto bits, AllocDevice(BitmapBytes(n)));
   ARROW_RETURN_NOT_OK(FromArx(arx_match_substring(&vs, offset_width, kd->op, reinterpret_cast<const void*>(s->pattern->address()), m,
                                                   rows.buffers[2].size, ARX_MATCH_PATH_AUTO,
                                                   reinterpret_cast<void*>(bits->mutable_address()), st)));
   out_arr->buffers[1] = bits;
   out_arr->null_count = 0;
   if (vs.validity != nullptr && vs.null_count != 0) {
-    ARROW_ASSIGN_OR_RAISE(auto valid, AllocDevice(((n + 63) / 64) * 8 + 8));
+    ARROW_ASSIGN_OR_RAISE(auto valid, AllocDevice(BitmapBytes(n)));
     ARROW_RETURN_NOT_OK(FromArx(arx_bitmap_copy(vs.validity, vs.offset, n, reinterpret_cast<void*>(valid->mutable_address()), st)));
     if (vs.null_count > 0) {
       out_arr->null_count = vs.null_count;
@@ -150,26 +116,23 @@ Status MatchSubstringExec(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp:
 Status RegisterMatchSubstring(cp::FunctionRegistry* reg, const char* name, int op, Fn fn_id) {
   ARROW_ASSIGN_OR_RAISE(auto fn, reg->GetFunction(name));
   if (fn->kind() != cp::Function::SCALAR) return Status::Invalid(name, " is not a scalar function");
-  auto* sfn = static_cast<cp::ScalarFunction*>(fn.get());
   auto& stock = g_stock_match_substring[op];
   stock.clear();
-  for (const cp::ScalarKernel* k : sfn->kernels()) stock.push_back(*k);
-  for (const auto& type : {arrow::utf8(), arrow::binary(), arrow::large_utf8(), arrow::large_binary()}) {
-    ARROW_ASSIGN_OR_RAISE(const cp::Kernel* k0, sfn->DispatchExact({type}));
-    cp::ScalarKernel copy = *static_cast<const cp::ScalarKernel*>(k0);
-    if (copy.data != nullptr || !copy.init) {
-      return Status::Invalid("arrow_amd: the reference's ", name, " kernel of ", type->ToString(), " is not of the expected shape");
-    }
-    auto data = std::make_shared<MatchSubstringKernelData>();
-    data->op = op;
-    data->fn = fn_id;
-    copy.data = std::move(data);
-    copy.signature = cp::KernelSignature::Make({cp::InputType(type)}, copy.signature->out_type());
-    copy.init = MatchSubstringInit;
-    copy.exec = MatchSubstringExec;
-    copy.null_handling = cp::NullHandling::COMPUTED_NO_PREALLOCATE;
-    copy.mem_allocation = cp::MemAllocation::NO_PREALLOCATE;
-    ARROW_RETURN_NOT_OK(sfn->AddKernel(std::move(copy)));
-  }
-  return Status::OK();
+  for (const cp::ScalarKernel* k : static_cast<cp::ScalarFunction*>(fn.get())->kernels()) stock.push_back(*k);
+  return AppendTwins(reg, name, {arrow::utf8(), arrow::binary(), arrow::large_utf8(), arrow::large_binary()},
+                     [](const auto& t) { return std::vector<arrow::TypeHolder>{t}; },
+                     [=](const ValueType& vt, cp::ScalarKernel* twin) -> arrow::Result<bool> {
+                       if (twin->data != nullptr || !twin->init) {
+                         return Status::Invalid("arrow_amd: the reference's ", name, " kernel of ", vt.probe->ToString(),
+                                                " is not of the expected shape");
+                       }
+                       auto data = std::make_shared<MatchSubstringKernelData>();
+                       data->op = op;
+                       data->fn = fn_id;
+                       twin->data = std::move(data);
+                       twin->signature = cp::KernelSignature::Make({vt.match}, twin->signature->out_type());
+                       twin->init = MatchSubstringInit;
+                       twin->exec = MatchSubstringExec;
+                       return true;
+                     });
 }

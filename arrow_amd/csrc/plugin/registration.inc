@@ -2,15 +2,6 @@
 // Part of the Arrow registration shim: included by ../arrow_plugin.cc inside its anonymous
 // namespace (one translation unit; the split is for reading, not for linkage).
 // ---------------------------------------------------------------- registration
-// A value type of array_filter / array_take: the concrete type used to find the stock kernel and
-// the matcher the added kernel is registered under (parametric types match by type id).
-struct ValueType {
-  std::shared_ptr<arrow::DataType> probe;
-  cp::InputType match;
-  ValueType(std::shared_ptr<arrow::DataType> t) : probe(t), match(t) {}  // NOLINT
-  ValueType(std::shared_ptr<arrow::DataType> t, Type::type id) : probe(std::move(t)), match(id) {}
-};
-
 std::vector<ValueType> FilterValueTypes() {
   return {arrow::boolean(), arrow::int8(), arrow::uint8(), arrow::int16(), arrow::uint16(), arrow::int32(), arrow::uint32(),
           arrow::int64(), arrow::uint64(), arrow::float16(), arrow::float32(), arrow::float64(), arrow::date32(),
@@ -183,14 +174,13 @@ Status RegisterAll() {
     using arrow::TimeUnit;
 #define ARX_REG_CMP_TEMPORAL(CT, ST, NUM, PROBE, MATCH, TI)                                                                     \
   {                                                                                                                             \
-    const std::shared_ptr<arrow::DataType> probe = PROBE;                                                                       \
-    const cp::InputType match = MATCH;                                                                                          \
-    ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareTemporal<CT, ST, NUM, ARX_CMP_EQUAL, 0 * 14 + TI>>(reg, "equal", probe, &match)));              \
-    ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareTemporal<CT, ST, NUM, ARX_CMP_NOT_EQUAL, 1 * 14 + TI>>(reg, "not_equal", probe, &match)));      \
-    ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareTemporal<CT, ST, NUM, ARX_CMP_GREATER, 2 * 14 + TI>>(reg, "greater", probe, &match)));          \
-    ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareTemporal<CT, ST, NUM, ARX_CMP_GREATER_EQUAL, 3 * 14 + TI>>(reg, "greater_equal", probe, &match))); \
-    ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareTemporal<CT, ST, NUM, ARX_CMP_LESS, 4 * 14 + TI>>(reg, "less", probe, &match)));                \
-    ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareTemporal<CT, ST, NUM, ARX_CMP_LESS_EQUAL, 5 * 14 + TI>>(reg, "less_equal", probe, &match)));    \
+    const ValueType vt(PROBE, MATCH);                                                                                           \
+    ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareTemporal<CT, ST, NUM, ARX_CMP_EQUAL, 0 * 14 + TI>>(reg, "equal", vt)));              \
+    ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareTemporal<CT, ST, NUM, ARX_CMP_NOT_EQUAL, 1 * 14 + TI>>(reg, "not_equal", vt)));      \
+    ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareTemporal<CT, ST, NUM, ARX_CMP_GREATER, 2 * 14 + TI>>(reg, "greater", vt)));          \
+    ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareTemporal<CT, ST, NUM, ARX_CMP_GREATER_EQUAL, 3 * 14 + TI>>(reg, "greater_equal", vt))); \
+    ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareTemporal<CT, ST, NUM, ARX_CMP_LESS, 4 * 14 + TI>>(reg, "less", vt)));                \
+    ARROW_RETURN_NOT_OK((RegisterScalarBinaryNP<OpCompareTemporal<CT, ST, NUM, ARX_CMP_LESS_EQUAL, 5 * 14 + TI>>(reg, "less_equal", vt)));    \
   }
     ARX_REG_CMP_TEMPORAL(int64_t, arrow::TimestampScalar, ARX_NUM_INT64, arrow::timestamp(TimeUnit::SECOND), cp::InputType(cp::match::TimestampTypeUnit(TimeUnit::SECOND)), 0)
     ARX_REG_CMP_TEMPORAL(int64_t, arrow::TimestampScalar, ARX_NUM_INT64, arrow::timestamp(TimeUnit::MILLI), cp::InputType(cp::match::TimestampTypeUnit(TimeUnit::MILLI)), 1)

@@ -170,11 +170,11 @@ Status ScalarBinaryNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::Exe
       hipStream_t st;
       ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
       ARROW_ASSIGN_OR_RAISE(out_arr->buffers[1], AllocDevice(std::max<int64_t>(data_bytes, 8)));
-      ARROW_ASSIGN_OR_RAISE(out_arr->buffers[0], AllocDevice(((n + 63) / 64) * 8 + 8));
+      ARROW_ASSIGN_OR_RAISE(out_arr->buffers[0], AllocDevice(BitmapBytes(n)));
       HIP_RETURN_NOT_OK(hipMemsetAsync(reinterpret_cast<void*>(out_arr->buffers[1]->mutable_address()), 0,
                                        static_cast<size_t>(std::max<int64_t>(data_bytes, 8)), st));
       HIP_RETURN_NOT_OK(hipMemsetAsync(reinterpret_cast<void*>(out_arr->buffers[0]->mutable_address()), 0,
-                                       static_cast<size_t>(((n + 63) / 64) * 8 + 8), st));
+                                       static_cast<size_t>(BitmapBytes(n)), st));
       HIP_RETURN_NOT_OK(hipStreamSynchronize(st));
       out_arr->null_count = n;
       CountGpu(Op::kFn);
@@ -259,80 +259,30 @@ Status ScalarBinaryNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::Exe
   }
 
   // ---- host operands: ScalarExecutor::PrepareOutput + PropagateNulls, then Arrow's stock kernel (or the Op's staging)
-  arrow::MemoryPool* pool = ctx->memory_pool();
-  std::shared_ptr<Buffer> data;
-  if (Op::kBitmapOut) {
-    ARROW_ASSIGN_OR_RAISE(data, ctx->AllocateBitmap(n));
-  } else {
-    ARROW_ASSIGN_OR_RAISE(data, ctx->Allocate(data_bytes));
-  }
-  std::shared_ptr<Buffer> validity;
-  int64_t null_count = 0;
-  bool null_scalar = false;
-  const ArraySpan* with_nulls[2];
-  int nv = 0;
-  for (int i = 0; i < 2; ++i) {
-    if (batch[i].is_scalar()) {
-      null_scalar = null_scalar || !batch[i].scalar->is_valid;
-    } else if (batch[i].array.MayHaveNulls()) {
-      with_nulls[nv++] = &batch[i].array;
-    }
-  }
-  if (null_scalar) {
-    ARROW_ASSIGN_OR_RAISE(validity, ctx->AllocateBitmap(n));
-    null_count = n;
-  } else if (nv == 1) {
-    ARROW_ASSIGN_OR_RAISE(validity, arrow::internal::CopyBitmap(pool, with_nulls[0]->buffers[0].data,
-                                                                with_nulls[0]->offset, n));
-    null_count = with_nulls[0]->null_count;
-  } else if (nv == 2) {
-    ARROW_ASSIGN_OR_RAISE(validity, arrow::internal::BitmapAnd(pool, with_nulls[0]->buffers[0].data,
-                                                               with_nulls[0]->offset, with_nulls[1]->buffers[0].data,
-                                                               with_nulls[1]->offset, n, 0));
-    null_count = arrow::kUnknownNullCount;
-  }
-  cp::ExecResult tmp;
-  ArraySpan span;
-  span.type = out_arr->type.get();
-  span.length = n;
-  span.offset = 0;
-  span.null_count = null_count;
-  if (validity) {
-    span.buffers[0].data = validity->mutable_data();
-    span.buffers[0].size = validity->size();
-  }
-  span.buffers[1].data = data->mutable_data();
-  span.buffers[1].size = data->size();
-  tmp.value = std::move(span);
+  const int width = Op::kBitmapOut ? 0 : static_cast<int>(sizeof(T));
   if constexpr (StagesHostArrays<Op>::value) {
-    ARROW_RETURN_NOT_OK(StagedHostCompare<Op>(ctx, batch, &tmp));
+    PreparedOutput p;
+    ARROW_RETURN_NOT_OK(p.Prepare(ctx, batch, out_arr->type.get(), width, TwinValidity::kIntersection));
+    ARROW_RETURN_NOT_OK(StagedHostCompare<Op>(ctx, batch, &p.tmp));
+    p.MoveInto(out_arr);
+    return Status::OK();
   } else {
-    CountStock(Op::kFn);
-    ARROW_RETURN_NOT_OK(Op::stock().exec(ctx, batch, &tmp));
+    return RunStockPrepared(Op::kFn, Op::stock().exec, std::nullopt, width, TwinValidity::kIntersection, ctx, batch, out);
   }
-  out_arr->buffers[0] = std::move(validity);
-  out_arr->buffers[1] = std::move(data);
-  out_arr->null_count = null_count;
-  return Status::OK();
 }
 
-// `match`: the matcher the added kernel is registered under when the type is parametric (timestamp(unit, any zone) ...);
-// the stock kernel is found with the concrete probe type t either way.
+// vt.match: the matcher the added kernel is registered under when the type is parametric (timestamp(unit, any zone) ...);
+// the stock kernel is found with the concrete probe type either way.
 template <class Op>
-Status RegisterScalarBinaryNP(cp::FunctionRegistry* reg, const char* name, const std::shared_ptr<arrow::DataType>& t,
-                              const cp::InputType* match = nullptr) {
-  ARROW_ASSIGN_OR_RAISE(auto fn, reg->GetFunction(name));
-  auto* sfn = static_cast<cp::ScalarFunction*>(fn.get());
-  ARROW_ASSIGN_OR_RAISE(const cp::Kernel* k0, sfn->DispatchExact({t, t}));
-  cp::ScalarKernel copy = *static_cast<const cp::ScalarKernel*>(k0);
-  Op::stock().exec = copy.exec;
-  Op::stock().init = copy.init;
-  const cp::InputType in = match != nullptr ? *match : cp::InputType(t);
-  copy.signature = cp::KernelSignature::Make({in, in}, copy.signature->out_type());
-  copy.exec = ScalarBinaryNP<Op>;
-  copy.null_handling = cp::NullHandling::COMPUTED_NO_PREALLOCATE;
-  copy.mem_allocation = cp::MemAllocation::NO_PREALLOCATE;
-  return sfn->AddKernel(std::move(copy));
+Status RegisterScalarBinaryNP(cp::FunctionRegistry* reg, const char* name, const ValueType& vt) {
+  return AppendTwins(reg, name, {vt}, [](const auto& t) { return std::vector<arrow::TypeHolder>{t, t}; },
+                     [](const ValueType& v, cp::ScalarKernel* twin) -> arrow::Result<bool> {
+                       Op::stock().exec = twin->exec;
+                       Op::stock().init = twin->init;
+                       twin->signature = cp::KernelSignature::Make({v.match, v.match}, twin->signature->out_type());
+                       twin->exec = ScalarBinaryNP<Op>;
+                       return true;
+                     });
 }
 
 // ---------------------------------------------------------------- and_kleene / or_kleene / invert
@@ -399,24 +349,9 @@ Status KleeneExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecR
     return Status::OK();
   }
   // host operands: NullHandling::COMPUTED_PREALLOCATE + MemAllocation::PREALLOCATE of the stock kernel
-  ARROW_ASSIGN_OR_RAISE(std::shared_ptr<Buffer> data, ctx->AllocateBitmap(n));
-  ARROW_ASSIGN_OR_RAISE(std::shared_ptr<Buffer> validity, ctx->AllocateBitmap(n));
-  cp::ExecResult tmp;
-  ArraySpan span;
-  span.type = out_arr->type.get();
-  span.length = n;
-  span.offset = 0;
-  span.null_count = arrow::kUnknownNullCount;
-  span.buffers[0].data = validity->mutable_data();
-  span.buffers[0].size = validity->size();
-  span.buffers[1].data = data->mutable_data();
-  span.buffers[1].size = data->size();
-  tmp.value = std::move(span);
-  CountStock(kFnBoolean);
-  ARROW_RETURN_NOT_OK(stock.exec(ctx, batch, &tmp));
-  out_arr->null_count = tmp.array_span()->null_count;
-  out_arr->buffers[0] = std::move(validity);
-  out_arr->buffers[1] = std::move(data);
+  int64_t null_count = 0;
+  ARROW_RETURN_NOT_OK(RunStockPrepared(kFnBoolean, stock.exec, std::nullopt, 0, TwinValidity::kAllocate, ctx, batch, out, &null_count));
+  out_arr->null_count = null_count;   // (as the reference's exec counted it)
   return Status::OK();
 }
 
@@ -446,51 +381,17 @@ Status InvertExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecR
     return Status::OK();
   }
   // host operand: NullHandling::INTERSECTION + PREALLOCATE
-  ARROW_ASSIGN_OR_RAISE(std::shared_ptr<Buffer> data, ctx->AllocateBitmap(n));
-  std::shared_ptr<Buffer> validity;
-  int64_t null_count = 0;
-  if (batch[0].is_scalar()) {
-    if (!batch[0].scalar->is_valid) {
-      ARROW_ASSIGN_OR_RAISE(validity, ctx->AllocateBitmap(n));
-      null_count = n;
-    }
-  } else if (batch[0].array.MayHaveNulls()) {
-    const ArraySpan& a = batch[0].array;
-    ARROW_ASSIGN_OR_RAISE(validity, arrow::internal::CopyBitmap(ctx->memory_pool(), a.buffers[0].data, a.offset, n));
-    null_count = a.null_count;
-  }
-  cp::ExecResult tmp;
-  ArraySpan span;
-  span.type = out_arr->type.get();
-  span.length = n;
-  span.offset = 0;
-  span.null_count = null_count;
-  if (validity) {
-    span.buffers[0].data = validity->mutable_data();
-    span.buffers[0].size = validity->size();
-  }
-  span.buffers[1].data = data->mutable_data();
-  span.buffers[1].size = data->size();
-  tmp.value = std::move(span);
-  CountStock(kFnBoolean);
-  ARROW_RETURN_NOT_OK(g_stock_invert.exec(ctx, batch, &tmp));
-  out_arr->buffers[0] = std::move(validity);
-  out_arr->buffers[1] = std::move(data);
-  out_arr->null_count = null_count;
-  return Status::OK();
+  return RunStockPrepared(kFnBoolean, g_stock_invert.exec, std::nullopt, 0, TwinValidity::kIntersection, ctx, batch, out);
 }
 
 Status RegisterBooleanNP(cp::FunctionRegistry* reg, const char* name, int arity, cp::ArrayKernelExec exec,
                          StockKernel* stock) {
-  ARROW_ASSIGN_OR_RAISE(auto fn, reg->GetFunction(name));
-  auto* sfn = static_cast<cp::ScalarFunction*>(fn.get());
-  std::vector<arrow::TypeHolder> types(arity, arrow::boolean());
-  ARROW_ASSIGN_OR_RAISE(const cp::Kernel* k0, sfn->DispatchExact(types));
-  cp::ScalarKernel copy = *static_cast<const cp::ScalarKernel*>(k0);
-  stock->exec = copy.exec;
-  stock->init = copy.init;
-  copy.exec = exec;
-  copy.null_handling = cp::NullHandling::COMPUTED_NO_PREALLOCATE;
-  copy.mem_allocation = cp::MemAllocation::NO_PREALLOCATE;
-  return sfn->AddKernel(std::move(copy));
+  return AppendTwins(reg, name, {arrow::boolean()},
+                     [arity](const auto& t) { return std::vector<arrow::TypeHolder>(arity, t); },
+                     [=](const ValueType&, cp::ScalarKernel* twin) -> arrow::Result<bool> {
+                       stock->exec = twin->exec;
+                       stock->init = twin->init;
+                       twin->exec = exec;   // (the reference's signature stays)
+                       return true;
+                     });
 }

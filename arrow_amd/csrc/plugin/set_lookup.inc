@@ -132,35 +132,11 @@ Status SetLookupBuild(DeviceSetLookupState* s, cp::ExecContext* exec_ctx, hipStr
 // a host batch: the reference's exec on what the executor preallocates for its COMPUTED_PREALLOCATE kernels
 Status SetLookupStock(cp::KernelContext* ctx, const SetLookupKernelData& kd, DeviceSetLookupState* s, const cp::ExecSpan& batch,
                       cp::ExecResult* out) {
-  const int64_t n = batch.length;
+  int64_t nulls = 0;
+  ARROW_RETURN_NOT_OK(RunStockPrepared(kd.index ? kFnIndexIn : kFnIsIn, s->stock_exec, s->stock.get(), kd.index ? 4 : 0,
+                                       TwinValidity::kAllocate, ctx, batch, out, &nulls));
   ArrayData* out_arr = out->array_data().get();
-  ARROW_ASSIGN_OR_RAISE(std::shared_ptr<Buffer> validity, ctx->AllocateBitmap(n));
-  std::shared_ptr<Buffer> data;
-  if (kd.index) {
-    ARROW_ASSIGN_OR_RAISE(data, ctx->Allocate(n * 4));
-  } else {
-    ARROW_ASSIGN_OR_RAISE(data, ctx->AllocateBitmap(n));
-  }
-  cp::ExecResult tmp;
-  ArraySpan span;
-  span.type = out_arr->type.get();
-  span.length = n;
-  span.offset = 0;
-  span.null_count = arrow::kUnknownNullCount;
-  span.buffers[0].data = validity->mutable_data();
-  span.buffers[0].size = validity->size();
-  span.buffers[1].data = data->mutable_data();
-  span.buffers[1].size = data->size();
-  tmp.value = std::move(span);
-  CountStock(kd.index ? kFnIndexIn : kFnIsIn);
-  cp::KernelState* mine = ctx->state();
-  ctx->SetState(s->stock.get());
-  const Status status = s->stock_exec(ctx, batch, &tmp);
-  ctx->SetState(mine);
-  ARROW_RETURN_NOT_OK(status);
-  int64_t nulls = tmp.array_span()->null_count;
-  if (nulls < 0) nulls = n - arrow::internal::CountSetBits(validity->data(), 0, n);
-  out_arr->buffers = {validity, data};
+  if (nulls < 0) nulls = batch.length - arrow::internal::CountSetBits(out_arr->buffers[0]->data(), 0, batch.length);
   out_arr->null_count = nulls;
   return Status::OK();
 }
@@ -194,7 +170,7 @@ Status SetLookupExec(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::Exec
   const int64_t m = s->set->length;
   ArrayData* out_arr = out->array_data().get();
   out_arr->buffers.assign(2, nullptr);
-  ARROW_ASSIGN_OR_RAISE(auto bits, AllocDevice(((n + 63) / 64) * 8 + 8));
+  ARROW_ASSIGN_OR_RAISE(auto bits, AllocDevice(BitmapBytes(n)));
   std::shared_ptr<Buffer> idx;
   if (kd->index) {
     ARROW_ASSIGN_OR_RAISE(idx, AllocDevice(std::max<int64_t>(n, 1) * 4));
@@ -236,36 +212,25 @@ Status SetLookupExec(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::Exec
 Status RegisterSetLookup(cp::FunctionRegistry* reg, const char* name, bool index) {
   ARROW_ASSIGN_OR_RAISE(auto fn, reg->GetFunction(name));
   if (fn->kind() != cp::Function::SCALAR) return Status::Invalid(name, " is not a scalar function");
-  auto* sfn = static_cast<cp::ScalarFunction*>(fn.get());
   auto& stock = g_stock_set_lookup[index ? 1 : 0];
   stock.clear();
-  for (const cp::ScalarKernel* k : sfn->kernels()) stock.push_back(*k);
-  struct SetLookupType {
-    std::shared_ptr<arrow::DataType> probe;
-    cp::InputType match;
-    SetLookupType(std::shared_ptr<arrow::DataType> t) : probe(t), match(t) {}  // NOLINT
-    SetLookupType(std::shared_ptr<arrow::DataType> t, Type::type id) : probe(std::move(t)), match(id) {}
-  };
-  const std::vector<SetLookupType> types = {
+  for (const cp::ScalarKernel* k : static_cast<cp::ScalarFunction*>(fn.get())->kernels()) stock.push_back(*k);
+  const std::vector<ValueType> types = {
       arrow::boolean(), arrow::int8(), arrow::uint8(), arrow::int16(), arrow::uint16(), arrow::int32(), arrow::uint32(),
       arrow::int64(), arrow::uint64(), arrow::float32(), arrow::float64(), arrow::date32(), arrow::date64(),
       {arrow::time32(arrow::TimeUnit::SECOND), Type::TIME32}, {arrow::time64(arrow::TimeUnit::NANO), Type::TIME64},
       {arrow::timestamp(arrow::TimeUnit::NANO), Type::TIMESTAMP}, {arrow::duration(arrow::TimeUnit::NANO), Type::DURATION},
       {arrow::decimal128(38, 9), Type::DECIMAL128}, arrow::utf8(), arrow::binary(), arrow::large_utf8(), arrow::large_binary()};
-  for (const auto& vt : types) {
-    auto k0 = sfn->DispatchExact({vt.probe});
-    if (!k0.ok()) continue;   // a type the reference does not look up either
-    cp::ScalarKernel copy = *static_cast<const cp::ScalarKernel*>(*k0);
-    if (copy.data != nullptr || !copy.init) continue;   // (none of the reference's set lookup kernels carries data)
-    auto data = std::make_shared<SetLookupKernelData>();
-    data->index = index;
-    copy.data = std::move(data);
-    copy.signature = cp::KernelSignature::Make({vt.match}, copy.signature->out_type());
-    copy.init = SetLookupInit;
-    copy.exec = SetLookupExec;
-    copy.null_handling = cp::NullHandling::COMPUTED_NO_PREALLOCATE;
-    copy.mem_allocation = cp::MemAllocation::NO_PREALLOCATE;
-    ARROW_RETURN_NOT_OK(sfn->AddKernel(std::move(copy)));
-  }
-  return Status::OK();
+  return AppendTwins(reg, name, types, [](const auto& t) { return std::vector<arrow::TypeHolder>{t}; },
+                     [index](const ValueType& vt, cp::ScalarKernel* twin) -> arrow::Result<bool> {
+                       if (twin->data != nullptr || !twin->init) return false;   // (none of the reference's set lookup kernels carries data)
+                       auto data = std::make_shared<SetLookupKernelData>();
+                       data->index = index;
+                       twin->data = std::move(data);
+                       twin->signature = cp::KernelSignature::Make({vt.match}, twin->signature->out_type());
+                       twin->init = SetLookupInit;
+                       twin->exec = SetLookupExec;
+                       return true;
+                     },
+                     /*skip_undispatched=*/true);   // a type the reference does not look up either
 }

@@ -182,11 +182,7 @@ Status SortChunkedNP(const StockKernel& stock, cp::KernelContext* ctx, const cp:
   out_arr->buffers[0] = nullptr;
   ARROW_ASSIGN_OR_RAISE(out_arr->buffers[1], ctx->Allocate(batch.length * 8));
   out_arr->null_count = 0;
-  CountStock(kFnSort);
-  ctx->SetState(state->stock.get());
-  const Status st = stock.exec_chunked(ctx, batch, out);
-  ctx->SetState(state);
-  return st;
+  return RunStock(kFnSort, stock.exec_chunked, std::optional<cp::KernelState*>(state->stock.get()), ctx, batch, out);
 }
 template <int K>
 Status SortChunkedT(cp::KernelContext* c, const cp::ExecBatch& b, arrow::Datum* o) {

@@ -1,0 +1,163 @@
+// The two halves every NO_PREALLOCATE kernel twin shares: its host fallback and its registration.
+// Part of the Arrow registration shim: included by ../arrow_plugin.cc inside its anonymous
+// namespace (one translation unit; the split is for reading, not for linkage).
+// ---------------------------------------------------------------- kernel twins
+// A scalar function taken over is registered as a twin: a copy of the reference's kernel with NullHandling::
+// COMPUTED_NO_PREALLOCATE + MemAllocation::NO_PREALLOCATE (the ScalarExecutor's own preallocation and null propagation,
+// exec.cc, run on the CPU and cannot touch device buffers).  Its exec runs the device kernel for device-resident
+// operands; for host operands it calls RunStockPrepared below.  AppendTwins registers it.
+
+// A value type of a twin (or of array_filter / array_take / array_sort_indices): the concrete type used to find the
+// stock kernel and the matcher the added kernel is registered under (parametric types match by type id).
+struct ValueType {
+  std::shared_ptr<arrow::DataType> probe;
+  cp::InputType match;
+  ValueType(std::shared_ptr<arrow::DataType> t) : probe(t), match(t) {}  // NOLINT
+  ValueType(std::shared_ptr<arrow::DataType> t, Type::type id) : probe(std::move(t)), match(id) {}
+  ValueType(std::shared_ptr<arrow::DataType> t, cp::InputType m) : probe(std::move(t)), match(std::move(m)) {}
+};
+
+// boolean and the fixed-width types coalesce and if_else take on the device.  The one rule for parametric types (unit,
+// time zone, precision / scale): they match by type id.
+std::vector<ValueType> FixedWidthTwinTypes(bool with_decimal128) {
+  std::vector<std::shared_ptr<arrow::DataType>> types = {
+      arrow::boolean(), arrow::int8(), arrow::uint8(), arrow::int16(), arrow::uint16(), arrow::int32(), arrow::uint32(), arrow::int64(),
+      arrow::uint64(), arrow::float32(), arrow::float64(), arrow::date32(), arrow::date64(), arrow::time32(arrow::TimeUnit::SECOND),
+      arrow::time64(arrow::TimeUnit::MICRO), arrow::timestamp(arrow::TimeUnit::SECOND), arrow::duration(arrow::TimeUnit::SECOND)};
+  if (with_decimal128) types.push_back(arrow::decimal128(38, 9));
+  std::vector<ValueType> out;
+  for (const auto& t : types) {
+    const bool parametric = arrow::is_temporal(t->id()) || t->id() == Type::DURATION || t->id() == Type::DECIMAL128;
+    out.push_back(parametric ? ValueType(t, t->id()) : ValueType(t));
+  }
+  return out;
+}
+
+// Says what a twin installs over the copy of the reference's kernel it is handed (which still holds the stock exec, init
+// and data: remember them here): signature, init, exec, data.  false: this type gets no twin.
+using TwinInstall = std::function<arrow::Result<bool>(const ValueType&, cp::ScalarKernel*)>;
+
+// Append one twin per type to the scalar function `name`: the reference's kernel is found by DispatchExact on probe(type)
+// — a type it does not take is an error unless skip_undispatched — copied, handed to `install`, given the two
+// NO_PREALLOCATE enums and added after the reference's own kernels (dispatch takes the last match).
+Status AppendTwins(cp::FunctionRegistry* reg, const std::string& name, const std::vector<ValueType>& types,
+                   const std::function<std::vector<arrow::TypeHolder>(const std::shared_ptr<arrow::DataType>&)>& probe,
+                   const TwinInstall& install, bool skip_undispatched = false) {
+  ARROW_ASSIGN_OR_RAISE(auto fn, reg->GetFunction(name));
+  if (fn->kind() != cp::Function::SCALAR) return Status::Invalid(name, " is not a scalar function");
+  auto* sfn = static_cast<cp::ScalarFunction*>(fn.get());
+  for (const ValueType& vt : types) {
+    auto k0 = sfn->DispatchExact(probe(vt.probe));
+    if (!k0.ok() && skip_undispatched) continue;
+    ARROW_RETURN_NOT_OK(k0.status());
+    cp::ScalarKernel twin = *static_cast<const cp::ScalarKernel*>(*k0);
+    ARROW_ASSIGN_OR_RAISE(const bool add, install(vt, &twin));
+    if (!add) continue;
+    twin.null_handling = cp::NullHandling::COMPUTED_NO_PREALLOCATE;
+    twin.mem_allocation = cp::MemAllocation::NO_PREALLOCATE;
+    ARROW_RETURN_NOT_OK(sfn->AddKernel(std::move(twin)));
+  }
+  return Status::OK();
+}
+
+// The output validity the executor would have prepared for the reference's kernel.
+enum class TwinValidity {
+  kNone,          // OUTPUT_NOT_NULL: no bitmap, null count 0
+  kAllocate,      // COMPUTED_PREALLOCATE: a zeroed bitmap for the kernel to fill, null count unknown
+  kIntersection,  // INTERSECTION (NullPropagator, exec.cc): no buffer when nothing can be null, a copy of the one bitmap
+                  // that can hold nulls, BitmapAnd of two, all clear with null count n for a null scalar
+};
+
+// What the ScalarExecutor would have preallocated for the reference's kernel: `tmp` is an ArraySpan at offset 0 over
+// the two buffers; null_count is the span's as prepared (0, n, an input's own or kUnknownNullCount).
+struct PreparedOutput {
+  std::shared_ptr<Buffer> validity, data;
+  int64_t null_count = 0;
+  cp::ExecResult tmp;
+
+  // width: bytes per value, 0 for a bitmap of batch.length bits
+  Status Prepare(cp::KernelContext* ctx, const cp::ExecSpan& batch, const arrow::DataType* type, int width, TwinValidity policy) {
+    const int64_t n = batch.length;
+    if (width == 0) {
+      ARROW_ASSIGN_OR_RAISE(data, ctx->AllocateBitmap(n));
+    } else {
+      ARROW_ASSIGN_OR_RAISE(data, ctx->Allocate(n * width));
+    }
+    if (policy == TwinValidity::kAllocate) {
+      ARROW_ASSIGN_OR_RAISE(validity, ctx->AllocateBitmap(n));
+      null_count = arrow::kUnknownNullCount;
+    } else if (policy == TwinValidity::kIntersection) {
+      bool null_scalar = false;
+      const ArraySpan* with_nulls[2];
+      int nv = 0;
+      for (const cp::ExecValue& v : batch.values) {
+        if (v.is_scalar()) {
+          null_scalar = null_scalar || !v.scalar->is_valid;
+        } else if (v.array.MayHaveNulls()) {
+          if (nv == 2) return Status::NotImplemented("arrow_amd: the validity intersection of more than two arrays");
+          with_nulls[nv++] = &v.array;
+        }
+      }
+      if (null_scalar) {
+        ARROW_ASSIGN_OR_RAISE(validity, ctx->AllocateBitmap(n));
+        null_count = n;
+      } else if (nv == 1) {
+        ARROW_ASSIGN_OR_RAISE(validity, arrow::internal::CopyBitmap(ctx->memory_pool(), with_nulls[0]->buffers[0].data,
+                                                                    with_nulls[0]->offset, n));
+        null_count = with_nulls[0]->null_count;
+      } else if (nv == 2) {
+        ARROW_ASSIGN_OR_RAISE(validity, arrow::internal::BitmapAnd(ctx->memory_pool(), with_nulls[0]->buffers[0].data,
+                                                                   with_nulls[0]->offset, with_nulls[1]->buffers[0].data,
+                                                                   with_nulls[1]->offset, n, 0));
+        null_count = arrow::kUnknownNullCount;
+      }
+    }
+    ArraySpan span;
+    span.type = type;
+    span.length = n;
+    span.offset = 0;
+    span.null_count = null_count;
+    if (validity) {
+      span.buffers[0].data = validity->mutable_data();
+      span.buffers[0].size = validity->size();
+    }
+    span.buffers[1].data = data->mutable_data();
+    span.buffers[1].size = data->size();
+    tmp.value = std::move(span);
+    return Status::OK();
+  }
+
+  // the filled buffers become `out`'s; the null count it reports is the prepared one
+  void MoveInto(ArrayData* out) {
+    out->buffers.resize(2);
+    out->buffers[0] = std::move(validity);
+    out->buffers[1] = std::move(data);
+    out->null_count = null_count;
+  }
+};
+
+// The host half of a twin: prepare the output, run the reference's exec (with its own KernelState installed, when
+// one is given) and hand the buffers to `out`.  stock_null_count, when asked for: what the exec left in the span.
+Status RunStockPrepared(Fn fn, cp::ArrayKernelExec exec, std::optional<cp::KernelState*> stock_state, int width,
+                        TwinValidity policy, cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecResult* out,
+                        int64_t* stock_null_count = nullptr) {
+  ArrayData* out_arr = out->array_data().get();
+  PreparedOutput p;
+  ARROW_RETURN_NOT_OK(p.Prepare(ctx, batch, out_arr->type.get(), width, policy));
+  ARROW_RETURN_NOT_OK(RunStock(fn, exec, stock_state, ctx, batch, &p.tmp));
+  if (stock_null_count != nullptr) *stock_null_count = p.tmp.array_span()->null_count;
+  p.MoveInto(out_arr);
+  return Status::OK();
+}
+
+// The bytes of a valid scalar operand of a device call: one byte 0 / 1 for a boolean (width 0), the value of a
+// fixed-width scalar otherwise.  Returns the scalar's width; nothing is written when that is not `width`.
+int64_t FixedWidthScalarBytes(const arrow::Scalar& sc, int width, void* out) {
+  if (width == 0) {
+    *static_cast<uint8_t*>(out) = static_cast<const arrow::BooleanScalar&>(sc).value ? 1 : 0;
+    return 0;
+  }
+  const auto bytes = static_cast<const arrow::internal::PrimitiveScalarBase&>(sc).view();
+  if (static_cast<int>(bytes.size()) == width) std::memcpy(out, bytes.data(), bytes.size());
+  return static_cast<int64_t>(bytes.size());
+}

@@ -47,7 +47,7 @@ Status ValidityExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::Exe
     }
     hipStream_t st;
     ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
-    const int64_t bytes = ((n + 63) / 64) * 8 + 8;
+    const int64_t bytes = BitmapBytes(n);
     ARROW_ASSIGN_OR_RAISE(out_arr->buffers[1], AllocDevice(bytes));
     void* d_out = reinterpret_cast<void*>(out_arr->buffers[1]->mutable_address());
     const void* validity = nullptr;
@@ -74,51 +74,28 @@ Status ValidityExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::Exe
     return Status::OK();
   }
   // host operand: the output the executor would have preallocated, then the reference's exec
-  ARROW_ASSIGN_OR_RAISE(std::shared_ptr<Buffer> data, ctx->AllocateBitmap(n));
-  std::shared_ptr<Buffer> validity;
-  int64_t null_count = 0;
-  if (KIND == kTrueUnlessNull && batch[0].is_array()) {   // NullPropagator (exec.cc): all null / a copy of the bitmap / no nulls
-    if (a.type->id() == Type::NA || (n > 0 && a.null_count == n)) {
-      ARROW_ASSIGN_OR_RAISE(validity, ctx->AllocateBitmap(n));
-      std::memset(validity->mutable_data(), 0, static_cast<size_t>(validity->size()));
-      null_count = n;
-    } else if (a.MayHaveNulls()) {
-      ARROW_ASSIGN_OR_RAISE(validity, arrow::internal::CopyBitmap(ctx->memory_pool(), a.buffers[0].data, a.offset, n));
-      null_count = a.null_count;
-    }
-  }
-  cp::ExecResult tmp;
-  ArraySpan span;
-  span.type = out_arr->type.get();
-  span.length = n;
-  span.offset = 0;
-  span.null_count = null_count;
-  if (validity) {
-    span.buffers[0].data = validity->mutable_data();
-    span.buffers[0].size = validity->size();
-  }
-  span.buffers[1].data = data->mutable_data();
-  span.buffers[1].size = data->size();
-  tmp.value = std::move(span);
-  ARROW_RETURN_NOT_OK(RunStock(kFnBoolean, g_stock_validity[KIND], state != nullptr ? state->stock.get() : nullptr, ctx, batch, &tmp));
-  out_arr->buffers[0] = std::move(validity);
-  out_arr->buffers[1] = std::move(data);
-  out_arr->null_count = null_count;
+  // (is_valid / is_null: OUTPUT_NOT_NULL; true_unless_null: INTERSECTION, where the NullPropagator, exec.cc, answers a null-typed or
+  // all-null array with an all-clear bitmap instead of a copy)
+  const bool propagate = KIND == kTrueUnlessNull && batch[0].is_array();
+  const bool all_null = propagate && (a.type->id() == Type::NA || (n > 0 && a.null_count == n));
+  PreparedOutput p;
+  ARROW_RETURN_NOT_OK(p.Prepare(ctx, batch, out_arr->type.get(), 0,
+                                all_null ? TwinValidity::kAllocate : propagate ? TwinValidity::kIntersection : TwinValidity::kNone));
+  if (all_null) p.null_count = p.tmp.array_span_mutable()->null_count = n;
+  ARROW_RETURN_NOT_OK(RunStock(kFnBoolean, g_stock_validity[KIND].exec,
+                               std::optional<cp::KernelState*>(state != nullptr ? state->stock.get() : nullptr), ctx, batch, &p.tmp));
+  p.MoveInto(out_arr);
   return Status::OK();
 }
 
 template <int KIND>
 Status RegisterValidityNP(cp::FunctionRegistry* reg, const char* name) {
-  ARROW_ASSIGN_OR_RAISE(auto fn, reg->GetFunction(name));
-  if (fn->kind() != cp::Function::SCALAR) return Status::Invalid(name, " is not a scalar function");
-  auto* sfn = static_cast<cp::ScalarFunction*>(fn.get());
-  ARROW_ASSIGN_OR_RAISE(const cp::Kernel* k0, sfn->DispatchExact({arrow::int64()}));
-  cp::ScalarKernel copy = *static_cast<const cp::ScalarKernel*>(k0);
-  g_stock_validity[KIND].exec = copy.exec;
-  g_stock_validity[KIND].init = copy.init;
-  copy.init = ValidityInit<KIND>;
-  copy.exec = ValidityExecNP<KIND>;
-  copy.null_handling = cp::NullHandling::COMPUTED_NO_PREALLOCATE;
-  copy.mem_allocation = cp::MemAllocation::NO_PREALLOCATE;
-  return sfn->AddKernel(std::move(copy));
+  return AppendTwins(reg, name, {arrow::int64()}, [](const auto& t) { return std::vector<arrow::TypeHolder>{t}; },
+                     [](const ValueType&, cp::ScalarKernel* twin) -> arrow::Result<bool> {
+                       g_stock_validity[KIND].exec = twin->exec;
+                       g_stock_validity[KIND].init = twin->init;
+                       twin->init = ValidityInit<KIND>;
+                       twin->exec = ValidityExecNP<KIND>;   // (the reference's signature stays: any type)
+                       return true;
+                     });
 }

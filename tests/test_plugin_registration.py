@@ -23,6 +23,58 @@ SCRIPT = textwrap.dedent(r'''
     f = pa.array(np.linspace(-1e40, 1e40, 1000))
     g = pa.array(np.linspace(1e40, -1e40, 1000), mask=np.arange(1000) % 5 == 0)
     fn = pa.array(f.to_numpy(), mask=np.arange(1000) % 11 == 0)
+    def gen(t, n, nulls=True, seed=0):
+        i = np.arange(n)
+        mask = (i + seed) % 3 == 0 if nulls else None
+        if pa.types.is_string(t) or pa.types.is_large_string(t):
+            return pa.array(["ab" * ((k + seed) % 4) + "c" * ((k + seed) % 2) for k in range(n)], pa.string(), mask=mask).cast(t)
+        if pa.types.is_boolean(t):
+            return pa.array((i * 7 + seed) % 2 == 0, mask=mask)
+        return pa.array(((i * 7 + seed) % 100).astype(np.int64), mask=mask).cast(t)
+    def shapes(t, seed=0):
+        # the operands on which a hand-made preallocation can go wrong: lengths around a bitmap word, a slice whose
+        # validity starts inside a byte, no validity buffer, nothing but nulls, more than one chunk
+        full = gen(t, 1000, seed=seed)
+        return [gen(t, n, seed=seed) for n in (0, 1, 63, 64, 65, 1000)] + \
+               [full.slice(7), full.slice(7, 64), gen(t, 1000, nulls=False, seed=seed), pa.nulls(65, t),
+                pa.chunked_array([full.slice(0, 300), full.slice(300)])]
+    def twins():
+        # the NO_PREALLOCATE twins beyond compare / arithmetic / Kleene / invert / sort: each hands the reference's
+        # exec the output the executor would have preallocated, so every shape must come out as the reference's own
+        out = []
+        i64, i32, i8, dec, s = pa.int64(), pa.int32(), pa.int8(), pa.decimal128(25, 3), pa.string()
+        for pred in (pc.is_valid, pc.is_null, pc.true_unless_null):
+            for t in (i64, s):
+                out += [pred(v) for v in shapes(t)] + [pred(gen(t, 1, nulls=False)[0]), pred(pa.scalar(None, t))]
+            out += [pred(pa.nulls(70)), pred(pa.nulls(0)), pred(pa.nulls(70).slice(7))]
+        out += [pc.is_null(pa.array([1.5, float("nan"), None]), nan_is_null=True)]
+        for t in (pa.bool_(), i8, i32, i64, dec):
+            one, null = gen(t, 1, nulls=False, seed=1)[0], pa.scalar(None, t)
+            for v in shapes(t):
+                w = gen(t, len(v), seed=1)
+                out += [pc.coalesce(v, w), pc.coalesce(v, one), pc.coalesce(v, null), pc.fill_null(v, one), pc.coalesce(v, w, one)]
+                if isinstance(v, pa.Array):
+                    out += [pc.coalesce(one, v), pc.coalesce(null, v)]
+            out += [pc.coalesce(one, null), pc.coalesce(null, null)]
+            for c in shapes(pa.bool_(), seed=2):
+                l, r = gen(t, len(c)), gen(t, len(c), seed=1)
+                plain = gen(t, len(c), nulls=False, seed=3)
+                out += [pc.if_else(c, l, r), pc.if_else(c, one, r), pc.if_else(c, l, null), pc.if_else(c, one, null),
+                        pc.if_else(c, one, one), pc.if_else(c, plain, plain), pc.if_else(c, plain, r)]
+            l, r = gen(t, 65), gen(t, 65, seed=1)
+            out += [pc.if_else(True, l, r), pc.if_else(False, l.slice(7), r.slice(7)), pc.if_else(pa.scalar(None, pa.bool_()), l, r),
+                    pc.if_else(True, one, null), pc.if_else(gen(pa.bool_(), 58, nulls=False), l.slice(7), r.slice(7))]
+        for t, members in ((i64, [7, 14, 21, None]), (i32, [7, 99]), (s, ["c", "abc", None]), (pa.large_string(), ["ab"])):
+            vs = pa.array(members, t)
+            for v in shapes(t) + [gen(t, 1, nulls=False, seed=1)[0], pa.scalar(None, t)]:
+                out += [pc.is_in(v, value_set=vs), pc.index_in(v, value_set=vs),
+                        pc.is_in(v, value_set=vs, skip_nulls=True), pc.index_in(v, value_set=vs, skip_nulls=True)]
+        for t in (s, pa.large_string(), pa.binary()):
+            for v in shapes(s) + [pa.scalar("ababc"), pa.scalar(None, s)]:
+                v = v.cast(t)
+                out += [pc.match_substring(v, "bc"), pc.starts_with(v, "ab"), pc.ends_with(v, "c"), pc.match_substring(v, "")]
+        out += [pc.match_substring(gen(s, 65), "BC", ignore_case=True), pc.starts_with(gen(s, 65), "AB", ignore_case=True)]
+        return out
     def run():
         # greater(double, double) is re-registered with NO_PREALLOCATE flags: every shape the
         # ScalarExecutor used to prepare for the stock kernel must come out identical
@@ -93,6 +145,7 @@ SCRIPT = textwrap.dedent(r'''
                    (an, a, an.slice(5, 0), pa.chunked_array([an.slice(0, 300), an.slice(300)]))]
         gt += [pc.count(an, mode=mode) for mode in ("only_valid", "only_null", "all")] + [pc.count(strs_h), pc.sum(f), pc.mean(an)]
         gt += [pa.table({"x": an}).group_by([]).aggregate([("x", "sum"), ("x", "min_max"), ("x", "count"), ("x", "max")]).to_pydict().__repr__()]
+        gt += twins()
         return gt + [pc.filter(a, m), pc.take(a, pa.array([5, 1, 999])), pc.greater(f, pa.array(f.to_numpy()[::-1].copy())),
                 pc.array_sort_indices(pa.array(np.arange(1000)[::-1].astype(np.uint64))),
                 pc.array_sort_indices(pa.array((np.arange(1000) % 13).astype(np.int64), mask=np.arange(1000) % 9 == 0),
@@ -116,9 +169,12 @@ SCRIPT = textwrap.dedent(r'''
     ours = run()
     for i, (x, y) in enumerate(zip(stock, ours)):
         assert (x == y) if isinstance(x, str) else x.equals(y), (i, x, y)
-        if isinstance(x, pa.Array):
+        if isinstance(x, (pa.Array, pa.ChunkedArray)):
             assert x.null_count == y.null_count, i
-    for fn in (b"array_filter", b"array_take", b"greater", b"array_sort_indices", b"cast", b"add", b"boolean", b"compare", b"reduce"):
+        if not isinstance(y, str):
+            y.validate(full=True)
+    for fn in (b"array_filter", b"array_take", b"greater", b"array_sort_indices", b"cast", b"add", b"boolean", b"compare", b"reduce",
+               b"coalesce", b"if_else", b"is_in", b"index_in", b"match_substring", b"starts_with", b"ends_with"):
         assert lib.arrow_amd_plugin_calls(fn, 0) >= 1, fn     # handed to Arrow's stock kernel
         assert lib.arrow_amd_plugin_calls(fn, 1) == 0, fn     # nothing claimed to be a GPU call
     assert lib.arrow_amd_plugin_calls(b"no_such_function", 0) == -1
