@@ -1320,6 +1320,24 @@ static int launch_compact(bool iota, int W, const CompactArgs& a, hipStream_t st
   return ARX_OK;
 }
 
+// What launch_compact above launches, restated as a pure function of the same inputs for arx_filter_compact_form (the
+// tests assert with it which kernel a case is about to run).  No device call.  Keep the two in step: the table of
+// tests/test_filter_dispatch.py pins this one.
+static int compact_form(bool iota, int W, bool values_aligned16, bool invert, int64_t length, int64_t out_length) {
+  const int filter_sparse = g_filter_sparse;
+  if (iota) {
+    if (!invert && filter_sparse != 0 && (W == 2 || W == 4 || W == 8)) return ARX_COMPACT_GATHER;
+    if (W != 2 && W != 4) return ARX_NOT_IMPLEMENTED;
+  } else {
+    const bool sparse = !invert && (filter_sparse == 1 ||
+                                    (filter_sparse < 0 && (W >= 8 || (out_length >= 0 && out_length * 4 <= length))));
+    if (sparse) return W == 1 || W == 2 || W == 4 || W == 8 || W == 16 || W == 32 ? ARX_COMPACT_GATHER : ARX_NOT_IMPLEMENTED;
+    if (W != 1 && W != 2 && W != 4 && W != 8 && W != 16) return ARX_NOT_IMPLEMENTED;
+  }
+  if (!iota && !values_aligned16) return ARX_COMPACT_SWEEP_UNALIGNED;  // element-wise loads; row numbers have no loads
+  return g_filter_batch >= 4 && g_filter_pipe ? ARX_COMPACT_SWEEP_PIPELINED : ARX_COMPACT_SWEEP_PLAIN;
+}
+
 // Zero the ceil(S/64) words of an output bitmap (tile-boundary words are OR-ed in).
 static int zero_out_validity(void* out_validity, int64_t out_length, hipStream_t st) {
   if (out_validity == nullptr) return ARX_OK;
@@ -1570,6 +1588,11 @@ int arx_mask_to_indices(const ArxSpan* mask, int null_selection, const void* ws,
   rc = zero_out_validity(out_validity, out_length, st);
   if (rc != ARX_OK) return rc;
   return launch_compact(true, index_width, a, st);
+}
+
+int arx_filter_compact_form(int row_numbers, int byte_width, int values_aligned16, int invert, int64_t length,
+                            int64_t out_length) {
+  return compact_form(row_numbers != 0, byte_width, values_aligned16 != 0, invert != 0, length, out_length);
 }
 
 size_t arx_take_workspace_bytes(void) { return sizeof(BoundsWs); }

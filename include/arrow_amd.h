@@ -153,6 +153,19 @@ int arx_mask_to_indices(const ArxSpan* mask, int null_selection, const void* ws,
                         int64_t out_length, int index_width, void* out_indices,
                         void* out_validity, void* stream);
 
+/* The compaction kernel forms of arx_filter_exec / arx_mask_to_indices / arx_bitmap_to_indices. */
+enum { ARX_COMPACT_GATHER = 0, ARX_COMPACT_SWEEP_PIPELINED = 1, ARX_COMPACT_SWEEP_PLAIN = 2, ARX_COMPACT_SWEEP_UNALIGNED = 3 };
+
+/* Which compaction kernel arx_filter_exec / arx_mask_to_indices would launch for these inputs under the current
+ * knobs (filter_sparse, filter_batch, filter_pipe).  No device call.  row_numbers: 0 = arx_filter_exec (byte_width =
+ * the value width, values_aligned16 = whether values->data + values->offset * byte_width is 16-byte aligned),
+ * 1 = arx_mask_to_indices / arx_bitmap_to_indices (byte_width = the index width; invert: arx_bitmap_to_indices only).
+ * out_length: what arx_filter_exec is given (-1 = unknown; arx_mask_to_indices does not use it).
+ * ARX_COMPACT_GATHER, _SWEEP_PIPELINED, _SWEEP_PLAIN, _SWEEP_UNALIGNED; <0 (ARX_NOT_IMPLEMENTED): unsupported.
+ * Not part of the reference interface: the tests use it to assert which kernel a case ran. */
+int arx_filter_compact_form(int row_numbers, int byte_width, int values_aligned16, int invert,
+                            int64_t length, int64_t out_length);
+
 /* ---------------------------------------------------------------------------
  * Take — replaces FixedWidthTakeExec / Gather<W,Idx,false>
  * (vector_selection_take_internal.cc:339-468, gather_internal.h:47-251) and

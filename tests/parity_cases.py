@@ -3460,3 +3460,380 @@ def check_select_k_partition_nth(amd, rng_for, scale=1, light=False):
                         assert took == ({"threshold": 0, "sorted": 1} if hi == 2 else {"threshold": 1, "sorted": 0}), (took, lo, hi, k)
     finally:
         amd.compute.SELECT_K_MIN_ROWS = saved
+
+
+# ------------------------------------------------------------------ the compaction forms, at the C ABI
+# arx_filter_compact_form's answers (include/arrow_amd.h)
+COMPACT_GATHER, COMPACT_SWEEP_PIPELINED, COMPACT_SWEEP_PLAIN, COMPACT_SWEEP_UNALIGNED = 0, 1, 2, 3
+COMPACT_FORM_NAMES = {COMPACT_GATHER: "gather", COMPACT_SWEEP_PIPELINED: "sweep_pipelined",
+                      COMPACT_SWEEP_PLAIN: "sweep_plain", COMPACT_SWEEP_UNALIGNED: "sweep_unaligned"}
+# knobs that reach a form whatever the selectivity (filter_sparse = -1 is asked for per case with sparse=-1)
+_FORM_KNOBS = {COMPACT_GATHER: {b"filter_sparse": 1},
+               COMPACT_SWEEP_PIPELINED: {b"filter_sparse": 0, b"filter_batch": 4, b"filter_pipe": 1},
+               COMPACT_SWEEP_PLAIN: {b"filter_sparse": 0, b"filter_batch": 4, b"filter_pipe": 0},
+               COMPACT_SWEEP_UNALIGNED: {b"filter_sparse": 0, b"filter_batch": 4, b"filter_pipe": 1}}
+# (kind, width, form name, null selection) -> cases whose arx_filter_compact_form assertion held and that then ran
+FORM_HITS: dict = {}
+_GUARD_BYTE = 0xEE
+_GUARD = 4096
+kFlushBytes = 2048   # the compaction's flush unit (selection.hip): a tile's first ring byte is its output address mod this
+
+
+def _hit(kind, width, form, sel):
+    key = (kind, width, COMPACT_FORM_NAMES[form], sel)
+    FORM_HITS[key] = FORM_HITS.get(key, 0) + 1
+
+
+class _Placed:
+    """`nbytes` payload bytes at `shift` bytes past an `align`-byte boundary inside a device buffer filled with 0xEE, at
+    least 4 KiB of it on either side: read() returns the payload and whether every other byte is still 0xEE."""
+
+    def __init__(self, nbytes, align, shift=0, host=None):
+        import torch
+
+        from arrow_amd.array import alloc
+
+        self.nbytes = int(nbytes)
+        self.raw = alloc(_GUARD + align + shift + self.nbytes + _GUARD)
+        self.raw.fill_(_GUARD_BYTE)
+        self.start = (-(self.raw.data_ptr() + _GUARD)) % align + _GUARD + shift
+        self.ptr = self.raw.data_ptr() + self.start
+        if host is not None:
+            host = np.ascontiguousarray(host).view(np.uint8).reshape(-1)
+            assert host.nbytes == self.nbytes
+            if self.nbytes:
+                self.raw[self.start: self.start + self.nbytes].copy_(torch.from_numpy(host.copy()))
+
+    def read(self):
+        host = self.raw.cpu().numpy()
+        end = self.start + self.nbytes
+        return host[self.start: end].copy(), bool((host[: self.start] == _GUARD_BYTE).all() and (host[end:] == _GUARD_BYTE).all())
+
+
+def _bitmap(bits):
+    """bool array -> LSB-first bitmap bytes in whole 64-bit words (None stays None)."""
+    if bits is None:
+        return None
+    out = np.zeros(((len(bits) + 63) // 64) * 8, dtype=np.uint8)
+    packed = np.packbits(bits, bitorder="little")
+    out[: len(packed)] = packed
+    return out
+
+
+def _span(L, validity, data, offset, length):
+    s = L.ArxSpan()
+    s.validity = None if validity is None else validity.ptr
+    s.data = None if data is None else data.ptr
+    s.offset, s.length = offset, length
+    s.null_count = 0 if validity is None else -1      # -1: unknown, the bitmap decides
+    return s
+
+
+def _mask_inputs(rng, n, moff, true_p, mnull):
+    """A boolean mask of n logical slots at bit offset moff (3 slots of tail): bits, validity or None, their device
+    bitmaps (64-byte aligned) and the logical views."""
+    total = moff + n + 3
+    bits = rng.random(total) < true_p
+    valid = (rng.random(total) >= mnull) if mnull > 0 else None
+    d_bits = _Placed(len(_bitmap(bits)), 64, host=_bitmap(bits))
+    d_valid = None if valid is None else _Placed(len(_bitmap(valid)), 64, host=_bitmap(valid))
+    mask_l = bits[moff: moff + n]
+    mvalid_l = np.ones(n, dtype=bool) if valid is None else valid[moff: moff + n]
+    return d_bits, d_valid, mask_l, mvalid_l
+
+
+def _emit(mask_l, mvalid_l, sel, mask_is_nullable):
+    if sel == "emit_null" and mask_is_nullable:
+        return mask_l | ~mvalid_l
+    return mask_l & mvalid_l
+
+
+def _workspace(lib, n):
+    """A 64-byte aligned count workspace for n mask slots: (holder, pointer, bytes)."""
+    nbytes = lib.arx_filter_workspace_bytes(n)
+    ws = _Placed(nbytes, 64)
+    return ws, ws.ptr, nbytes
+
+
+def _check_output_bitmap(tag, placed, length, want_valid):
+    raw, untouched = placed.read()
+    assert untouched, f"{tag}: bytes around the output validity were written"
+    bits = np.unpackbits(raw, bitorder="little")
+    assert_equal(bits[:length].astype(bool), want_valid, tag + " validity")
+    assert not bits[length:].any(), f"{tag}: padding bits of the last validity word are not zero"
+
+
+def check_filter_form(amd, width, form, sel, n, moff=0, true_p=0.3, vnull=0.0, mnull=0.0, disp=0, sparse=None,
+                      voff_units=3):
+    """arx_filter_count -> arx_filter_exec on `width`-byte values built so that the compaction provably takes `form`:
+    the aligned forms put logical element 0 on a 16-byte boundary (value offset = voff_units * 16/width), the unaligned
+    form off one (offset + 1; 16-byte values: the buffer starts 8 bytes past a boundary); the knobs of _FORM_KNOBS
+    force gather / sweep, sparse=-1 leaves the choice to the selectivity instead.  arx_filter_compact_form must name
+    `form` BEFORE the launch.  The output goes to `disp` elements past a 2 KiB boundary.  Reference: numpy on the
+    (n, width) byte view; every byte, null slots included, every validity bit, the padding bits, the length, the null
+    count, and 0xEE guards (>= 4 KiB) around the output data and validity."""
+    import ctypes as C
+
+    from arrow_amd import _lib as L
+    from arrow_amd.array import current_stream, default_device
+
+    lib = L.get_lib()
+    stream = current_stream(default_device())
+    code = 1 if sel == "emit_null" else 0
+    rng = np.random.default_rng([util.kRandomSeed, width, form, code, n, moff, int(true_p * 1000), int(vnull * 1000),
+                                 int(mnull * 1000), disp])
+    tag = f"filter_form[W={width},{COMPACT_FORM_NAMES[form]},{sel},n={n},moff={moff},p={true_p},nulls=({vnull},{mnull}),disp={disp},sparse={sparse}]"
+    # ---- inputs
+    per16 = max(1, 16 // width)
+    voff = voff_units * per16
+    shift = 0
+    if form == COMPACT_SWEEP_UNALIGNED:
+        if width < 16:
+            voff += 1
+        else:
+            shift = 8
+    elif form == COMPACT_GATHER and width < 16:
+        voff += 1                    # the gather form does not care: keep it off the boundary
+    total = voff + n + per16 + 16 // min(width, 16)   # >= 16 bytes of tail: the last granule load of the aligned forms stays inside
+    vals = rng.integers(0, 256, size=(total, width), dtype=np.uint8)
+    vvalid = (rng.random(total) >= vnull) if vnull > 0 else None
+    d_vals = _Placed(vals.nbytes, 16, shift, host=vals)
+    d_vvalid = None if vvalid is None else _Placed(len(_bitmap(vvalid)), 64, host=_bitmap(vvalid))
+    aligned16 = (d_vals.ptr + voff * width) % 16 == 0
+    assert aligned16 == (form in (COMPACT_SWEEP_PIPELINED, COMPACT_SWEEP_PLAIN)) or form == COMPACT_GATHER, tag
+    d_mask, d_mvalid, mask_l, mvalid_l = _mask_inputs(rng, n, moff, true_p, mnull)
+    vspan = _span(L, d_vvalid, d_vals, voff, n)
+    mspan = _span(L, d_mvalid, d_mask, moff, n)
+    # ---- reference
+    emit = _emit(mask_l, mvalid_l, sel, d_mvalid is not None)
+    want = vals[voff: voff + n][emit].copy()
+    want[~mvalid_l[emit]] = 0
+    vvalid_l = np.ones(n, dtype=bool) if vvalid is None else vvalid[voff: voff + n]
+    want_valid = (vvalid_l & mvalid_l)[emit]
+    S = int(emit.sum())
+    # ---- count
+    ws, ws_ptr, ws_bytes = _workspace(lib, n)
+    n_out, n_null = C.c_int64(-1), C.c_int64(-1)
+    L.check(lib.arx_filter_count_nulls(C.byref(vspan), C.byref(mspan), code, ws_ptr, ws_bytes, C.byref(n_out), C.byref(n_null), stream))
+    assert (n_out.value, n_null.value) == (S, int(S - want_valid.sum())), (tag, n_out.value, n_null.value, S, int(S - want_valid.sum()))
+    n_out = C.c_int64(-1)
+    L.check(lib.arx_filter_count(C.byref(mspan), code, ws_ptr, ws_bytes, C.byref(n_out), stream))
+    assert n_out.value == S, (tag, n_out.value, S)
+    # ---- exec, under the knobs of the form
+    out = _Placed(S * width, kFlushBytes, disp * width)
+    need_validity = d_vvalid is not None or d_mvalid is not None    # neither input has nulls -> no buffer is needed
+    out_valid = _Placed(((S + 63) // 64) * 8, 64) if need_validity else None
+    knobs = dict(_FORM_KNOBS[form])
+    if sparse is not None:
+        knobs[b"filter_sparse"] = sparse
+    with util.options(lib, knobs):
+        got_form = lib.arx_filter_compact_form(0, width, int(aligned16), 0, n, S)
+        assert got_form == form, f"{tag}: the dispatch names {COMPACT_FORM_NAMES.get(got_form, got_form)}"
+        L.check(lib.arx_filter_exec(C.byref(vspan), width, C.byref(mspan), code, ws_ptr, S, out.ptr,
+                                    None if out_valid is None else out_valid.ptr, stream))
+        got, untouched = out.read()
+    _hit("values", width, form, sel)
+    assert untouched, f"{tag}: bytes around the output data were written"
+    assert_equal(got.reshape(S, width), want, tag + " data bytes")
+    if out_valid is not None:
+        _check_output_bitmap(tag, out_valid, S, want_valid)
+    else:
+        assert want_valid.all(), tag
+    assert ws.read()[1], f"{tag}: bytes around the workspace were written"
+
+
+def filter_form_cases(width, form, sel):
+    """The cases of one (width, form, null selection) cell of the matrix: every length at selectivity 0.3, every selectivity at the multi-tile (12 293) and the multi-group
+    (266 241) length; the null densities, mask bit offsets and output displacements rotate through the cases so that
+    each value meets each length class.  Yields check_filter_form keyword arguments."""
+    nulls = [(0.2, 0.0), (0.0, 0.3), (0.0, 0.0), (1.0, 1.0)]
+    moffs = [1, 63, 0]
+    disps = [1, kFlushBytes // width - 1, 0]
+    lengths = [1, 63, 4095, 4096, 4097, 3 * 4096 + 5, 262144 + 4097]
+    cases = [(n, 0.3) for n in lengths]
+    cases += [(n, p) for n in lengths[-2:] for p in (0.0, 0.02, 1.0)]
+    for i, (n, p) in enumerate(cases):
+        vnull, mnull = nulls[i % 4]
+        kw = dict(n=n, true_p=p, vnull=vnull, mnull=mnull, moff=moffs[i % 3], disp=disps[(i // 2) % 3])
+        if n >= 4096 and (vnull, mnull) == (1.0, 1.0) and p == 0.3:
+            kw["vnull"], kw["mnull"] = 0.2, 0.3      # a multi-tile case keeps rows under DROP; both inputs nullable
+        # the automatic choice (filter_sparse = -1) in every other case where it provably leads to the same form: 8 bytes
+        # and wider always gather; narrower values gather up to 25 % emitted rows and sweep above (taken only where the
+        # expected fraction is far from 25 % for the length, so that the draw cannot cross it)
+        mn = kw["mnull"]
+        frac = p * (1 - mn) + (mn if sel == "emit_null" else 0.0)
+        if i % 2 == 1:
+            if form == COMPACT_GATHER and (width >= 8 or frac <= 0.1):
+                kw["sparse"] = -1
+            elif form != COMPACT_GATHER and width < 8 and (frac == 1.0 or (frac >= 0.29 and n >= 4095)):
+                kw["sparse"] = -1
+        if i % 5 == 4:
+            kw["voff_units"] = 0
+        yield kw
+
+
+def check_filter_w32_sweep_is_refused(amd):
+    """32-byte values have the gather form only: with filter_sparse = 0 arx_filter_exec answers ARX_NOT_IMPLEMENTED
+    and writes nothing."""
+    import ctypes as C
+
+    from arrow_amd import _lib as L
+    from arrow_amd.array import current_stream, default_device
+
+    lib = L.get_lib()
+    stream = current_stream(default_device())
+    rng = np.random.default_rng([util.kRandomSeed, 32])
+    n = 5000
+    vals = rng.integers(0, 256, size=(n + 1, 32), dtype=np.uint8)
+    d_vals = _Placed(vals.nbytes, 16, host=vals)
+    d_mask, _, mask_l, _ = _mask_inputs(rng, n, 1, 0.5, 0.0)
+    vspan, mspan = _span(L, None, d_vals, 0, n), _span(L, None, d_mask, 1, n)
+    ws, ws_ptr, ws_bytes = _workspace(lib, n)
+    n_out = C.c_int64(-1)
+    L.check(lib.arx_filter_count(C.byref(mspan), 0, ws_ptr, ws_bytes, C.byref(n_out), stream))
+    S = int(mask_l.sum())
+    assert n_out.value == S
+    out = _Placed(S * 32, kFlushBytes)
+    with util.options(lib, {b"filter_sparse": 0}):
+        assert lib.arx_filter_compact_form(0, 32, 1, 0, n, S) == L.ARX_NOT_IMPLEMENTED
+        assert lib.arx_filter_exec(C.byref(vspan), 32, C.byref(mspan), 0, ws_ptr, S, out.ptr, None, stream) == L.ARX_NOT_IMPLEMENTED
+        got, untouched = out.read()
+    assert untouched and (got == _GUARD_BYTE).all(), "a refused filter wrote to its output"
+
+
+def check_mask_to_indices_form(amd, width, form, sel, n, moff=0, true_p=0.3, mnull=0.0, disp=0):
+    """arx_mask_to_indices called directly, `width`-byte row numbers, in the form the knobs of _FORM_KNOBS select
+    (row numbers have no loads: the sweep is always an aligned one).  Reference: np.flatnonzero of the same emit mask
+    as the filter's, 0 + null for a null mask slot under EMIT_NULL."""
+    import ctypes as C
+
+    from arrow_amd import _lib as L
+    from arrow_amd.array import current_stream, default_device
+
+    lib = L.get_lib()
+    stream = current_stream(default_device())
+    code = 1 if sel == "emit_null" else 0
+    rng = np.random.default_rng([util.kRandomSeed, 77, width, form, code, n, moff, int(true_p * 1000), int(mnull * 1000), disp])
+    tag = f"mask_to_indices_form[W={width},{COMPACT_FORM_NAMES[form]},{sel},n={n},moff={moff},p={true_p},mnull={mnull},disp={disp}]"
+    d_mask, d_mvalid, mask_l, mvalid_l = _mask_inputs(rng, n, moff, true_p, mnull)
+    mspan = _span(L, d_mvalid, d_mask, moff, n)
+    emit = _emit(mask_l, mvalid_l, sel, d_mvalid is not None)
+    want = np.flatnonzero(emit).astype({2: np.uint16, 4: np.uint32, 8: np.uint64}[width])
+    want_valid = mvalid_l[emit]
+    want[~want_valid] = 0
+    S = len(want)
+    ws, ws_ptr, ws_bytes = _workspace(lib, n)
+    n_out = C.c_int64(-1)
+    L.check(lib.arx_filter_count(C.byref(mspan), code, ws_ptr, ws_bytes, C.byref(n_out), stream))
+    assert n_out.value == S, (tag, n_out.value, S)
+    out = _Placed(S * width, kFlushBytes, disp * width)
+    out_valid = _Placed(((S + 63) // 64) * 8, 64) if d_mvalid is not None else None
+    with util.options(lib, _FORM_KNOBS[form]):
+        got_form = lib.arx_filter_compact_form(1, width, 1, 0, n, S)
+        assert got_form == form, f"{tag}: the dispatch names {COMPACT_FORM_NAMES.get(got_form, got_form)}"
+        L.check(lib.arx_mask_to_indices(C.byref(mspan), code, ws_ptr, S, width, out.ptr,
+                                        None if out_valid is None else out_valid.ptr, stream))
+        got, untouched = out.read()
+    _hit("row_numbers", width, form, sel)
+    assert untouched, f"{tag}: bytes around the row numbers were written"
+    assert_equal(got.view(want.dtype), want, tag + " row numbers")
+    if out_valid is not None:
+        _check_output_bitmap(tag, out_valid, S, want_valid)
+
+
+def check_mask_to_indices_width8_refusals(amd):
+    """index_width 8 is the gather form with DROP only: ARX_NOT_IMPLEMENTED under filter_sparse = 0 and for EMIT_NULL,
+    nothing written."""
+    import ctypes as C
+
+    from arrow_amd import _lib as L
+    from arrow_amd.array import current_stream, default_device
+
+    lib = L.get_lib()
+    stream = current_stream(default_device())
+    rng = np.random.default_rng([util.kRandomSeed, 78])
+    n = 5000
+    d_mask, d_mvalid, mask_l, mvalid_l = _mask_inputs(rng, n, 3, 0.3, 0.1)
+    mspan = _span(L, d_mvalid, d_mask, 3, n)
+    ws, ws_ptr, ws_bytes = _workspace(lib, n)
+    for code, knob in ((0, 0), (1, 1), (1, -1)):
+        n_out = C.c_int64(-1)
+        L.check(lib.arx_filter_count(C.byref(mspan), code, ws_ptr, ws_bytes, C.byref(n_out), stream))
+        out = _Placed(n_out.value * 8, kFlushBytes)
+        out_valid = _Placed(((n_out.value + 63) // 64) * 8, 64)
+        with util.options(lib, {b"filter_sparse": knob}):
+            if knob == 0:
+                assert lib.arx_filter_compact_form(1, 8, 1, 0, n, n_out.value) == L.ARX_NOT_IMPLEMENTED
+            rc = lib.arx_mask_to_indices(C.byref(mspan), code, ws_ptr, n_out.value, 8, out.ptr, out_valid.ptr, stream)
+            assert rc == L.ARX_NOT_IMPLEMENTED, (code, knob, rc)
+            for buf in (out, out_valid):
+                got, untouched = buf.read()
+                assert untouched and (got == _GUARD_BYTE).all(), "a refused arx_mask_to_indices wrote to its output"
+
+
+def check_bitmap_to_indices(amd, n, bit_offset, invert, true_p=0.3):
+    """arx_bitmap_to_indices against np.flatnonzero(bits) / np.flatnonzero(~bits): the inverted form is the only caller
+    of the sweeping row-number kernel with invert = 1; inverted bits past the end must not appear."""
+    import ctypes as C
+
+    from arrow_amd import _lib as L
+    from arrow_amd.array import current_stream, default_device
+
+    lib = L.get_lib()
+    stream = current_stream(default_device())
+    rng = np.random.default_rng([util.kRandomSeed, 79, n, bit_offset, invert, int(true_p * 1000)])
+    tag = f"bitmap_to_indices[n={n},off={bit_offset},invert={invert},p={true_p}]"
+    d_bits, _, bits_l, _ = _mask_inputs(rng, n, bit_offset, true_p, 0.0)
+    want = np.flatnonzero(~bits_l if invert else bits_l).astype(np.uint32)
+    ws, ws_ptr, ws_bytes = _workspace(lib, n)
+    out = _Placed(len(want) * 4, 64)
+    form = lib.arx_filter_compact_form(1, 4, 1, invert, n, -1)
+    assert form in (COMPACT_SWEEP_PIPELINED, COMPACT_SWEEP_PLAIN) if invert else form == COMPACT_GATHER, (tag, form)
+    count = C.c_int64(-1)
+    L.check(lib.arx_bitmap_to_indices(d_bits.ptr, bit_offset, n, invert, ws_ptr, ws_bytes, C.cast(out.ptr, C.POINTER(C.c_uint32)),
+                                      C.byref(count), stream))
+    got, untouched = out.read()
+    _hit("bit_positions" + ("_inverted" if invert else ""), 4, form, "drop")
+    assert count.value == len(want), (tag, count.value, len(want))
+    assert untouched, f"{tag}: bytes around the positions were written"
+    assert_equal(got.view(np.uint32), want, tag)
+
+
+def check_expand_by_mask(amd, width, n, moff, mnull, true_p=0.4):
+    """arx_expand_by_mask (the inverse of a DROP filter): out = zeros; out[mask & mask_valid] = dense, every byte of the
+    n slots, nothing past them."""
+    import ctypes as C
+
+    from arrow_amd import _lib as L
+    from arrow_amd.array import current_stream, default_device
+
+    lib = L.get_lib()
+    stream = current_stream(default_device())
+    rng = np.random.default_rng([util.kRandomSeed, 80, width, n, moff, int(mnull * 1000)])
+    tag = f"expand_by_mask[W={width},n={n},moff={moff},mnull={mnull}]"
+    d_mask, d_mvalid, mask_l, mvalid_l = _mask_inputs(rng, n, moff, true_p, mnull)
+    mspan = _span(L, d_mvalid, d_mask, moff, n)
+    keep = mask_l & mvalid_l
+    S = int(keep.sum())
+    dense = rng.integers(1, 256, size=(S, width), dtype=np.uint8)      # no zero byte: a slot left at zero shows
+    want = np.zeros((n, width), dtype=np.uint8)
+    want[keep] = dense
+    d_dense = _Placed(dense.nbytes, 16, host=dense)
+    ws, ws_ptr, ws_bytes = _workspace(lib, n)
+    n_out = C.c_int64(-1)
+    L.check(lib.arx_filter_count(C.byref(mspan), 0, ws_ptr, ws_bytes, C.byref(n_out), stream))
+    assert n_out.value == S, (tag, n_out.value, S)
+    out = _Placed(n * width, 16)
+    L.check(lib.arx_expand_by_mask(d_dense.ptr, width, C.byref(mspan), ws_ptr, out.ptr, stream))
+    got, untouched = out.read()
+    assert untouched, f"{tag}: bytes around the output were written"
+    assert_equal(got.reshape(n, width), want, tag)
+
+
+def compact_form_of_filter(amd, values_array, mask: HostArray, sel):
+    """What arx_filter_compact_form says about compute.filter(values_array, mask) under the knobs of the moment."""
+    from arrow_amd import _lib as L
+
+    emit = _emit(mask.logical_values(), mask.logical_valid(), sel, mask.valid is not None)
+    w = values_array.type.byte_width
+    return L.get_lib().arx_filter_compact_form(0, w, int(values_array.values_ptr() % 16 == 0), 0, mask.length, int(emit.sum()))

@@ -70,6 +70,21 @@ def test_filter_tuning_variants_agree(gpu_ctx):
                 assert lib.arx_set_option(b"filter_pipe", pipe) == 0
                 for sel in ("drop", "emit_null"):
                     P.check_filter(gpu_ctx, v, m, sel, use_pyarrow=False)
+        # int64 under the automatic choice runs the gather form, which reads neither knob: the forms the knobs do select
+        # are the aligned sweeps, of a narrow type above 25 % and of int64 with the gather form switched off
+        for dtype, offset, sparse in ((np.int32, 8, -1), (np.int64, 2, 0)):
+            v = U.random_array(rng, dtype, 9000, null_p=0.1, offset=offset)
+            m = U.random_mask(rng, 9000, 0.5, null_p=0.05)
+            dv = v.to_device(gpu_ctx)
+            with U.options(lib, {b"filter_sparse": sparse}):
+                for batch in (1, 4):
+                    for pipe in (0, 1):
+                        assert lib.arx_set_option(b"filter_batch", batch) == 0
+                        assert lib.arx_set_option(b"filter_pipe", pipe) == 0
+                        for sel in ("drop", "emit_null"):
+                            want = P.COMPACT_SWEEP_PIPELINED if (batch, pipe) == (4, 1) else P.COMPACT_SWEEP_PLAIN
+                            assert P.compact_form_of_filter(gpu_ctx, dv, m, sel) == want, (dtype, batch, pipe, sel)
+                            P.check_filter(gpu_ctx, v, m, sel, use_pyarrow=False)
 
 
 def test_filter_10m_rows_config1(gpu_ctx):
@@ -1400,3 +1415,95 @@ def test_select_k_and_partition_nth(gpu_ctx):
 def test_sort_boolean_keys(gpu_ctx):
     """Round 6 (f3): boolean sort keys — the counting sort as three GetTakeIndices."""
     P.check_sort_boolean_keys(gpu_ctx, rng_for, scale=100)
+
+
+# ------------------------------------------------------------------ every compaction form the dispatch can choose
+FORM_CELLS = [(w, f) for w in (1, 2, 4, 8, 16) for f in (P.COMPACT_GATHER, P.COMPACT_SWEEP_PIPELINED, P.COMPACT_SWEEP_PLAIN,
+                                                         P.COMPACT_SWEEP_UNALIGNED)] + [(32, P.COMPACT_GATHER)]
+ROW_NUMBER_CELLS = [(2, P.COMPACT_GATHER), (2, P.COMPACT_SWEEP_PIPELINED), (2, P.COMPACT_SWEEP_PLAIN),
+                    (4, P.COMPACT_GATHER), (4, P.COMPACT_SWEEP_PIPELINED), (4, P.COMPACT_SWEEP_PLAIN)]
+
+
+def _form_id(cell):
+    return f"W{cell[0]}-{P.COMPACT_FORM_NAMES[cell[1]]}"
+
+
+@pytest.mark.parametrize("sel", ["drop", "emit_null"])
+@pytest.mark.parametrize("cell", FORM_CELLS, ids=_form_id)
+def test_filter_every_compaction_form(gpu_ctx, cell, sel):
+    """arx_filter_count -> arx_filter_exec at the C ABI, one (width, kernel form, null selection) cell per test: the
+    checker asserts with arx_filter_compact_form that the case runs the form it names before it launches, then
+    compares every output byte and validity bit with numpy (P.filter_form_cases: lengths 1 .. 266 241, selectivities
+    0 .. 1, four null densities, mask bit offsets 0 / 1 / 63, outputs 0 / 1 / 2048/W - 1 elements past a 2 KiB line)."""
+    width, form = cell
+    for kw in P.filter_form_cases(width, form, sel):
+        P.check_filter_form(gpu_ctx, width, form, sel, **kw)
+
+
+def test_filter_32_byte_values_have_no_sweep_form(gpu_ctx):
+    P.check_filter_w32_sweep_is_refused(gpu_ctx)
+
+
+@pytest.mark.parametrize("sel", ["drop", "emit_null"])
+@pytest.mark.parametrize("cell", ROW_NUMBER_CELLS, ids=_form_id)
+def test_mask_to_indices_every_form(gpu_ctx, cell, sel):
+    """arx_mask_to_indices called directly, 2- and 4-byte row numbers under filter_sparse 1 (gather) and 0 (sweep, both
+    batch forms).  Under the sweep, selectivity 0.3 keeps a tile's row numbers inside the LDS ring (each lane walks its
+    own word), 1.0 does not (the 4096-row sweep)."""
+    width, form = cell
+    lengths = [1, 63, 4095, 4096, 4097, 3 * 4096 + 5] + ([65535] if width == 2 else [262144 + 4097])
+    cases = [(n, 0.3) for n in lengths] + [(n, p) for n in lengths[-2:] for p in (0.0, 0.02, 1.0)]
+    for i, (n, p) in enumerate(cases):
+        P.check_mask_to_indices_form(gpu_ctx, width, form, sel, n, moff=(1, 63, 0)[i % 3], true_p=p,
+                                     mnull=(0.3, 0.0, 0.05, 1.0)[i % 4] if n < 4096 or p != 0.3 else 0.3,
+                                     disp=(1, P.kFlushBytes // width - 1, 0)[(i // 2) % 3])
+
+
+def test_mask_to_indices_8_byte_row_numbers(gpu_ctx):
+    """index_width 8: the gather form with DROP, refused (nothing written) under filter_sparse = 0 and for EMIT_NULL."""
+    for i, (n, p) in enumerate([(1, 0.3), (63, 0.3), (4097, 0.3), (3 * 4096 + 5, 1.0), (262144 + 4097, 0.3), (262144 + 4097, 0.02)]):
+        P.check_mask_to_indices_form(gpu_ctx, 8, P.COMPACT_GATHER, "drop", n, moff=(1, 63, 0)[i % 3], true_p=p,
+                                     mnull=(0.3, 0.0)[i % 2], disp=(1, P.kFlushBytes // 8 - 1, 0)[i % 3])
+    P.check_mask_to_indices_width8_refusals(gpu_ctx)
+
+
+@pytest.mark.parametrize("invert", [0, 1])
+def test_bitmap_to_indices(gpu_ctx, invert):
+    """Positions of the set / clear bits; lengths that are no multiple of 64: inverted bits past the end must not appear.
+    Clear bits at 70 % (the sweep) and, on the multi-tile lengths, at 10 % (each lane walks its own word)."""
+    for n in (1, 64, 65, 4097, 262144 + 4097):
+        for off in (0, 1, 63):
+            P.check_bitmap_to_indices(gpu_ctx, n, off, invert)
+    for n in (4097, 262144 + 4097):
+        P.check_bitmap_to_indices(gpu_ctx, n, 63, invert, true_p=0.9)
+        P.check_bitmap_to_indices(gpu_ctx, n, 1, invert, true_p=0.0)
+        P.check_bitmap_to_indices(gpu_ctx, n, 1, invert, true_p=1.0)
+
+
+@pytest.mark.parametrize("width", [1, 2, 4, 8, 16])
+def test_expand_by_mask(gpu_ctx, width):
+    for i, n in enumerate((1, 64, 65, 4097, 262144 + 4097)):
+        P.check_expand_by_mask(gpu_ctx, width, n, (1, 63, 0)[i % 3], 0.0)
+        P.check_expand_by_mask(gpu_ctx, width, n, (63, 0, 1)[i % 3], 0.2)
+
+
+def test_every_compaction_form_cell_was_asserted(gpu_ctx):
+    """Runs the 63-row case of every cell (so that this test stands alone), then reads the checker's own tally: every
+    (kind, width, form, null selection) cell has cases whose arx_filter_compact_form assertion held.  Prints the tally:
+    after a run of the whole file it holds the counts of the whole matrix."""
+    for sel in ("drop", "emit_null"):
+        for width, form in FORM_CELLS:
+            P.check_filter_form(gpu_ctx, width, form, sel, 63, moff=1, mnull=0.3)
+        for width, form in ROW_NUMBER_CELLS:
+            P.check_mask_to_indices_form(gpu_ctx, width, form, sel, 63, moff=1, mnull=0.3)
+    P.check_mask_to_indices_form(gpu_ctx, 8, P.COMPACT_GATHER, "drop", 63)
+    for invert in (0, 1):
+        P.check_bitmap_to_indices(gpu_ctx, 65, 1, invert)
+    cells = [("values", w, P.COMPACT_FORM_NAMES[f], s) for w, f in FORM_CELLS for s in ("drop", "emit_null")]
+    cells += [("row_numbers", w, P.COMPACT_FORM_NAMES[f], s) for w, f in ROW_NUMBER_CELLS for s in ("drop", "emit_null")]
+    cells += [("row_numbers", 8, "gather", "drop"), ("bit_positions", 4, "gather", "drop")]
+    for key in sorted(P.FORM_HITS):
+        print("compaction form cases", *key, P.FORM_HITS[key])
+    assert [c for c in cells if P.FORM_HITS.get(c, 0) == 0] == []
+    assert any(k[0] == "bit_positions_inverted" and k[2].startswith("sweep") for k in P.FORM_HITS)
+    assert not [k for k in P.FORM_HITS if k[1] == 32 and k[2] != "gather"]
