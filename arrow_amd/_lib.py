@@ -235,6 +235,7 @@ SIGNATURES = {
     "arx_set_lookup_index_in_binary": (_int, [_p, _bspan, _int, _int, _bspan, _int, _int, _p, _p, _p]),
     "arx_match_substring": (_int, [_bspan, _int, _int, _p, _i64, _i64, _int, _p, _p]),
     "arx_if_else": (_int, [_int, _span, _span, _p, _span, _p, _i64, _p, _p, _p]),
+    "arx_temporal_component": (_int, [_int, _int, _span, _i64, _int, _int, _p, _p, _p]),
     "arx_hash_join_workspace_bytes": (_sz, [_i64]),
     "arx_hash_join_key_validity": (_int, [_span, _int, _i64, _p, _p]),
     "arx_hash_join_bool_key": (_int, [_span, _p, _p]),

@@ -94,6 +94,15 @@ class MatchSubstringOptions(FunctionOptions):
         self.ignore_case = bool(ignore_case)
 
 
+class DayOfWeekOptions(FunctionOptions):
+    """api_scalar.h DayOfWeekOptions: count_from_zero (Monday = 0 rather than 1 at the defaults) and week_start, the ISO
+    weekday (Monday = 1 .. Sunday = 7) the numbering starts at."""
+
+    def __init__(self, count_from_zero: bool = True, week_start: int = 1):
+        self.count_from_zero = bool(count_from_zero)
+        self.week_start = int(week_start)
+
+
 # --------------------------------------------------------------------------- scratch space
 _tls = threading.local()
 
@@ -1032,6 +1041,12 @@ def _build_registry() -> FunctionRegistry:
     f = Function("if_else", Function.SCALAR, 3)
     f.add_kernel(Kernel((bool_, _IF_ELSE_VALUE, _IF_ELSE_VALUE), _exec_if_else))
     reg.add_function(f)
+
+    # year .. iso_week of dates and timestamps, hour .. nanosecond of timestamps and times (csrc/temporal.hip)
+    for name in _TEMPORAL_COMPONENTS:
+        f = Function(name, Function.SCALAR, 1, DayOfWeekOptions() if name == "day_of_week" else None)
+        f.add_kernel(Kernel((_temporal_input(name),), _exec_temporal(name), int64))
+        reg.add_function(f)
 
     f = Function("hash_sum", Function.HASH_AGGREGATE, 2, ScalarAggregateOptions())
     f.add_kernel(HashAggregateKernel((int64, uint32), _hash_sum_init, _hash_sum_resize,
@@ -2483,6 +2498,107 @@ def if_else(cond: Array, left, right) -> Array:
                                        "arrow_amd.Scalar on one side")
     wrap = lambda x: x if isinstance(x, (Array, Scalar)) else Scalar(x, typed[0], x is not None)  # noqa: E731
     return call_function("if_else", [cond, wrap(left), wrap(right)])
+
+
+# --------------------------------------------------------------------------- date / time fields
+# Year .. ISOWeek, Hour .. Nanosecond (compute/kernels/scalar_temporal_unary.cc): csrc/temporal.hip.  name -> ARX_TEMPORAL_*
+_TEMPORAL_COMPONENTS = {"year": 0, "quarter": 1, "month": 2, "day": 3, "day_of_week": 4, "day_of_year": 5, "iso_year": 6,
+                        "iso_week": 7, "hour": 8, "minute": 9, "second": 10, "millisecond": 11, "microsecond": 12,
+                        "nanosecond": 13}
+# type name (a timestamp's without its zone) -> ARX_TIME_*
+_TEMPORAL_INPUTS = {"date32[day]": 0, "date64[ms]": 1, "timestamp[s]": 2, "timestamp[ms]": 3, "timestamp[us]": 4,
+                    "timestamp[ns]": 5, "time32[s]": 6, "time32[ms]": 7, "time64[us]": 8, "time64[ns]": 9}
+
+
+def _without_zone(name: str) -> str:
+    """A type's name without a timestamp's zone: timestamp[us, tz=UTC] -> timestamp[us]."""
+    unit, sep, _ = name.partition(", tz=")
+    return unit + "]" if sep else name
+
+
+def _temporal_input_code(t: DataType):
+    return _TEMPORAL_INPUTS.get(_without_zone(t.name))
+
+
+def _temporal_input(name: str):
+    """The reference's kernel lists: calendar fields take dates and timestamps, time-of-day fields timestamps and times
+    (a timestamp matches by unit whatever its zone; the exec refuses a zone)."""
+    calendar = _TEMPORAL_COMPONENTS[name] <= 7
+
+    def matches(t: DataType) -> bool:
+        code = _temporal_input_code(t)
+        return code is not None and (code <= 5 if calendar else code >= 2)
+    return matches
+
+
+def _exec_temporal(name: str):
+    component = _TEMPORAL_COMPONENTS[name]
+
+    def run(args, options):
+        (values,) = args
+        if not isinstance(values, Array):
+            raise ArrowNotImplementedError(f"arrow_amd: {name} of a scalar on the device path")
+        if _without_zone(values.type.name) != values.type.name:
+            raise ArrowNotImplementedError(f"arrow_amd: {name} of {values.type.name} on device-resident arrays: time zones need "
+                                           "the tz database, which has no device kernel")
+        options = options or DayOfWeekOptions()
+        week_start, count_from_zero = (options.week_start, options.count_from_zero) if name == "day_of_week" else (1, True)
+        if not 1 <= week_start <= 7:
+            raise ArrowInvalid(f"week_start must follow ISO convention (Monday=1, Sunday=7). Got week_start={week_start}")
+        n = values.length
+        dev = values.device
+        lib, stream = _lib_and_stream(dev)
+        known = values._null_count          # (a pending device-side count stays pending: no read-back here)
+        nulls = values.validity is not None and (callable(known) or known != 0)
+        vspan = _lib.ArxSpan(values.validity.data_ptr() if nulls else None, values.data.data_ptr(), values.offset, n,
+                             kUnknownNullCount if callable(known) else int(known))
+        out = alloc(n * 8, dev)
+        valid = alloc(bitmap_nbytes(n), dev) if nulls else None
+        with tracing.span("arx_temporal_component"):
+            check(lib.arx_temporal_component(component, _temporal_input_code(values.type), C.byref(vspan), n, week_start,
+                                             1 if count_from_zero else 0, out.data_ptr(), _ptr_or_none(valid), stream))
+        if not nulls:
+            return Array(int64, n, [None, out], 0, 0)
+        res = Array(int64, n, [valid, out], kUnknownNullCount, 0)
+        if callable(known) or known == kUnknownNullCount:
+            nbytes = (n + 7) // 8
+            res.set_lazy_null_count(
+                lambda: n - int(np.unpackbits(valid[:nbytes].cpu().numpy(), bitorder="little")[:n].sum()) if n else 0)
+        else:
+            res._null_count = int(known)
+        return res
+    return run
+
+
+def _temporal_wrapper(name: str, doc: str):
+    def f(values: Array) -> Array:
+        return call_function(name, [values])
+    f.__name__ = f.__qualname__ = name
+    f.__doc__ = (f"compute::{doc} (scalar_temporal_unary.cc): an int64 Array on the device, null where `values` is null (no "
+                 "validity buffer when `values` has none; the null count is the input's).  Proleptic Gregorian calendar, floor "
+                 "division before the epoch, no time zones (a zoned timestamp raises ArrowNotImplementedError).")
+    return f
+
+
+year = _temporal_wrapper("year", "Year")
+quarter = _temporal_wrapper("quarter", "Quarter")
+month = _temporal_wrapper("month", "Month")
+day = _temporal_wrapper("day", "Day")
+day_of_year = _temporal_wrapper("day_of_year", "DayOfYear")
+iso_year = _temporal_wrapper("iso_year", "ISOYear")
+iso_week = _temporal_wrapper("iso_week", "ISOWeek")
+hour = _temporal_wrapper("hour", "Hour")
+minute = _temporal_wrapper("minute", "Minute")
+second = _temporal_wrapper("second", "Second")
+millisecond = _temporal_wrapper("millisecond", "Millisecond")
+microsecond = _temporal_wrapper("microsecond", "Microsecond")
+nanosecond = _temporal_wrapper("nanosecond", "Nanosecond")
+
+
+def day_of_week(values: Array, *, count_from_zero: bool = True, week_start: int = 1) -> Array:
+    """compute::DayOfWeek: (ISO weekday - week_start + 7) % 7, plus 1 unless count_from_zero; Monday = 0 at the defaults.
+    week_start outside 1 .. 7 raises ArrowInvalid with the reference's text.  See year."""
+    return call_function("day_of_week", [values], DayOfWeekOptions(count_from_zero, week_start))
 
 
 # --------------------------------------------------------------------------- hash join

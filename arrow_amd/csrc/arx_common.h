@@ -85,6 +85,7 @@ CounterTable sort_counters();
 CounterTable set_lookup_counters();
 CounterTable match_substring_counters();
 CounterTable if_else_counters();
+CounterTable temporal_counters();
 
 #define ARX_HIP(call)                                          \
   do {                                                         \

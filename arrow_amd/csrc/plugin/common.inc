@@ -90,11 +90,15 @@ std::atomic<int64_t> g_string_key_hash_collisions{0};   // batches regrouped by 
 // silent route through the stock CPU kernel is a test failure, not a pass)
 enum Fn { kFnFilter = 0, kFnTake, kFnGreater, kFnSort, kFnCast, kFnHashSum, kFnAdd, kFnBoolean, kFnCompare, kFnParquet,
           kFnReduce, kFnOrderBy, kFnTakeColumns, kFnUnique, kFnCoalesce, kFnIsIn, kFnIndexIn, kFnHashJoin,
-          kFnMatchSubstring, kFnStartsWith, kFnEndsWith, kFnIfElse, kNumFn };
+          kFnMatchSubstring, kFnStartsWith, kFnEndsWith, kFnIfElse, kFnYear, kFnQuarter, kFnMonth, kFnDay, kFnDayOfWeek,
+          kFnDayOfYear, kFnIsoYear, kFnIsoWeek, kFnHour, kFnMinute, kFnSecond, kFnMillisecond, kFnMicrosecond, kFnNanosecond,
+          kNumFn };
 const char* const kFnNames[kNumFn] = {"array_filter", "array_take", "greater", "array_sort_indices",
                                       "cast", "hash_sum", "add", "boolean", "compare", "parquet", "reduce", "order_by",
                                       "take_columns", "unique", "coalesce", "is_in", "index_in", "hashjoin",
-                                      "match_substring", "starts_with", "ends_with", "if_else"};
+                                      "match_substring", "starts_with", "ends_with", "if_else", "year", "quarter", "month", "day",
+                                      "day_of_week", "day_of_year", "iso_year", "iso_week", "hour", "minute", "second",
+                                      "millisecond", "microsecond", "nanosecond"};
 std::atomic<int64_t> g_fn_gpu[kNumFn];
 std::atomic<int64_t> g_fn_stock[kNumFn];
 void CountGpu(Fn f) {

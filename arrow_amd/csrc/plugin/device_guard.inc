@@ -223,16 +223,18 @@ Status GuardAggregateKernels(cp::Function* fn, int num_stock) {
   return Status::OK();
 }
 
-// the functions whose kernel lists the shim appends to — and the string-search siblings of match_substring, to which it
-// adds nothing (every kernel of theirs is the reference's, so every one gets a guard): a device-resident input is
-// refused by name instead of being read by a CPU kernel
+// the functions whose kernel lists the shim appends to — and the string-search siblings of match_substring and the
+// temporal siblings of year .. nanosecond, to which it adds nothing (every kernel of theirs is the reference's, so every
+// one gets a guard): a device-resident input is refused by name instead of being read by a CPU kernel
 const char* const kGuardedFunctions[] = {
     "array_filter", "array_take", "array_sort_indices", "equal", "not_equal", "greater", "greater_equal", "less", "less_equal",
     "add", "subtract", "multiply", "divide", "add_checked", "subtract_checked", "multiply_checked", "divide_checked",
     "and_kleene", "or_kleene", "invert", "unique", "value_counts", "dictionary_encode", "indices_nonzero",
     "sum", "mean", "min_max", "min", "max", "coalesce", "is_in", "index_in", "match_substring", "starts_with", "ends_with",
     "match_like", "match_substring_regex", "find_substring", "find_substring_regex", "count_substring",
-    "count_substring_regex", "if_else"};
+    "count_substring_regex", "if_else", "year", "quarter", "month", "day", "day_of_week", "day_of_year", "iso_year", "iso_week",
+    "hour", "minute", "second", "millisecond", "microsecond", "nanosecond", "is_leap_year", "subsecond", "week", "us_week",
+    "us_year", "year_month_day", "iso_calendar", "strftime", "floor_temporal", "ceil_temporal", "round_temporal"};
 
 // before the shim registers anything: how many kernels of each guarded function are the reference's
 arrow::Result<std::vector<int>> CountStockKernels(cp::FunctionRegistry* reg) {

@@ -1301,6 +1301,55 @@ int arx_match_substring(const ArxBinarySpan* values, int offset_width, int op, c
  * counts the launches of the kernel of widths 8 and 16, of widths 1, 2 and 4 (8 / width rows a lane) and of booleans. */
 int arx_if_else(int byte_width, const ArxSpan* cond, const ArxSpan* left, const void* left_scalar, const ArxSpan* right,
                 const void* right_scalar, int64_t length, void* out_data, void* out_validity, void* stream);
+/* Date / time field extraction (Year .. ISOWeek, Hour .. Nanosecond, compute/kernels/scalar_temporal_unary.cc; csrc/temporal.hip):
+ * out[i] = the `component` of values[i] as int64, in the proleptic Gregorian calendar without a time zone; every division
+ * is a floor division, so instants before the epoch are right (timestamp[ms] -1: year 1969, hour 23, millisecond 999).
+ * millisecond / microsecond / nanosecond are the three-digit fields (0 .. 999); quarter = (month - 1) / 3 + 1; iso_year /
+ * iso_week follow ISO 8601; day_of_week = (ISO weekday - week_start + 7) % 7 + (count_from_zero ? 0 : 1), week_start 1
+ * (Monday) .. 7 (Sunday), both ignored by the other components apart from the range check.
+ * in_type: the physical type and unit of values.  The calendar components ARX_TEMPORAL_YEAR .. ARX_TEMPORAL_ISO_WEEK take
+ * ARX_TIME_DATE32 .. ARX_TIME_TIMESTAMP_NS, the time-of-day components ARX_TEMPORAL_HOUR .. ARX_TEMPORAL_NANOSECOND take
+ * ARX_TIME_TIMESTAMP_S .. ARX_TIME_TIME64_NS (the reference's kernel lists).  values carries its own offset; the output
+ * starts at offset 0: length * 8 data bytes, and the input's validity in ceil(length / 64) whole words (padding bits zero).
+ * A null slot is written as zero and its bytes never enter the arithmetic.  out_validity may be NULL exactly when
+ * values->validity is NULL.  Results equal the reference's for every instant of the years -32767 .. 32767; beyond, the day
+ * count wraps to 32 bits and the result is a function of the row's value alone.
+ * ARX_INVALID, with nothing launched or written, for a component / in_type pair outside the above, a week_start outside
+ * 1 .. 7, a negative length, NULL values, a span whose length is not `length`, and for length > 0 a NULL out_data or data
+ * buffer and a NULL out_validity that is required; length == 0 succeeds, launches nothing and writes nothing.
+ * Asynchronous; no read-back.  arx_get_counter("temporal_civil_launches" / "temporal_iso_launches" /
+ * "temporal_weekday_launches" / "temporal_time_launches") counts the launches of each decomposition group: year, quarter,
+ * month, day, day_of_year / iso_year, iso_week / day_of_week / hour .. nanosecond. */
+enum {
+  ARX_TEMPORAL_YEAR = 0,
+  ARX_TEMPORAL_QUARTER = 1,
+  ARX_TEMPORAL_MONTH = 2,
+  ARX_TEMPORAL_DAY = 3,
+  ARX_TEMPORAL_DAY_OF_WEEK = 4,
+  ARX_TEMPORAL_DAY_OF_YEAR = 5,
+  ARX_TEMPORAL_ISO_YEAR = 6,
+  ARX_TEMPORAL_ISO_WEEK = 7,
+  ARX_TEMPORAL_HOUR = 8,
+  ARX_TEMPORAL_MINUTE = 9,
+  ARX_TEMPORAL_SECOND = 10,
+  ARX_TEMPORAL_MILLISECOND = 11,
+  ARX_TEMPORAL_MICROSECOND = 12,
+  ARX_TEMPORAL_NANOSECOND = 13
+};
+enum {
+  ARX_TIME_DATE32 = 0,
+  ARX_TIME_DATE64 = 1,
+  ARX_TIME_TIMESTAMP_S = 2,
+  ARX_TIME_TIMESTAMP_MS = 3,
+  ARX_TIME_TIMESTAMP_US = 4,
+  ARX_TIME_TIMESTAMP_NS = 5,
+  ARX_TIME_TIME32_S = 6,
+  ARX_TIME_TIME32_MS = 7,
+  ARX_TIME_TIME64_US = 8,
+  ARX_TIME_TIME64_NS = 9
+};
+int arx_temporal_component(int component, int in_type, const ArxSpan* values, int64_t length, int week_start, int count_from_zero,
+                           void* out_data, void* out_validity, void* stream);
 
 /* Hash join — the equi-join of HashJoinNode (acero/hash_join_node.cc; SwissJoin, acero/swiss_join.cc) after the Grouper:
  * the right (build) input's key rows are consumed (arx_grouper_consume: dense uint32 ids, G groups), the left (probe)
