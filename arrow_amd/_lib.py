@@ -234,6 +234,10 @@ SIGNATURES = {
     "arx_set_lookup_is_in_binary": (_int, [_p, _bspan, _int, _int, _bspan, _int, _int, _p, _p]),
     "arx_set_lookup_index_in_binary": (_int, [_p, _bspan, _int, _int, _bspan, _int, _int, _p, _p, _p]),
     "arx_match_substring": (_int, [_bspan, _int, _int, _p, _i64, _i64, _int, _p, _p]),
+    "arx_string_length": (_int, [_bspan, _int, _int, _i64, _int, _p, _p]),
+    "arx_string_slice_workspace_bytes": (_sz, [_i64, _int]),
+    "arx_string_slice_offsets": (_int, [_bspan, _int, _int, _i64, _i64, _i64, _int, _p, _sz, _p, C.POINTER(_i64), _p]),
+    "arx_string_slice_data": (_int, [_bspan, _int, _p, _sz, _p, _i64, _p, _p]),
     "arx_if_else": (_int, [_int, _span, _span, _p, _span, _p, _i64, _p, _p, _p]),
     "arx_temporal_component": (_int, [_int, _int, _span, _i64, _int, _int, _p, _p, _p]),
     "arx_hash_join_workspace_bytes": (_sz, [_i64]),

@@ -94,6 +94,15 @@ class MatchSubstringOptions(FunctionOptions):
         self.ignore_case = bool(ignore_case)
 
 
+class SliceOptions(FunctionOptions):
+    """api_scalar.h SliceOptions: start, stop (None: to the row's end) and step, as Python's slice takes them."""
+
+    def __init__(self, start: int = 0, stop=None, step: int = 1):
+        self.start = int(start)
+        self.stop = None if stop is None else int(stop)
+        self.step = int(step)
+
+
 class DayOfWeekOptions(FunctionOptions):
     """api_scalar.h DayOfWeekOptions: count_from_zero (Monday = 0 rather than 1 at the defaults) and week_start, the ISO
     weekday (Monday = 1 .. Sunday = 7) the numbering starts at."""
@@ -1035,6 +1044,16 @@ def _build_registry() -> FunctionRegistry:
     for name in _MATCH_OPS:
         f = Function(name, Function.SCALAR, 1, MatchSubstringOptions())
         f.add_kernel(Kernel((_BASE_BINARY,), _exec_match_substring(name), bool_))
+        reg.add_function(f)
+
+    # lengths and slices of utf8 / binary rows (csrc/string_slice.hip)
+    for name in ("binary_length", "utf8_length"):
+        f = Function(name, Function.SCALAR, 1)
+        f.add_kernel(Kernel((_STRING_INPUT[name],), _exec_string_length(name), int32))
+        reg.add_function(f)
+    for name in ("binary_slice", "utf8_slice_codeunits"):
+        f = Function(name, Function.SCALAR, 1, SliceOptions())
+        f.add_kernel(Kernel((_STRING_INPUT[name],), _exec_string_slice(name)))
         reg.add_function(f)
 
     # if_else(cond, left, right): left / right of ONE type, boolean or 1 / 2 / 4 / 8 bytes wide (csrc/if_else.hip)
@@ -2427,6 +2446,135 @@ def starts_with(values: Array, pattern, *, ignore_case: bool = False) -> Array:
 def ends_with(values: Array, pattern, *, ignore_case: bool = False) -> Array:
     """compute::EndsWith: true where the row's last bytes are `pattern`.  See match_substring."""
     return _call_match_substring("ends_with", values, pattern, ignore_case)
+
+
+# --------------------------------------------------------------------------- string lengths and slices
+# binary_length / utf8_length / binary_slice / utf8_slice_codeunits (compute/kernels/scalar_string_ascii.cc,
+# scalar_string_utf8.cc): csrc/string_slice.hip.  The `path` handed to arx_string_length / arx_string_slice_offsets for
+# the codepoint walk: 0 = the library chooses (rows, or waves from a mean row size on), 1 = one lane per row, 2 = one
+# wave per row.  Tests set it to reach either form.
+STRING_SLICE_PATH = 0
+_STRING_UNIT = {"binary_length": 0, "utf8_length": 1, "binary_slice": 0, "utf8_slice_codeunits": 1}
+_NO_STOP = 2**63 - 1            # stop = INT64_MAX: to the row's end
+_BINARY_ONLY = lambda t: t.name == "binary"  # noqa: E731
+_UTF8_ONLY = lambda t: t.name == "string"  # noqa: E731
+
+
+def _input_validity(values: Array, lib, stream):
+    """The input's validity at offset 0 for a result of the same rows: (buffer | None, null count | a lazy count)."""
+    n = values.length
+    if values.validity is None:
+        return None, 0
+    valid = alloc(bitmap_nbytes(n), values.device)
+    check(lib.arx_bitmap_copy(values.validity.data_ptr(), values.offset, n, valid.data_ptr(), stream))
+    known = values._null_count
+    if not callable(known) and known != kUnknownNullCount:
+        return valid, int(known)
+    nbytes = (n + 7) // 8
+    return valid, (lambda: n - int(np.unpackbits(valid[:nbytes].cpu().numpy(), bitorder="little")[:n].sum()) if n else 0)
+
+
+def _with_null_count(out: Array, count) -> Array:
+    if callable(count):
+        out.set_lazy_null_count(count)
+    else:
+        out._null_count = count
+    return out
+
+
+def _data_bytes_hint(values: Array) -> int:
+    return int(values.buffers[2].numel()) if values.buffers[2] is not None else -1
+
+
+def _exec_string_length(name: str):
+    def run(args, options):
+        (values,) = args
+        if not isinstance(values, Array):
+            raise ArrowNotImplementedError(f"arrow_amd: {name} of a scalar on the device path")
+        lib, stream = _lib_and_stream(values.device)
+        n = values.length
+        out = alloc(max(n, 1) * 4, values.device)
+        vspan = values.binary_span()
+        with tracing.span("arx_string_length"):
+            check(lib.arx_string_length(C.byref(vspan), 4, _STRING_UNIT[name], _data_bytes_hint(values), int(STRING_SLICE_PATH),
+                                        out.data_ptr(), stream))
+        valid, count = _input_validity(values, lib, stream)
+        return _with_null_count(Array(int32, n, [valid, out], kUnknownNullCount, 0), count)
+    return run
+
+
+def _exec_string_slice(name: str):
+    def run(args, options):
+        (values,) = args
+        if not isinstance(values, Array):
+            raise ArrowNotImplementedError(f"arrow_amd: {name} of a scalar on the device path")
+        options = options or SliceOptions(0)
+        if options.step == 0:
+            raise ArrowInvalid("Slice step cannot be zero")
+        if options.step != 1:
+            raise ArrowNotImplementedError(f"arrow_amd: {name} with step={options.step} on device-resident arrays: only step=1 has "
+                                           "a device kernel")
+        dev = values.device
+        lib, stream = _lib_and_stream(dev)
+        n = values.length
+        clamp = lambda x: max(-2**63, min(int(x), 2**63 - 2))  # noqa: E731  (INT64_MAX itself means "no stop")
+        stop = _NO_STOP if options.stop is None else clamp(options.stop)
+        out_offsets = alloc((n + 1) * 4, dev)
+        ws = _workspace(dev, lib.arx_string_slice_workspace_bytes(n, 4), "string_slice")
+        total = C.c_int64(0)
+        vspan = values.binary_span()
+        with tracing.span("arx_string_slice_offsets"):
+            check(lib.arx_string_slice_offsets(C.byref(vspan), 4, _STRING_UNIT[name], clamp(options.start), stop, _data_bytes_hint(values),
+                                               int(STRING_SLICE_PATH), ws.data_ptr(), ws.numel(), out_offsets.data_ptr(),
+                                               C.byref(total), stream))
+        out_data = alloc(total.value, dev)
+        with tracing.span("arx_string_slice_data"):
+            check(lib.arx_string_slice_data(C.byref(vspan), 4, ws.data_ptr(), ws.numel(), out_offsets.data_ptr(), total.value,
+                                            out_data.data_ptr(), stream))
+        valid, count = _input_validity(values, lib, stream)
+        return _with_null_count(Array(values.type, n, [valid, out_offsets, out_data], kUnknownNullCount, 0), count)
+    return run
+
+
+def _call_string_function(name: str, values, options, *reference_args) -> Array:
+    import pyarrow as pa
+    import pyarrow.compute as pc
+
+    if not isinstance(values, Array):
+        raise TypeError(f"{name}: values must be an arrow_amd.Array")
+    if not _STRING_INPUT[name](values.type):
+        # the reference's own "has no kernel matching input types" error, from a zero-length call
+        getattr(pc, name)(pa.array([], _pa_type(values.type)), *reference_args)
+    return call_function(name, [values], options)
+
+
+_STRING_INPUT = {"binary_length": is_base_binary, "utf8_length": _UTF8_ONLY, "binary_slice": _BINARY_ONLY,
+                 "utf8_slice_codeunits": _UTF8_ONLY}
+
+
+def binary_length(values: Array) -> Array:
+    """compute::BinaryLength: int32, the bytes of each row of a utf8 / binary array; null where the row is null.  The
+    result stays on the device."""
+    return _call_string_function("binary_length", values, None)
+
+
+def utf8_length(values: Array) -> Array:
+    """compute::UTF8Length: int32, the codepoints of each row of a utf8 array (every byte that is not a continuation byte
+    counts one, valid UTF-8 or not); null where the row is null.  The result stays on the device."""
+    return _call_string_function("utf8_length", values, None)
+
+
+def binary_slice(values: Array, start: int, stop=None, step: int = 1) -> Array:
+    """compute::BinarySlice under SliceOptions: Python's b[start:stop] of each row of a binary array; a null row stays
+    null and holds no bytes.  step=0 raises the reference's ArrowInvalid, any other step but 1 ArrowNotImplementedError
+    (there is no CPU fallback).  The result stays on the device."""
+    return _call_string_function("binary_slice", values, SliceOptions(start, stop, step), 0)
+
+
+def utf8_slice_codeunits(values: Array, start: int, stop=None, step: int = 1) -> Array:
+    """compute::UTF8SliceCodeunits under SliceOptions: Python's s[start:stop] of each row of a utf8 array, counted in
+    codepoints.  See binary_slice."""
+    return _call_string_function("utf8_slice_codeunits", values, SliceOptions(start, stop, step), 0)
 
 
 # --------------------------------------------------------------------------- if_else

@@ -86,6 +86,7 @@ CounterTable set_lookup_counters();
 CounterTable match_substring_counters();
 CounterTable if_else_counters();
 CounterTable temporal_counters();
+CounterTable string_slice_counters();
 
 #define ARX_HIP(call)                                          \
   do {                                                         \

@@ -14,13 +14,11 @@
 //   bin_scan_blocks: exclusive scan of the workgroup totals (one workgroup)
 //   bin_offsets   : exclusive scan inside each workgroup's 4096 slots + its base -> out offsets
 //   bin_copy      : output-centric, one workgroup per 16 KiB of output bytes (dense dword stores)
-#include "arx_common.h"
+#include "binary_scan_copy.h"
 
 #include <algorithm>
 
 namespace arx {
-
-constexpr int kBinRows = kBlock * 16;  // output slots per workgroup
 
 struct BinTakeArgs {
   const void* offsets;      // element 0 of the logical values array: int32 (utf8 / binary) or int64 (large_utf8 / large_binary) entries
@@ -290,18 +288,56 @@ static int make_args(const ArxBinarySpan* values, const ArxSpan* indices, int in
   return ARX_OK;
 }
 
+// workspace: [workgroup byte totals, 64-bit][source start of every output slot, one offset each]
+size_t bin_sums_bytes(int64_t num_indices) {
+  return (static_cast<size_t>(ceil_div(num_indices, kBinRows) + 2) * 8 + 63) & ~static_cast<size_t>(63);
+}
+size_t bin_workspace_bytes(int64_t num_indices, int offset_width) {
+  if (num_indices < 0) num_indices = 0;
+  return bin_sums_bytes(num_indices) + static_cast<size_t>(num_indices) * offset_width + 64;
+}
+
+template <typename O>
+int bin_scan_lengths(O* out_offsets, int64_t length, long long* sums, const char* what, int64_t* out_total, hipStream_t st) {
+  const int64_t nblocks = ceil_div(length, kBinRows);
+  hipLaunchKernelGGL(bin_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, sums, nblocks);
+  ARX_CHECK_LAUNCH("bin_scan_blocks_kernel");
+  long long total = 0;
+  ARX_HIP(hipMemcpyAsync(&total, sums + nblocks, 8, hipMemcpyDeviceToHost, st));
+  ARX_HIP(hipStreamSynchronize(st));
+  if (sizeof(O) == 4 && total > 2147483647LL) {
+    // the reference's offset builder overflows the same way (int32 offsets)
+    set_error("offset overflow while %s: %lld bytes do not fit int32 offsets", what, total);
+    return ARX_INVALID;
+  }
+  hipLaunchKernelGGL(bin_offsets_kernel<O>, dim3(static_cast<unsigned>(nblocks)), dim3(kBlock), 0, st, out_offsets, length, sums);
+  ARX_CHECK_LAUNCH("bin_offsets_kernel");
+  *out_total = total;
+  return ARX_OK;
+}
+template int bin_scan_lengths<int32_t>(int32_t*, int64_t, long long*, const char*, int64_t*, hipStream_t);
+template int bin_scan_lengths<int64_t>(int64_t*, int64_t, long long*, const char*, int64_t*, hipStream_t);
+
+template <typename O>
+int bin_copy_rows(const uint8_t* data, const O* src_start, const O* out_offsets, int64_t rows, int64_t copy_bytes, uint8_t* out_data,
+                  int shift, hipStream_t st) {
+  const int64_t chunks = ceil_div(copy_bytes, kBinChunk);
+  if (chunks > 0x7FFFFFFFll) {
+    set_error("binary take: %lld output bytes are more than one launch takes", static_cast<long long>(copy_bytes >> shift));
+    return ARX_NOT_IMPLEMENTED;
+  }
+  hipLaunchKernelGGL(bin_copy_kernel<O>, dim3(static_cast<unsigned>(chunks)), dim3(kBlock), 0, st, data, src_start, out_offsets, rows,
+                     copy_bytes, out_data, shift);
+  ARX_CHECK_LAUNCH("bin_copy_kernel");
+  return ARX_OK;
+}
+template int bin_copy_rows<int32_t>(const uint8_t*, const int32_t*, const int32_t*, int64_t, int64_t, uint8_t*, int, hipStream_t);
+template int bin_copy_rows<int64_t>(const uint8_t*, const int64_t*, const int64_t*, int64_t, int64_t, uint8_t*, int, hipStream_t);
+
 }  // namespace arx
 
 using namespace arx;
 
-// workspace: [workgroup byte totals, 64-bit][source start of every output slot, one offset each]
-static size_t bin_sums_bytes(int64_t num_indices) {
-  return (static_cast<size_t>(ceil_div(num_indices, kBinRows) + 2) * 8 + 63) & ~static_cast<size_t>(63);
-}
-static size_t bin_workspace_bytes(int64_t num_indices, int offset_width) {
-  if (num_indices < 0) num_indices = 0;
-  return bin_sums_bytes(num_indices) + static_cast<size_t>(num_indices) * offset_width + 64;
-}
 
 template <typename O>
 static int binary_take_offsets(const ArxBinarySpan* values, const ArxSpan* indices, int index_type, void* ws, size_t ws_bytes,
@@ -334,21 +370,7 @@ static int binary_take_offsets(const ArxBinarySpan* values, const ArxSpan* indic
   hipLaunchKernelGGL(bin_lengths_kernel<O>, dim3(static_cast<unsigned>(nblocks)), dim3(kBlock), 0, st, a, out_offsets,
                      src_start, static_cast<uint64_t*>(out_validity), reinterpret_cast<unsigned long long*>(valid_count), sums);
   ARX_CHECK_LAUNCH("bin_lengths_kernel");
-  hipLaunchKernelGGL(bin_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, sums, nblocks);
-  ARX_CHECK_LAUNCH("bin_scan_blocks_kernel");
-  long long total = 0;
-  ARX_HIP(hipMemcpyAsync(&total, sums + nblocks, 8, hipMemcpyDeviceToHost, st));
-  ARX_HIP(hipStreamSynchronize(st));
-  if (sizeof(O) == 4 && total > 2147483647LL) {
-    // the reference's offset builder overflows the same way (int32 offsets)
-    set_error("offset overflow while taking from a binary array: %lld bytes do not fit int32 offsets", total);
-    return ARX_INVALID;
-  }
-  hipLaunchKernelGGL(bin_offsets_kernel<O>, dim3(static_cast<unsigned>(nblocks)), dim3(kBlock), 0, st, out_offsets,
-                     a.length, sums);
-  ARX_CHECK_LAUNCH("bin_offsets_kernel");
-  *out_total_bytes = total;
-  return ARX_OK;
+  return bin_scan_lengths<O>(out_offsets, a.length, sums, "taking from a binary array", out_total_bytes, st);
 }
 
 // shift: see bin_copy_kernel — total_bytes stays what the offsets count (elements for a list), the copy moves it << shift
@@ -370,17 +392,8 @@ static int binary_take_data(const ArxBinarySpan* values, int64_t num_indices, co
     return ARX_INVALID;
   }
   const O* src_start = reinterpret_cast<const O*>(static_cast<const uint8_t*>(ws) + bin_sums_bytes(num_indices));
-  const int64_t copy_bytes = total_bytes << shift;
-  const int64_t chunks = ceil_div(copy_bytes, kBinChunk);
-  if (chunks > 0x7FFFFFFFll) {
-    set_error("binary take: %lld output bytes are more than one launch takes", static_cast<long long>(total_bytes));
-    return ARX_NOT_IMPLEMENTED;
-  }
-  hipLaunchKernelGGL(bin_copy_kernel<O>, dim3(static_cast<unsigned>(chunks)), dim3(kBlock), 0, as_stream(stream),
-                     static_cast<const uint8_t*>(values->data), src_start, out_offsets, num_indices, copy_bytes,
-                     static_cast<uint8_t*>(out_data), shift);
-  ARX_CHECK_LAUNCH("bin_copy_kernel");
-  return ARX_OK;
+  return bin_copy_rows<O>(static_cast<const uint8_t*>(values->data), src_start, out_offsets, num_indices, total_bytes << shift,
+                          static_cast<uint8_t*>(out_data), shift, as_stream(stream));
 }
 
 extern "C" {

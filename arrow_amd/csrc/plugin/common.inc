@@ -92,13 +92,14 @@ enum Fn { kFnFilter = 0, kFnTake, kFnGreater, kFnSort, kFnCast, kFnHashSum, kFnA
           kFnReduce, kFnOrderBy, kFnTakeColumns, kFnUnique, kFnCoalesce, kFnIsIn, kFnIndexIn, kFnHashJoin,
           kFnMatchSubstring, kFnStartsWith, kFnEndsWith, kFnIfElse, kFnYear, kFnQuarter, kFnMonth, kFnDay, kFnDayOfWeek,
           kFnDayOfYear, kFnIsoYear, kFnIsoWeek, kFnHour, kFnMinute, kFnSecond, kFnMillisecond, kFnMicrosecond, kFnNanosecond,
-          kNumFn };
+          kFnBinaryLength, kFnUtf8Length, kFnBinarySlice, kFnUtf8SliceCodeunits, kNumFn };
 const char* const kFnNames[kNumFn] = {"array_filter", "array_take", "greater", "array_sort_indices",
                                       "cast", "hash_sum", "add", "boolean", "compare", "parquet", "reduce", "order_by",
                                       "take_columns", "unique", "coalesce", "is_in", "index_in", "hashjoin",
                                       "match_substring", "starts_with", "ends_with", "if_else", "year", "quarter", "month", "day",
                                       "day_of_week", "day_of_year", "iso_year", "iso_week", "hour", "minute", "second",
-                                      "millisecond", "microsecond", "nanosecond"};
+                                      "millisecond", "microsecond", "nanosecond", "binary_length", "utf8_length", "binary_slice",
+                                      "utf8_slice_codeunits"};
 std::atomic<int64_t> g_fn_gpu[kNumFn];
 std::atomic<int64_t> g_fn_stock[kNumFn];
 void CountGpu(Fn f) {

@@ -223,8 +223,9 @@ Status GuardAggregateKernels(cp::Function* fn, int num_stock) {
   return Status::OK();
 }
 
-// the functions whose kernel lists the shim appends to — and the string-search siblings of match_substring and the
-// temporal siblings of year .. nanosecond, to which it adds nothing (every kernel of theirs is the reference's, so every
+// the functions whose kernel lists the shim appends to — and the string-search siblings of match_substring, the
+// temporal siblings of year .. nanosecond and the nearest string siblings of the lengths and slices (replace_slice,
+// reverse, case mapping), to which it adds nothing (every kernel of theirs is the reference's, so every
 // one gets a guard): a device-resident input is refused by name instead of being read by a CPU kernel
 const char* const kGuardedFunctions[] = {
     "array_filter", "array_take", "array_sort_indices", "equal", "not_equal", "greater", "greater_equal", "less", "less_equal",
@@ -234,7 +235,9 @@ const char* const kGuardedFunctions[] = {
     "match_like", "match_substring_regex", "find_substring", "find_substring_regex", "count_substring",
     "count_substring_regex", "if_else", "year", "quarter", "month", "day", "day_of_week", "day_of_year", "iso_year", "iso_week",
     "hour", "minute", "second", "millisecond", "microsecond", "nanosecond", "is_leap_year", "subsecond", "week", "us_week",
-    "us_year", "year_month_day", "iso_calendar", "strftime", "floor_temporal", "ceil_temporal", "round_temporal"};
+    "us_year", "year_month_day", "iso_calendar", "strftime", "floor_temporal", "ceil_temporal", "round_temporal",
+    "binary_length", "utf8_length", "binary_slice", "utf8_slice_codeunits", "binary_replace_slice", "utf8_replace_slice",
+    "binary_reverse", "utf8_reverse", "ascii_reverse", "utf8_upper", "utf8_lower", "ascii_upper", "ascii_lower"};
 
 // before the shim registers anything: how many kernels of each guarded function are the reference's
 arrow::Result<std::vector<int>> CountStockKernels(cp::FunctionRegistry* reg) {

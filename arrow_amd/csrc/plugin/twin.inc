@@ -75,14 +75,9 @@ struct PreparedOutput {
   int64_t null_count = 0;
   cp::ExecResult tmp;
 
-  // width: bytes per value, 0 for a bitmap of batch.length bits
-  Status Prepare(cp::KernelContext* ctx, const cp::ExecSpan& batch, const arrow::DataType* type, int width, TwinValidity policy) {
+  // `validity` and `null_count` as the policy prepares them
+  Status PrepareValidity(cp::KernelContext* ctx, const cp::ExecSpan& batch, TwinValidity policy) {
     const int64_t n = batch.length;
-    if (width == 0) {
-      ARROW_ASSIGN_OR_RAISE(data, ctx->AllocateBitmap(n));
-    } else {
-      ARROW_ASSIGN_OR_RAISE(data, ctx->Allocate(n * width));
-    }
     if (policy == TwinValidity::kAllocate) {
       ARROW_ASSIGN_OR_RAISE(validity, ctx->AllocateBitmap(n));
       null_count = arrow::kUnknownNullCount;
@@ -112,6 +107,18 @@ struct PreparedOutput {
         null_count = arrow::kUnknownNullCount;
       }
     }
+    return Status::OK();
+  }
+
+  // width: bytes per value, 0 for a bitmap of batch.length bits
+  Status Prepare(cp::KernelContext* ctx, const cp::ExecSpan& batch, const arrow::DataType* type, int width, TwinValidity policy) {
+    const int64_t n = batch.length;
+    if (width == 0) {
+      ARROW_ASSIGN_OR_RAISE(data, ctx->AllocateBitmap(n));
+    } else {
+      ARROW_ASSIGN_OR_RAISE(data, ctx->Allocate(n * width));
+    }
+    ARROW_RETURN_NOT_OK(PrepareValidity(ctx, batch, policy));
     ArraySpan span;
     span.type = type;
     span.length = n;
@@ -148,6 +155,36 @@ Status RunStockPrepared(Fn fn, cp::ArrayKernelExec exec, std::optional<cp::Kerne
   if (stock_null_count != nullptr) *stock_null_count = p.tmp.array_span()->null_count;
   p.MoveInto(out_arr);
   return Status::OK();
+}
+
+// The host half of a twin whose result is a variable-length column (utf8 / binary and their large forms).  Such a
+// reference kernel writes into the ArrayData itself; what the executor prepares for it is read off the kernel's own
+// enums, remembered from the copy AppendTwins hands to `install`: the validity as its null_handling says, and, when its
+// mem_allocation is PREALLOCATE, the offsets buffer (batch.length + 1 entries; the executor preallocates no data buffer
+// for a variable-length type).  Whatever is not prepared the exec allocates.
+struct StockContract {
+  cp::NullHandling::type null_handling = cp::NullHandling::INTERSECTION;
+  cp::MemAllocation::type mem_allocation = cp::MemAllocation::NO_PREALLOCATE;
+};
+Status RunStockVarLength(Fn fn, cp::ArrayKernelExec exec, std::optional<cp::KernelState*> stock_state, StockContract contract,
+                         cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecResult* out) {
+  ArrayData* out_arr = out->array_data().get();
+  const TwinValidity policy = contract.null_handling == cp::NullHandling::INTERSECTION           ? TwinValidity::kIntersection
+                              : contract.null_handling == cp::NullHandling::COMPUTED_PREALLOCATE ? TwinValidity::kAllocate
+                                                                                                 : TwinValidity::kNone;
+  PreparedOutput p;
+  ARROW_RETURN_NOT_OK(p.PrepareValidity(ctx, batch, policy));
+  out_arr->length = batch.length;
+  out_arr->offset = 0;
+  out_arr->buffers.assign(3, nullptr);
+  out_arr->buffers[0] = std::move(p.validity);
+  out_arr->null_count = p.null_count;
+  if (contract.mem_allocation == cp::MemAllocation::PREALLOCATE) {
+    const Type::type id = out_arr->type->id();
+    const int width = (id == Type::LARGE_STRING || id == Type::LARGE_BINARY) ? 8 : 4;
+    ARROW_ASSIGN_OR_RAISE(out_arr->buffers[1], ctx->Allocate((batch.length + 1) * width));
+  }
+  return RunStock(fn, exec, stock_state, ctx, batch, out);
 }
 
 // The bytes of a valid scalar operand of a device call: one byte 0 / 1 for a boolean (width 0), the value of a

@@ -1285,6 +1285,52 @@ enum {
 };
 int arx_match_substring(const ArxBinarySpan* values, int offset_width, int op, const void* pattern, int64_t pattern_length,
                         int64_t data_bytes_hint, int path, void* out_bits, void* stream);
+/* String lengths and slices — binary_length, utf8_length, binary_slice and utf8_slice_codeunits with step 1
+ * (compute/kernels/scalar_string_ascii.cc, scalar_string_utf8.cc; csrc/string_slice.hip).
+ * values: utf8 / binary (offset_width 4) or large_utf8 / large_binary (offset_width 8), any offset.  A null row counts 0
+ * and slices to an empty row whatever its offsets span; the result's validity is the input's: the caller copies it
+ * (arx_bitmap_copy).  Outputs start at offset 0.
+ * unit: ARX_STRING_UNIT_BYTES counts and slices bytes (offset arithmetic: no data byte is read before the copy).
+ * ARX_STRING_UNIT_CODEPOINTS counts and slices codepoints, where a codepoint starts at every byte that is not 0b10xxxxxx,
+ * valid UTF-8 or not: codepoint k >= 0 begins at the (k + 1)-th such byte of the row or at the row's end if there are
+ * fewer, "k from the end" at the k-th counted backwards or at the row's start; so a position never leaves its row.
+ * start / stop of either sign resolve as Python's slice does (stop = INT64_MAX: none, to the row's end), then
+ * begin = min(begin, end).  A non-negative bound is walked from the row's front, a negative one from its back.
+ * path (codepoints only): ARX_STRING_PATH_ROWS = one lane per row, ARX_STRING_PATH_WAVES = one wave per row, its lanes on
+ * consecutive 16-byte granules (long or skewed rows), ARX_STRING_PATH_AUTO = waves when data_bytes_hint / length reaches a
+ * fixed threshold.  data_bytes_hint: the size of the values' data buffer or -1 if unknown (auto then takes rows).
+ * A load touches only aligned 16-byte granules that hold at least one byte of a valid row.
+ * arx_string_length: out_lengths[i] = the bytes / codepoints of row i, int32 for offset_width 4 and int64 for 8; length
+ * elements, nothing past them.  Asynchronous; no read-back.
+ * arx_string_slice_offsets: step one of a slice.  ws: arx_string_slice_workspace_bytes(length, offset_width) device
+ * bytes, 8-byte aligned; it receives every row's source position and serves the data call.  out_offsets: length + 1
+ * entries of offset_width bytes, the result's offsets; *out_total_bytes = their last entry = the bytes of the result's
+ * data buffer (never more than the input's, so int32 offsets cannot overflow).  Synchronous (one read-back: the total).
+ * arx_string_slice_data: step two, the copy of total_bytes bytes into out_data with the same values, ws and out_offsets.
+ * Asynchronous.  Scan and copy are those of arx_binary_take_offsets / arx_binary_take_data.
+ * ARX_INVALID, with nothing launched or written, for a unit, path or offset_width outside the above, a negative length
+ * or total_bytes, NULL values / out_lengths / out_offsets / out_total_bytes, and for length > 0 NULL offsets, a ws that
+ * is NULL or too small, and NULL out_data / data with total_bytes > 0.  length == 0 succeeds and launches nothing; the
+ * offsets call then writes out_offsets[0] = 0 and *out_total_bytes = 0, the others nothing.
+ * arx_get_counter("string_slice_row_launches" / "string_slice_wave_launches") counts the launches of each form of the
+ * codepoint walk; byte-unit calls launch neither. */
+enum {
+  ARX_STRING_UNIT_BYTES = 0,
+  ARX_STRING_UNIT_CODEPOINTS = 1
+};
+enum {
+  ARX_STRING_PATH_AUTO = 0,
+  ARX_STRING_PATH_ROWS = 1,
+  ARX_STRING_PATH_WAVES = 2
+};
+int arx_string_length(const ArxBinarySpan* values, int offset_width, int unit, int64_t data_bytes_hint, int path,
+                      void* out_lengths, void* stream);
+size_t arx_string_slice_workspace_bytes(int64_t length, int offset_width);
+int arx_string_slice_offsets(const ArxBinarySpan* values, int offset_width, int unit, int64_t start, int64_t stop,
+                             int64_t data_bytes_hint, int path, void* ws, size_t ws_bytes, void* out_offsets,
+                             int64_t* out_total_bytes, void* stream);
+int arx_string_slice_data(const ArxBinarySpan* values, int offset_width, const void* ws, size_t ws_bytes,
+                          const void* out_offsets, int64_t total_bytes, void* out_data, void* stream);
 /* if_else(cond, left, right) of ONE fixed-width type or boolean (IfElseFunctor, compute/kernels/scalar_if_else.cc; csrc/if_else.hip):
  * out[i] = cond[i] ? left[i] : right[i]; out is null where cond is null (whatever its data bit says), else it takes the
  * validity of the chosen operand: valid = cv & ((c & lv) | (~c & rv)), booleans data = (c & l) | (~c & r).
