@@ -103,6 +103,13 @@ class SliceOptions(FunctionOptions):
         self.step = int(step)
 
 
+class TrimOptions(FunctionOptions):
+    """api_scalar.h TrimOptions: the `characters` to trim (str, UTF-8 encoded, or bytes)."""
+
+    def __init__(self, characters=""):
+        self.characters = characters
+
+
 class DayOfWeekOptions(FunctionOptions):
     """api_scalar.h DayOfWeekOptions: count_from_zero (Monday = 0 rather than 1 at the defaults) and week_start, the ISO
     weekday (Monday = 1 .. Sunday = 7) the numbering starts at."""
@@ -1054,6 +1061,11 @@ def _build_registry() -> FunctionRegistry:
     for name in ("binary_slice", "utf8_slice_codeunits"):
         f = Function(name, Function.SCALAR, 1, SliceOptions())
         f.add_kernel(Kernel((_STRING_INPUT[name],), _exec_string_slice(name)))
+        reg.add_function(f)
+    # the twelve trims of utf8 rows (csrc/string_trim.hip)
+    for name in _TRIMS:
+        f = Function(name, Function.SCALAR, 1)
+        f.add_kernel(Kernel((_UTF8_ONLY,), _exec_string_trim(name)))
         reg.add_function(f)
 
     # if_else(cond, left, right): left / right of ONE type, boolean or 1 / 2 / 4 / 8 bytes wide (csrc/if_else.hip)
@@ -2575,6 +2587,96 @@ def utf8_slice_codeunits(values: Array, start: int, stop=None, step: int = 1) ->
     """compute::UTF8SliceCodeunits under SliceOptions: Python's s[start:stop] of each row of a utf8 array, counted in
     codepoints.  See binary_slice."""
     return _call_string_function("utf8_slice_codeunits", values, SliceOptions(start, stop, step), 0)
+
+
+# --------------------------------------------------------------------------- string trimming
+# {ascii,utf8}_{,l,r}trim and their _whitespace forms (compute/kernels/scalar_string_ascii.cc, scalar_string_utf8.cc):
+# csrc/string_trim.hip writes the offsets, the copy is the slices' arx_string_slice_data.  name -> (sides, set kind) of
+# arx_string_trim_offsets; the set kinds 2 (bytes) and 3 (codepoints) take TrimOptions.
+_TRIM_SIDES = {"trim": 3, "ltrim": 1, "rtrim": 2}
+_TRIMS = {f"{enc}_{side}{ws}": (_TRIM_SIDES[side], {("ascii", "_whitespace"): 0, ("utf8", "_whitespace"): 1, ("ascii", ""): 2,
+                                                    ("utf8", ""): 3}[enc, ws])
+          for enc in ("ascii", "utf8") for side in _TRIM_SIDES for ws in ("_whitespace", "")}
+TRIM_MAX_CODEPOINTS = 64        # ARX_TRIM_MAX_CODEPOINTS: distinct codepoints the device kernel takes as arguments
+
+
+def _utf8_codepoints(raw: bytes):
+    """The codepoints of `raw` as the reference's UTF8Decode reads them (lead and continuation bits only), or its
+    ArrowInvalid."""
+    out, i = [], 0
+    while i < len(raw):
+        lead = raw[i]
+        extra = 0 if lead < 0x80 else 1 if 0xC0 <= lead < 0xE0 else 2 if 0xE0 <= lead < 0xF0 else 3 if 0xF0 <= lead < 0xF8 else None
+        tail = raw[i + 1: i + 1 + (extra or 0)]
+        if extra is None or len(tail) != extra or any((x & 0xC0) != 0x80 for x in tail):
+            raise ArrowInvalid("Invalid UTF8 sequence in input")
+        v = lead if extra == 0 else lead & (0xFF >> (extra + 2))
+        for x in tail:
+            v = (v << 6) | (x & 0x3F)
+        out.append(v)
+        i += 1 + extra
+    return out
+
+
+def _exec_string_trim(name: str):
+    sides, kind = _TRIMS[name]
+
+    def run(args, options):
+        (values,) = args
+        if not isinstance(values, Array):
+            raise ArrowNotImplementedError(f"arrow_amd: {name} of a scalar on the device path")
+        members, count = None, 0
+        if kind >= 2:
+            if options is None:
+                raise ArrowInvalid(f"Function '{name}' cannot be called without options")
+            raw = options.characters.encode() if isinstance(options.characters, str) else bytes(options.characters)
+            if kind == 2:
+                members, count = (C.c_uint8 * max(len(raw), 1)).from_buffer_copy(raw or b"\0"), len(raw)
+            else:
+                codepoints = _utf8_codepoints(raw)
+                if len(set(codepoints)) > TRIM_MAX_CODEPOINTS:
+                    raise ArrowNotImplementedError(f"arrow_amd: {name} with {len(set(codepoints))} distinct characters on device-resident "
+                                                   f"arrays: the device kernel takes up to {TRIM_MAX_CODEPOINTS}")
+                members, count = (C.c_uint32 * max(len(codepoints), 1))(*codepoints), len(codepoints)
+        dev = values.device
+        lib, stream = _lib_and_stream(dev)
+        n = values.length
+        out_offsets = alloc((n + 1) * 4, dev)
+        ws = _workspace(dev, lib.arx_string_slice_workspace_bytes(n, 4), "string_slice")
+        total = C.c_int64(0)
+        vspan = values.binary_span()
+        with tracing.span("arx_string_trim_offsets"):
+            check(lib.arx_string_trim_offsets(C.byref(vspan), 4, sides, kind, C.cast(members, C.c_void_p) if members is not None else None,
+                                              count, ws.data_ptr(), ws.numel(), out_offsets.data_ptr(), C.byref(total), stream))
+        out_data = alloc(total.value, dev)
+        with tracing.span("arx_string_slice_data"):
+            check(lib.arx_string_slice_data(C.byref(vspan), 4, ws.data_ptr(), ws.numel(), out_offsets.data_ptr(), total.value,
+                                            out_data.data_ptr(), stream))
+        valid, null_count = _input_validity(values, lib, stream)
+        return _with_null_count(Array(values.type, n, [valid, out_offsets, out_data], kUnknownNullCount, 0), null_count)
+    return run
+
+
+def _make_trim(name: str):
+    if _TRIMS[name][1] < 2:
+        def trim(values: Array) -> Array:
+            return _call_string_function(name, values, None)
+    else:
+        def trim(values: Array, characters) -> Array:
+            return _call_string_function(name, values, TrimOptions(characters), characters)
+    trim.__name__ = trim.__qualname__ = name
+    what = {1: "front", 2: "back", 3: "front and back"}[_TRIMS[name][0]]
+    of = ("ASCII whitespace bytes (9 .. 13, 32)", "Unicode whitespace codepoints", "bytes of `characters`",
+          "codepoints of `characters`")[_TRIMS[name][1]]
+    trim.__doc__ = (f"compute::{name}: each row of a utf8 array without the {of} at its {what}; a null row stays null and holds no "
+                    "bytes.  The result stays on the device.")
+    return trim
+
+
+for _name in _TRIMS:
+    globals()[_name] = _make_trim(_name)
+    _STRING_INPUT[_name] = _UTF8_ONLY
+del _name
 
 
 # --------------------------------------------------------------------------- if_else

@@ -103,6 +103,7 @@ namespace {
 #include "plugin/if_else.inc"
 #include "plugin/temporal.inc"
 #include "plugin/string_slice.inc"
+#include "plugin/string_trim.inc"
 #include "plugin/grouper_chain.inc"
 #include "plugin/acero_node.inc"
 #include "plugin/acero_node_general.inc"

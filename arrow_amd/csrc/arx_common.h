@@ -87,6 +87,7 @@ CounterTable match_substring_counters();
 CounterTable if_else_counters();
 CounterTable temporal_counters();
 CounterTable string_slice_counters();
+CounterTable string_trim_counters();
 
 #define ARX_HIP(call)                                          \
   do {                                                         \

@@ -92,14 +92,19 @@ enum Fn { kFnFilter = 0, kFnTake, kFnGreater, kFnSort, kFnCast, kFnHashSum, kFnA
           kFnReduce, kFnOrderBy, kFnTakeColumns, kFnUnique, kFnCoalesce, kFnIsIn, kFnIndexIn, kFnHashJoin,
           kFnMatchSubstring, kFnStartsWith, kFnEndsWith, kFnIfElse, kFnYear, kFnQuarter, kFnMonth, kFnDay, kFnDayOfWeek,
           kFnDayOfYear, kFnIsoYear, kFnIsoWeek, kFnHour, kFnMinute, kFnSecond, kFnMillisecond, kFnMicrosecond, kFnNanosecond,
-          kFnBinaryLength, kFnUtf8Length, kFnBinarySlice, kFnUtf8SliceCodeunits, kNumFn };
+          kFnBinaryLength, kFnUtf8Length, kFnBinarySlice, kFnUtf8SliceCodeunits, kFnAsciiTrimWhitespace, kFnAsciiLtrimWhitespace,
+          kFnAsciiRtrimWhitespace, kFnUtf8TrimWhitespace, kFnUtf8LtrimWhitespace, kFnUtf8RtrimWhitespace, kFnAsciiTrim, kFnAsciiLtrim,
+          kFnAsciiRtrim, kFnUtf8Trim, kFnUtf8Ltrim, kFnUtf8Rtrim, kNumFn };
 const char* const kFnNames[kNumFn] = {"array_filter", "array_take", "greater", "array_sort_indices",
                                       "cast", "hash_sum", "add", "boolean", "compare", "parquet", "reduce", "order_by",
                                       "take_columns", "unique", "coalesce", "is_in", "index_in", "hashjoin",
                                       "match_substring", "starts_with", "ends_with", "if_else", "year", "quarter", "month", "day",
                                       "day_of_week", "day_of_year", "iso_year", "iso_week", "hour", "minute", "second",
                                       "millisecond", "microsecond", "nanosecond", "binary_length", "utf8_length", "binary_slice",
-                                      "utf8_slice_codeunits"};
+                                      "utf8_slice_codeunits", "ascii_trim_whitespace", "ascii_ltrim_whitespace",
+                                      "ascii_rtrim_whitespace", "utf8_trim_whitespace", "utf8_ltrim_whitespace",
+                                      "utf8_rtrim_whitespace", "ascii_trim", "ascii_ltrim", "ascii_rtrim", "utf8_trim", "utf8_ltrim",
+                                      "utf8_rtrim"};
 std::atomic<int64_t> g_fn_gpu[kNumFn];
 std::atomic<int64_t> g_fn_stock[kNumFn];
 void CountGpu(Fn f) {

@@ -28,10 +28,7 @@
 // begin into the workspace and its length into out_offsets, adds the lengths of every kBinRows rows into the
 // workspace's sums (one atomic a wave), scans (bin_scan_lengths) and returns the total; arx_string_slice_data copies
 // (bin_copy_rows).  The output never exceeds the input, so int32 offsets cannot overflow.
-#include "binary_scan_copy.h"
-
-#include <algorithm>
-#include <atomic>
+#include "string_rows.h"
 
 namespace arx {
 
@@ -44,7 +41,6 @@ namespace {
 // the threshold bounds the other case, a bound deep inside long or skewed rows.
 constexpr int64_t kWavesPathMeanRow = 512;
 constexpr int64_t kNoStop = INT64_MAX;
-constexpr uint64_t kBit7 = 0x8080808080808080ull;
 constexpr int kLengthMaxBlocks = 1 << 20;   // workgroups of a binary_length launch (a workgroup strides over what is left)
 
 std::atomic<int64_t> g_slice_row_launches{0}, g_slice_wave_launches{0};
@@ -54,16 +50,6 @@ struct Leads {
   uint64_t lo, hi;
 };
 __device__ __forceinline__ int lead_count(Leads l) { return __popcll(l.lo) + __popcll(l.hi); }
-
-// bit 7 of the bytes [from, to) of a 64-bit word, 0 <= from, to <= 8 after clamping
-__device__ __forceinline__ uint64_t byte_range_bit7(int64_t from, int64_t to) {
-  from = from < 0 ? 0 : from;
-  to = to > 8 ? 8 : to;
-  if (to <= from) return 0;
-  const uint64_t below_to = to >= 8 ? ~uint64_t(0) : ((uint64_t(1) << (8 * to)) - 1);
-  const uint64_t below_from = (uint64_t(1) << (8 * from)) - 1;   // from < 8 here
-  return below_to & ~below_from & kBit7;
-}
 
 // the leads of the aligned granule at address g among the row's bytes [s, e) (addresses); g + 16 > s and g < e
 __device__ __forceinline__ Leads granule_leads(uint64_t g, uint64_t s, uint64_t e) {
@@ -346,41 +332,12 @@ __global__ __launch_bounds__(kBlock) void slice_waves_kernel(Bits valid, const O
   }
 }
 
-int device_cus() {
-  static std::atomic<int> cus{0};
-  int c = cus.load(std::memory_order_relaxed);
-  if (c == 0) {
-    int dev = 0, n = 0;
-    c = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-    cus.store(c, std::memory_order_relaxed);
-  }
-  return c;
-}
-
-unsigned rows_grid(int64_t n) {
-  return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, kBlock), static_cast<int64_t>(device_cus()) * 8)));
-}
 unsigned waves_grid(int64_t n) {   // a wave takes 64 rows a step
   return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, kBlock), static_cast<int64_t>(device_cus()) * 8)));
 }
 
 bool take_waves(int path, int64_t hint, int64_t n) {
   return path == ARX_STRING_PATH_WAVES || (path == ARX_STRING_PATH_AUTO && hint >= 0 && hint / n >= kWavesPathMeanRow);
-}
-
-struct Column {
-  Bits valid;
-  const void* offsets;   // element 0 of the logical array
-  const uint8_t* data;
-  int64_t n;
-};
-Column column_of(const ArxBinarySpan* values, int offset_width) {
-  Column c;
-  c.n = values->length;
-  c.offsets = reinterpret_cast<const uint8_t*>(values->offsets) + values->offset * offset_width;
-  c.data = static_cast<const uint8_t*>(values->data);
-  c.valid = make_bits(values->null_count == 0 ? nullptr : values->validity, values->offset, c.n);
-  return c;
 }
 
 template <typename O>
@@ -431,18 +388,6 @@ int slice_offsets_launch(const Column& c, int unit, bool waves, int64_t start, i
   return bin_scan_lengths<O>(lens, c.n, reinterpret_cast<long long*>(sums), "slicing a binary array", out_total, st);
 }
 
-// the checks the three calls share; `who` names the call
-int check_common(const char* who, const ArxBinarySpan* values, int offset_width) {
-  if (offset_width != 4 && offset_width != 8) {
-    set_error("%s: offset_width %d is not 4 or 8", who, offset_width);
-    return ARX_INVALID;
-  }
-  if (values->length < 0) {
-    set_error("%s: negative length %lld of values", who, static_cast<long long>(values->length));
-    return ARX_INVALID;
-  }
-  return ARX_OK;
-}
 int check_unit_path(const char* who, int unit, int path) {
   if (unit != ARX_STRING_UNIT_BYTES && unit != ARX_STRING_UNIT_CODEPOINTS) {
     set_error("%s: unit %d is not 0 (bytes) or 1 (codepoints)", who, unit);
@@ -512,11 +457,8 @@ int arx_string_slice_offsets(const ArxBinarySpan* values, int offset_width, int 
     set_error("string_slice_offsets: NULL offsets of values");
     return ARX_INVALID;
   }
-  if (ws == nullptr || ws_bytes < bin_workspace_bytes(values->length, offset_width) || (reinterpret_cast<uint64_t>(ws) & 7) != 0) {
-    set_error("string_slice_offsets: ws of %llu bytes is NULL, unaligned or smaller than arx_string_slice_workspace_bytes = %llu",
-              static_cast<unsigned long long>(ws_bytes), static_cast<unsigned long long>(bin_workspace_bytes(values->length, offset_width)));
-    return ARX_INVALID;
-  }
+  rc = check_offsets_workspace("string_slice_offsets", ws, ws_bytes, values->length, offset_width);
+  if (rc != ARX_OK) return rc;
   const Column c = column_of(values, offset_width);
   const bool waves = take_waves(path, data_bytes_hint, c.n);
   return offset_width == 4 ? slice_offsets_launch<int32_t>(c, unit, waves, start, stop, ws, out_offsets, out_total_bytes, st)

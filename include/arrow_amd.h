@@ -1331,6 +1331,50 @@ int arx_string_slice_offsets(const ArxBinarySpan* values, int offset_width, int 
                              int64_t* out_total_bytes, void* stream);
 int arx_string_slice_data(const ArxBinarySpan* values, int offset_width, const void* ws, size_t ws_bytes,
                           const void* out_offsets, int64_t total_bytes, void* out_data, void* stream);
+/* String trimming — ascii_trim / ascii_ltrim / ascii_rtrim, their _whitespace forms and the six utf8_ forms
+ * (compute/kernels/scalar_string_ascii.cc, scalar_string_utf8.cc; csrc/string_trim.hip).
+ * values: utf8 (offset_width 4) or large_utf8 (offset_width 8), any offset.  A trimmed row is a sub-range of its row, so
+ * arx_string_trim_offsets is step one of a slice: ws (arx_string_slice_workspace_bytes(length, offset_width) device
+ * bytes, 8-byte aligned), out_offsets and *out_total_bytes are those of arx_string_slice_offsets, and step two is
+ * arx_string_slice_data with the same values, ws and out_offsets.  A null row trims to an empty row whatever its offsets
+ * span; the result's validity is the input's: the caller copies it (arx_bitmap_copy).
+ * sides: ARX_TRIM_LEFT drops from the row's front while what it meets is in the set, ARX_TRIM_RIGHT from its back,
+ * ARX_TRIM_BOTH left first and then right on what is left.
+ * set_kind: ARX_TRIM_ASCII_WHITESPACE trims the bytes 9 .. 13 and 32; ARX_TRIM_BYTES the set_length bytes at `set` (any
+ * bytes, duplicates allowed).  ARX_TRIM_UTF8_WHITESPACE trims the codepoints U+0009-000D, U+001C-0020, U+0085, U+00A0,
+ * U+1680, U+2000-200A, U+2028, U+2029, U+202F, U+205F and U+3000; ARX_TRIM_CODEPOINTS the set_length uint32_t codepoints
+ * at `set` (duplicates allowed; more than ARX_TRIM_MAX_CODEPOINTS distinct ones: ARX_NOT_IMPLEMENTED).  `set` is a HOST
+ * pointer, read before the call returns; the two whitespace kinds ignore set and set_length.
+ * The two codepoint kinds trim units, defined on any bytes: at the front a continuation byte (0b10xxxxxx) alone, else a
+ * lead and the continuation bytes after it inside the row, at most three; at the back, after stepping over at most three
+ * continuation bytes, the row's last byte alone if the byte reached is a continuation byte too, else from that lead to
+ * the row's end.  A unit has a value when its length is the one its lead declares and the value is not below the
+ * minimum of that length; trimming passes a unit whose value is in the set and stops at any other, so a result never
+ * leaves its row.  Valid UTF-8 gives the reference's result; where the reference raises on an invalid sequence, the
+ * trim stops there.
+ * A load touches only aligned 16-byte granules that hold at least one byte of a valid row.
+ * Synchronous (one read-back: the total).  ARX_INVALID, with nothing launched or written, for a sides, set_kind or
+ * offset_width outside the above, a negative length or set_length, NULL values / out_offsets / out_total_bytes, a NULL
+ * set with set_length > 0, and for length > 0 NULL offsets and a ws that is NULL, unaligned or too small.  length == 0
+ * succeeds and launches nothing; it writes out_offsets[0] = 0 and *out_total_bytes = 0.
+ * arx_get_counter("string_trim_launches") counts the launches of the trim kernel. */
+enum {
+  ARX_TRIM_LEFT = 1,
+  ARX_TRIM_RIGHT = 2,
+  ARX_TRIM_BOTH = 3
+};
+enum {
+  ARX_TRIM_ASCII_WHITESPACE = 0,
+  ARX_TRIM_UTF8_WHITESPACE = 1,
+  ARX_TRIM_BYTES = 2,
+  ARX_TRIM_CODEPOINTS = 3
+};
+enum {
+  ARX_TRIM_MAX_CODEPOINTS = 64
+};
+int arx_string_trim_offsets(const ArxBinarySpan* values, int offset_width, int sides, int set_kind, const void* set,
+                            int64_t set_length, void* ws, size_t ws_bytes, void* out_offsets, int64_t* out_total_bytes,
+                            void* stream);
 /* if_else(cond, left, right) of ONE fixed-width type or boolean (IfElseFunctor, compute/kernels/scalar_if_else.cc; csrc/if_else.hip):
  * out[i] = cond[i] ? left[i] : right[i]; out is null where cond is null (whatever its data bit says), else it takes the
  * validity of the chosen operand: valid = cv & ((c & lv) | (~c & rv)), booleans data = (c & l) | (~c & r).
