@@ -2394,15 +2394,7 @@ def _exec_match_substring(name: str):
 
 
 def _call_match_substring(name: str, values, pattern, ignore_case: bool) -> Array:
-    import pyarrow as pa
-    import pyarrow.compute as pc
-
-    if not isinstance(values, Array):
-        raise TypeError(f"{name}: values must be an arrow_amd.Array")
-    if not is_base_binary(values.type):
-        # the reference's own "has no kernel matching input types" error, from a zero-length call
-        getattr(pc, name)(pa.array([], _pa_type(values.type)), "")
-    return call_function(name, [values], MatchSubstringOptions(pattern, ignore_case))
+    return _call_string_function(name, values, MatchSubstringOptions(pattern, ignore_case), "")
 
 
 def _match_substring(name: str, values: Array, pattern, ignore_case: bool) -> Array:
@@ -2427,19 +2419,8 @@ def _match_substring(name: str, values: Array, pattern, ignore_case: bool) -> Ar
                                   words.data_ptr(), stream))
     # (dpat is dropped on return while the kernel may still be queued: torch's caching allocator hands a freed block out
     # again only to work queued behind this call on the same stream)
-    if values.validity is None:
-        return Array(bool_, n, [None, words], 0, 0)
-    valid = alloc(bitmap_nbytes(n), dev)
-    check(lib.arx_bitmap_copy(values.validity.data_ptr(), values.offset, n, valid.data_ptr(), stream))
-    known = values._null_count
-    out = Array(bool_, n, [valid, words], kUnknownNullCount, 0)
-    if not callable(known) and known != kUnknownNullCount:
-        out._null_count = int(known)
-    else:
-        nbytes = (n + 7) // 8
-        out.set_lazy_null_count(
-            lambda: n - int(np.unpackbits(valid[:nbytes].cpu().numpy(), bitorder="little")[:n].sum()) if n else 0)
-    return out
+    valid, count = _input_validity(values, lib, stream)
+    return _with_null_count(Array(bool_, n, [valid, words], kUnknownNullCount, 0), count)
 
 
 def match_substring(values: Array, pattern, *, ignore_case: bool = False) -> Array:
@@ -2526,26 +2507,32 @@ def _exec_string_slice(name: str):
         if options.step != 1:
             raise ArrowNotImplementedError(f"arrow_amd: {name} with step={options.step} on device-resident arrays: only step=1 has "
                                            "a device kernel")
-        dev = values.device
-        lib, stream = _lib_and_stream(dev)
-        n = values.length
         clamp = lambda x: max(-2**63, min(int(x), 2**63 - 2))  # noqa: E731  (INT64_MAX itself means "no stop")
         stop = _NO_STOP if options.stop is None else clamp(options.stop)
-        out_offsets = alloc((n + 1) * 4, dev)
-        ws = _workspace(dev, lib.arx_string_slice_workspace_bytes(n, 4), "string_slice")
-        total = C.c_int64(0)
-        vspan = values.binary_span()
-        with tracing.span("arx_string_slice_offsets"):
-            check(lib.arx_string_slice_offsets(C.byref(vspan), 4, _STRING_UNIT[name], clamp(options.start), stop, _data_bytes_hint(values),
-                                               int(STRING_SLICE_PATH), ws.data_ptr(), ws.numel(), out_offsets.data_ptr(),
-                                               C.byref(total), stream))
-        out_data = alloc(total.value, dev)
-        with tracing.span("arx_string_slice_data"):
-            check(lib.arx_string_slice_data(C.byref(vspan), 4, ws.data_ptr(), ws.numel(), out_offsets.data_ptr(), total.value,
-                                            out_data.data_ptr(), stream))
-        valid, count = _input_validity(values, lib, stream)
-        return _with_null_count(Array(values.type, n, [valid, out_offsets, out_data], kUnknownNullCount, 0), count)
+        return _sub_range_result(values, "arx_string_slice_offsets", lambda lib, vspan, *rest: lib.arx_string_slice_offsets(
+            vspan, 4, _STRING_UNIT[name], clamp(options.start), stop, _data_bytes_hint(values), int(STRING_SLICE_PATH), *rest))
     return run
+
+
+def _sub_range_result(values: Array, span_name: str, offsets_call) -> Array:
+    """The result of a function whose every row is a sub-range of the input's row (slices, trims).
+    `offsets_call(lib, vspan, ws, ws_bytes, out_offsets, total, stream)` writes the n + 1 offsets and leaves each row's
+    source position in the workspace; arx_string_slice_data copies the bytes and the validity is the input's."""
+    dev = values.device
+    lib, stream = _lib_and_stream(dev)
+    n = values.length
+    out_offsets = alloc((n + 1) * 4, dev)
+    ws = _workspace(dev, lib.arx_string_slice_workspace_bytes(n, 4), "string_slice")
+    total = C.c_int64(0)
+    vspan = values.binary_span()
+    with tracing.span(span_name):
+        check(offsets_call(lib, C.byref(vspan), ws.data_ptr(), ws.numel(), out_offsets.data_ptr(), C.byref(total), stream))
+    out_data = alloc(total.value, dev)
+    with tracing.span("arx_string_slice_data"):
+        check(lib.arx_string_slice_data(C.byref(vspan), 4, ws.data_ptr(), ws.numel(), out_offsets.data_ptr(), total.value,
+                                        out_data.data_ptr(), stream))
+    valid, count = _input_validity(values, lib, stream)
+    return _with_null_count(Array(values.type, n, [valid, out_offsets, out_data], kUnknownNullCount, 0), count)
 
 
 def _call_string_function(name: str, values, options, *reference_args) -> Array:
@@ -2561,7 +2548,8 @@ def _call_string_function(name: str, values, options, *reference_args) -> Array:
 
 
 _STRING_INPUT = {"binary_length": is_base_binary, "utf8_length": _UTF8_ONLY, "binary_slice": _BINARY_ONLY,
-                 "utf8_slice_codeunits": _UTF8_ONLY}
+                 "utf8_slice_codeunits": _UTF8_ONLY, "match_substring": is_base_binary, "starts_with": is_base_binary,
+                 "ends_with": is_base_binary}
 
 
 def binary_length(values: Array) -> Array:
@@ -2638,22 +2626,8 @@ def _exec_string_trim(name: str):
                     raise ArrowNotImplementedError(f"arrow_amd: {name} with {len(set(codepoints))} distinct characters on device-resident "
                                                    f"arrays: the device kernel takes up to {TRIM_MAX_CODEPOINTS}")
                 members, count = (C.c_uint32 * max(len(codepoints), 1))(*codepoints), len(codepoints)
-        dev = values.device
-        lib, stream = _lib_and_stream(dev)
-        n = values.length
-        out_offsets = alloc((n + 1) * 4, dev)
-        ws = _workspace(dev, lib.arx_string_slice_workspace_bytes(n, 4), "string_slice")
-        total = C.c_int64(0)
-        vspan = values.binary_span()
-        with tracing.span("arx_string_trim_offsets"):
-            check(lib.arx_string_trim_offsets(C.byref(vspan), 4, sides, kind, C.cast(members, C.c_void_p) if members is not None else None,
-                                              count, ws.data_ptr(), ws.numel(), out_offsets.data_ptr(), C.byref(total), stream))
-        out_data = alloc(total.value, dev)
-        with tracing.span("arx_string_slice_data"):
-            check(lib.arx_string_slice_data(C.byref(vspan), 4, ws.data_ptr(), ws.numel(), out_offsets.data_ptr(), total.value,
-                                            out_data.data_ptr(), stream))
-        valid, null_count = _input_validity(values, lib, stream)
-        return _with_null_count(Array(values.type, n, [valid, out_offsets, out_data], kUnknownNullCount, 0), null_count)
+        return _sub_range_result(values, "arx_string_trim_offsets", lambda lib, vspan, *rest: lib.arx_string_trim_offsets(
+            vspan, 4, sides, kind, C.cast(members, C.c_void_p) if members is not None else None, count, *rest))
     return run
 
 

@@ -8,8 +8,6 @@
 // or a scalar; the result lives in HBM), host operands go to the reference kernel behind the executor's preallocation
 // contract (COMPUTED_PREALLOCATE / PREALLOCATE, which a NO_PREALLOCATE twin has to honour itself).  More than two
 // operands on the device are refused by name.
-cp::ArrayKernelExec g_stock_coalesce[arrow::Type::MAX_ID] = {};
-
 Status CoalesceExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecResult* out) {
   const int64_t n = batch.length;
   ArrayData* out_arr = out->array_data().get();
@@ -53,9 +51,9 @@ Status CoalesceExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::Exe
     return Status::OK();
   }
   // ---- host operands: the executor's preallocation, then the reference kernel
-  const cp::ArrayKernelExec stock = g_stock_coalesce[type.id()];
-  if (stock == nullptr) return Status::Invalid("arrow_amd: no reference coalesce kernel recorded for ", type.ToString());
-  return RunStockPrepared(kFnCoalesce, stock, std::nullopt, width, TwinValidity::kAllocate, ctx, batch, out);
+  const TwinData* kd = TwinDataOf(ctx->kernel());
+  if (kd == nullptr) return TwinWithoutData();
+  return RunStockPrepared(kFnCoalesce, kd->stock_exec, std::nullopt, width, TwinValidity::kAllocate, ctx, batch, out);
 }
 
 Status RegisterCoalesce(cp::FunctionRegistry* reg) {
@@ -63,10 +61,8 @@ Status RegisterCoalesce(cp::FunctionRegistry* reg) {
                      [](const auto& t) { return std::vector<arrow::TypeHolder>{t, t}; },
                      [](const ValueType& vt, cp::ScalarKernel* twin) -> arrow::Result<bool> {
                        if (twin->data != nullptr) return false;   // (none of the reference's coalesce kernels carries data)
-                       g_stock_coalesce[vt.probe->id()] = twin->exec;
-                       twin->signature = cp::KernelSignature::Make({vt.match}, twin->signature->out_type(), /*is_varargs=*/true);
-                       twin->exec = CoalesceExecNP;
-                       twin->can_write_into_slices = false;
+                       ARROW_RETURN_NOT_OK(InstallTwin("coalesce", vt, twin, true, std::make_shared<TwinData>(), kFnCoalesce, nullptr, CoalesceExecNP,
+                                                       cp::KernelSignature::Make({vt.match}, twin->signature->out_type(), /*is_varargs=*/true)));
                        return true;
                      });
 }

@@ -290,6 +290,9 @@ int FixedByteWidth(const arrow::DataType& t) {
   }
 }
 
+// bytes per offset of a binary / utf8 type: 8 for the large forms, 4 otherwise
+int BinaryOffsetWidth(Type::type id) { return (id == Type::LARGE_STRING || id == Type::LARGE_BINARY) ? 8 : 4; }
+
 // ---------------------------------------------------------------- state = stock state + options
 template <typename Options>
 struct ShimState : public cp::KernelState {

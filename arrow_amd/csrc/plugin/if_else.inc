@@ -9,8 +9,6 @@
 // behind the executor's preallocation contract, which a NO_PREALLOCATE twin has to honour itself (as CoalesceExecNP
 // does).  A mix of host and device arrays and a scalar cond over device operands are refused by name; device arrays of
 // every other type reach the reference's own kernels, which sit behind the device guard (plugin/device_guard.inc).
-cp::ArrayKernelExec g_stock_if_else[arrow::Type::MAX_ID] = {};
-
 // left / right of a device call as arx_if_else takes it: *span stays NULL for a scalar, *scalar for an array and a null scalar
 Status IfElseOperand(const cp::ExecValue& v, int width, const arrow::DataType& type, ArxSpan* storage, uint8_t* scalar_bytes,
                      const ArxSpan** span, const void** scalar) {
@@ -76,9 +74,9 @@ Status IfElseExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecR
     return Status::OK();
   }
   // ---- host operands: the executor's preallocation, then the reference kernel
-  const cp::ArrayKernelExec stock = g_stock_if_else[type.id()];
-  if (stock == nullptr) return Status::Invalid("arrow_amd: no reference if_else kernel recorded for ", type.ToString());
-  return RunStockPrepared(kFnIfElse, stock, std::nullopt, width, TwinValidity::kAllocate, ctx, batch, out);
+  const TwinData* kd = TwinDataOf(ctx->kernel());
+  if (kd == nullptr) return TwinWithoutData();
+  return RunStockPrepared(kFnIfElse, kd->stock_exec, std::nullopt, width, TwinValidity::kAllocate, ctx, batch, out);
 }
 
 // the result's type is the operands' (the reference's kernel of a probe type may state that very type: time32[s])
@@ -91,11 +89,9 @@ Status RegisterIfElse(cp::FunctionRegistry* reg) {
                      [](const auto& t) { return std::vector<arrow::TypeHolder>{arrow::boolean(), t, t}; },
                      [](const ValueType& vt, cp::ScalarKernel* twin) -> arrow::Result<bool> {
                        if (twin->data != nullptr) return false;   // (none of the reference's if_else kernels carries data)
-                       g_stock_if_else[vt.probe->id()] = twin->exec;
-                       twin->signature = cp::KernelSignature::Make({cp::InputType(arrow::boolean()), vt.match, vt.match},
-                                                                   cp::OutputType(ResolveIfElseType));
-                       twin->exec = IfElseExecNP;
-                       twin->can_write_into_slices = false;
+                       ARROW_RETURN_NOT_OK(InstallTwin("if_else", vt, twin, true, std::make_shared<TwinData>(), kFnIfElse, nullptr, IfElseExecNP,
+                                                       cp::KernelSignature::Make({cp::InputType(arrow::boolean()), vt.match, vt.match},
+                                                                                 cp::OutputType(ResolveIfElseType))));
                        return true;
                      });
 }

@@ -147,7 +147,7 @@ arrow::Result<arrow::Datum> SortIndicesByKeysOnDevice(const std::vector<DeviceSo
     } else if ((k.column.type()->id() == Type::STRING || k.column.type()->id() == Type::BINARY) && k.column.is_array()) {
       ARROW_ASSIGN_OR_RAISE(auto parts, SplitBinaryKeyOnDevice(*k.column.array()));
       for (auto& part : parts) keys.push_back(DeviceSortKey{std::move(part), k.order, k.placement});
-    } else if ((k.column.type()->id() == Type::LARGE_STRING || k.column.type()->id() == Type::LARGE_BINARY) && k.column.is_array()) {
+    } else if (BinaryOffsetWidth(k.column.type()->id()) == 8 && k.column.is_array()) {
       ARROW_ASSIGN_OR_RAISE(auto narrowed, NarrowLargeBinaryOnDevice(*k.column.array()));
       ARROW_ASSIGN_OR_RAISE(auto parts, SplitBinaryKeyOnDevice(*narrowed));
       for (auto& part : parts) keys.push_back(DeviceSortKey{std::move(part), k.order, k.placement});

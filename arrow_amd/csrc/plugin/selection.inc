@@ -250,13 +250,12 @@ int IndexTypeId(const arrow::DataType& t);
 // TakeExec / FilterExec for base binary on arrays that live in HBM: the offsets/validity pass,
 // one 8-byte read-back of the byte total (the reference grows a builder instead), then the bytes.
 // Host-resident strings stay on the stock kernels (they would be PCIe-bound both ways).
-bool IsInt64BinaryId(Type::type id) { return id == Type::LARGE_STRING || id == Type::LARGE_BINARY; }
 StockKernel g_stock_filter_bin, g_stock_take_bin, g_stock_filter_large_bin, g_stock_take_large_bin;   // (large_: int64 offsets)
 
 arrow::Result<std::unique_ptr<cp::KernelState>> BinaryFilterInit(cp::KernelContext* ctx,
                                                                  const cp::KernelInitArgs& args) {
   auto state = std::make_unique<ShimState<cp::FilterOptions>>();
-  const bool large_in = !args.inputs.empty() && args.inputs[0].type != nullptr && IsInt64BinaryId(args.inputs[0].type->id());
+  const bool large_in = !args.inputs.empty() && args.inputs[0].type != nullptr && BinaryOffsetWidth(args.inputs[0].type->id()) == 8;
   const StockKernel& stock_k = large_in ? g_stock_filter_large_bin : g_stock_filter_bin;
   if (stock_k.init) {
     ARROW_ASSIGN_OR_RAISE(state->stock, stock_k.init(ctx, args));
@@ -268,7 +267,7 @@ arrow::Result<std::unique_ptr<cp::KernelState>> BinaryFilterInit(cp::KernelConte
 arrow::Result<std::unique_ptr<cp::KernelState>> BinaryTakeInit(cp::KernelContext* ctx,
                                                                const cp::KernelInitArgs& args) {
   auto state = std::make_unique<ShimState<cp::TakeOptions>>();
-  const bool large_in = !args.inputs.empty() && args.inputs[0].type != nullptr && IsInt64BinaryId(args.inputs[0].type->id());
+  const bool large_in = !args.inputs.empty() && args.inputs[0].type != nullptr && BinaryOffsetWidth(args.inputs[0].type->id()) == 8;
   const StockKernel& stock_k = large_in ? g_stock_take_large_bin : g_stock_take_bin;
   if (stock_k.init) {
     ARROW_ASSIGN_OR_RAISE(state->stock, stock_k.init(ctx, args));
@@ -355,17 +354,16 @@ Status BinaryTakeOnDevice(const ArxBinarySpan& dv, const ArxSpan& di, int tid, h
 }
 
 bool IsInt32Binary(const arrow::DataType& t) { return t.id() == Type::STRING || t.id() == Type::BINARY; }
-bool IsInt64Binary(const arrow::DataType& t) { return t.id() == Type::LARGE_STRING || t.id() == Type::LARGE_BINARY; }
 
 Status BinaryTakeExec(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecResult* out) {
   auto* state = static_cast<ShimState<cp::TakeOptions>*>(ctx->state());
   const ArraySpan& values = batch[0].array;
   const ArraySpan& indices = batch[1].array;
   if (!OnRocm3(values) && !OnRocm(indices)) {
-    return RunStock(kFnTake, IsInt64BinaryId(values.type->id()) ? g_stock_take_large_bin : g_stock_take_bin, state->stock.get(), ctx, batch, out);
+    return RunStock(kFnTake, BinaryOffsetWidth(values.type->id()) == 8 ? g_stock_take_large_bin : g_stock_take_bin, state->stock.get(), ctx, batch, out);
   }
   const int tid = IndexTypeId(*indices.type);
-  const bool large = IsInt64Binary(*values.type);
+  const bool large = BinaryOffsetWidth(values.type->id()) == 8;
   if (tid < 0 || !(IsInt32Binary(*values.type) || large)) {
     return Status::NotImplemented("arrow_amd: take of ", values.type->ToString(), " by ",
                                   indices.type->ToString(), " on device-resident arrays");
@@ -388,9 +386,9 @@ Status BinaryFilterExec(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::E
   const ArraySpan& values = batch[0].array;
   const ArraySpan& filter = batch[1].array;
   if (!OnRocm3(values) && !OnRocm(filter)) {
-    return RunStock(kFnFilter, IsInt64BinaryId(values.type->id()) ? g_stock_filter_large_bin : g_stock_filter_bin, state->stock.get(), ctx, batch, out);
+    return RunStock(kFnFilter, BinaryOffsetWidth(values.type->id()) == 8 ? g_stock_filter_large_bin : g_stock_filter_bin, state->stock.get(), ctx, batch, out);
   }
-  const bool large = IsInt64Binary(*values.type);
+  const bool large = BinaryOffsetWidth(values.type->id()) == 8;
   if (filter.type->id() != Type::BOOL || !(IsInt32Binary(*values.type) || large)) {
     return Status::NotImplemented("arrow_amd: filter of ", values.type->ToString(), " on device-resident arrays");
   }

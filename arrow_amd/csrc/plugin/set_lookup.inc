@@ -11,12 +11,13 @@
 // (the registered casts; a pair without one is refused with a Status).  Outputs stay in HBM: is_in a bitmap without
 // nulls, index_in int32 indices with the bitmap of hits as validity.  Host batches run the reference's exec on the
 // outputs the executor would have preallocated for it (COMPUTED_PREALLOCATE: a validity bitmap and the values).
-struct SetLookupKernelData : public cp::KernelState {
+struct SetLookupKernelData : public TwinData {
   bool index = false;
 };
-// the reference's kernels of is_in [0] / index_in [1] as registered before the shim's: an added kernel matches a whole
-// type id (every timestamp unit, every decimal128 precision), the init and exec of a call are those of the reference's
-// kernel that matches its concrete input type
+// the reference's kernels of is_in [0] / index_in [1] as registered before the shim's.  Unlike the other twins these do
+// not run the stock exec / init their TwinData remembers (the probe type's): an added kernel matches a whole type id
+// (every timestamp unit, every decimal128 precision) while the reference's init differs per concrete type, so the init
+// and exec of a call are those of the reference's kernel that matches its concrete input type, searched per call
 std::vector<cp::ScalarKernel> g_stock_set_lookup[2];
 
 struct DeviceSetLookupState : public cp::KernelState {
@@ -37,11 +38,10 @@ struct DeviceSetLookupState : public cp::KernelState {
 
 // key width of a type on the device table: 1 .. 16 by bits, 0 boolean, -1 binary (offset width 4 / 8); -2 = none
 int SetLookupKeyWidth(const arrow::DataType& t, int* offset_width) {
-  *offset_width = 4;
+  *offset_width = BinaryOffsetWidth(t.id());
   switch (t.id()) {
     case Type::BOOL: return 0;
-    case Type::STRING: case Type::BINARY: return -1;
-    case Type::LARGE_STRING: case Type::LARGE_BINARY: *offset_width = 8; return -1;
+    case Type::STRING: case Type::BINARY: case Type::LARGE_STRING: case Type::LARGE_BINARY: return -1;
     case Type::DECIMAL128: return 16;
     case Type::INT8: case Type::UINT8: case Type::INT16: case Type::UINT16: case Type::INT32: case Type::UINT32:
     case Type::INT64: case Type::UINT64: case Type::FLOAT: case Type::DOUBLE: case Type::DATE32: case Type::DATE64:
@@ -51,12 +51,8 @@ int SetLookupKeyWidth(const arrow::DataType& t, int* offset_width) {
   }
 }
 
-const SetLookupKernelData* SetLookupDataOf(const cp::Kernel* k) {
-  return k != nullptr ? dynamic_cast<const SetLookupKernelData*>(k->data.get()) : nullptr;
-}
-
 arrow::Result<std::unique_ptr<cp::KernelState>> SetLookupInit(cp::KernelContext* ctx, const cp::KernelInitArgs& args) {
-  const SetLookupKernelData* data = SetLookupDataOf(args.kernel);
+  const auto* data = TwinDataOf<SetLookupKernelData>(args.kernel);
   if (data == nullptr || args.options == nullptr) return Status::Invalid("arrow_amd: set lookup kernel without its data or options");
   auto state = std::make_unique<DeviceSetLookupState>();
   state->options = *static_cast<const cp::SetLookupOptions*>(args.options);
@@ -133,7 +129,7 @@ Status SetLookupBuild(DeviceSetLookupState* s, cp::ExecContext* exec_ctx, hipStr
 Status SetLookupStock(cp::KernelContext* ctx, const SetLookupKernelData& kd, DeviceSetLookupState* s, const cp::ExecSpan& batch,
                       cp::ExecResult* out) {
   int64_t nulls = 0;
-  ARROW_RETURN_NOT_OK(RunStockPrepared(kd.index ? kFnIndexIn : kFnIsIn, s->stock_exec, s->stock.get(), kd.index ? 4 : 0,
+  ARROW_RETURN_NOT_OK(RunStockPrepared(kd.fn, s->stock_exec, s->stock.get(), kd.index ? 4 : 0,
                                        TwinValidity::kAllocate, ctx, batch, out, &nulls));
   ArrayData* out_arr = out->array_data().get();
   if (nulls < 0) nulls = batch.length - arrow::internal::CountSetBits(out_arr->buffers[0]->data(), 0, batch.length);
@@ -142,7 +138,7 @@ Status SetLookupStock(cp::KernelContext* ctx, const SetLookupKernelData& kd, Dev
 }
 
 Status SetLookupExec(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecResult* out) {
-  const SetLookupKernelData* kd = SetLookupDataOf(ctx->kernel());
+  const auto* kd = TwinDataOf<SetLookupKernelData>(ctx->kernel());
   auto* s = static_cast<DeviceSetLookupState*>(ctx->state());
   if (kd == nullptr || s == nullptr) return Status::Invalid("arrow_amd: set lookup kernel ran without its data or state");
   if (!batch[0].is_array() || !SpanTouchesRocm(batch[0].array)) return SetLookupStock(ctx, *kd, s, batch, out);
@@ -203,7 +199,7 @@ Status SetLookupExec(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::Exec
     out_arr->null_count = 0;
   }
   HIP_RETURN_NOT_OK(hipStreamSynchronize(st));   // (the cast rows and this thread's scratch may be released after return)
-  CountGpu(kd->index ? kFnIndexIn : kFnIsIn);
+  CountGpu(kd->fn);
   return Status::OK();
 }
 
@@ -222,14 +218,11 @@ Status RegisterSetLookup(cp::FunctionRegistry* reg, const char* name, bool index
       {arrow::timestamp(arrow::TimeUnit::NANO), Type::TIMESTAMP}, {arrow::duration(arrow::TimeUnit::NANO), Type::DURATION},
       {arrow::decimal128(38, 9), Type::DECIMAL128}, arrow::utf8(), arrow::binary(), arrow::large_utf8(), arrow::large_binary()};
   return AppendTwins(reg, name, types, [](const auto& t) { return std::vector<arrow::TypeHolder>{t}; },
-                     [index](const ValueType& vt, cp::ScalarKernel* twin) -> arrow::Result<bool> {
+                     [name, index](const ValueType& vt, cp::ScalarKernel* twin) -> arrow::Result<bool> {
                        if (twin->data != nullptr || !twin->init) return false;   // (none of the reference's set lookup kernels carries data)
                        auto data = std::make_shared<SetLookupKernelData>();
                        data->index = index;
-                       twin->data = std::move(data);
-                       twin->signature = cp::KernelSignature::Make({vt.match}, twin->signature->out_type());
-                       twin->init = SetLookupInit;
-                       twin->exec = SetLookupExec;
+                       ARROW_RETURN_NOT_OK(InstallTwin(name, vt, twin, true, std::move(data), index ? kFnIndexIn : kFnIsIn, SetLookupInit, SetLookupExec));
                        return true;
                      },
                      /*skip_undispatched=*/true);   // a type the reference does not look up either

@@ -3,11 +3,9 @@
 // namespace (one translation unit; the split is for reading, not for linkage).
 // ---------------------------------------------------------------- string trimming
 // One twin per function and input type, utf8 (int32 offsets) and large_utf8 (int64): the reference has trim kernels for
-// no other type.  A device-resident array runs arx_string_trim_offsets + arx_string_slice_data into HBM buffers, as the
-// slices do (plugin/string_slice.inc); the result's validity is the input's, copied to offset 0, and there is no bitmap
-// when the input has none.  A host batch (or a scalar) runs the reference's exec behind RunStockVarLength with the
-// null_handling / mem_allocation read off the reference's kernel.  The six functions that take TrimOptions run the
-// reference's init first (its state serves host batches) and keep a copy of the options for the device call.  The
+// no other type.  A device-resident array runs arx_string_trim_offsets through SubRangeResultOnDevice (plugin/twin.inc),
+// as the slices do; a host batch (or a scalar) runs the reference's exec behind RunStockVarLength.  The six functions
+// that take TrimOptions keep a copy of them for the device call (TwinInit).  The
 // reference reports an invalid UTF-8 `characters` from its exec ("Invalid UTF8 sequence in input"), so the device path
 // of the utf8_ functions says the same when it decodes them; more than ARX_TRIM_MAX_CODEPOINTS distinct codepoints have
 // no device kernel and are refused by name.
@@ -33,26 +31,9 @@ const StringTrimFunction kStringTrimFunctions[] = {
 
 bool TrimTakesOptions(const StringTrimFunction& f) { return f.set_kind == ARX_TRIM_BYTES || f.set_kind == ARX_TRIM_CODEPOINTS; }
 
-struct StringTrimKernelData : public cp::KernelState {
+struct StringTrimKernelData : public TwinData {
   const StringTrimFunction* f = nullptr;
-  cp::ArrayKernelExec stock_exec = nullptr;
-  cp::KernelInit stock_init;   // the functions with TrimOptions: the reference's state
-  StockContract contract;      // what the executor prepares for the reference's kernel
 };
-
-const StringTrimKernelData* StringTrimDataOf(const cp::Kernel* k) {
-  return k != nullptr ? dynamic_cast<const StringTrimKernelData*>(k->data.get()) : nullptr;
-}
-
-arrow::Result<std::unique_ptr<cp::KernelState>> StringTrimInit(cp::KernelContext* ctx, const cp::KernelInitArgs& args) {
-  const StringTrimKernelData* data = StringTrimDataOf(args.kernel);
-  if (data == nullptr || !data->stock_init) return Status::Invalid("arrow_amd: a string trim kernel was initialised without its data");
-  auto state = std::make_unique<ShimState<cp::TrimOptions>>();
-  ARROW_ASSIGN_OR_RAISE(state->stock, data->stock_init(ctx, args));   // the reference's state and its option checks
-  if (args.options == nullptr) return Status::Invalid("arrow_amd: ", data->f->name, " without TrimOptions");
-  state->options = *static_cast<const cp::TrimOptions*>(args.options);
-  return state;
-}
 
 // the codepoints of `characters` as the reference's UTF8Decode reads them: lead and continuation bits only
 arrow::Result<std::vector<uint32_t>> TrimCodepoints(const std::string& characters) {
@@ -74,8 +55,8 @@ arrow::Result<std::vector<uint32_t>> TrimCodepoints(const std::string& character
 }
 
 Status StringTrimExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecResult* out) {
-  const StringTrimKernelData* kd = StringTrimDataOf(ctx->kernel());
-  if (kd == nullptr || kd->stock_exec == nullptr) return Status::Invalid("arrow_amd: a string trim kernel ran without its data");
+  const auto* kd = TwinDataOf<StringTrimKernelData>(ctx->kernel());
+  if (kd == nullptr) return TwinWithoutData();
   const StringTrimFunction& f = *kd->f;
   auto* state = TrimTakesOptions(f) ? static_cast<ShimState<cp::TrimOptions>*>(ctx->state()) : nullptr;
   if (TrimTakesOptions(f) && state == nullptr) return Status::Invalid("arrow_amd: ", f.name, " ran without its state");
@@ -102,31 +83,16 @@ Status StringTrimExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::E
     set = codepoints.data();
     set_length = static_cast<int64_t>(codepoints.size());
   }
-  const int offset_width = batch[0].type()->id() == Type::LARGE_STRING ? 8 : 4;
-  const ArraySpan& rows = batch[0].array;
-  const int64_t n = rows.length;
   hipStream_t st;
   ARROW_RETURN_NOT_OK(t_scratch.Stream(&st));
   ArxBinarySpan vs{};
-  ARROW_RETURN_NOT_OK(DeviceBinarySpan(rows, &vs));
-  ArrayData* out_arr = out->array_data().get();
-  out_arr->length = n;
-  out_arr->offset = 0;
-  out_arr->buffers.assign(3, nullptr);
-  ARROW_ASSIGN_OR_RAISE(out_arr->buffers[1], AllocDevice((n + 1) * offset_width));
-  const size_t ws_bytes = arx_string_slice_workspace_bytes(n, offset_width);
-  void* ws = nullptr;
-  ARROW_RETURN_NOT_OK(t_scratch.Get(kBinWs, ws_bytes, &ws));
-  void* d_off = reinterpret_cast<void*>(out_arr->buffers[1]->mutable_address());
-  int64_t total = 0;
-  ARROW_RETURN_NOT_OK(FromArx(arx_string_trim_offsets(&vs, offset_width, f.sides, f.set_kind, set, set_length, ws, ws_bytes, d_off, &total, st)));
-  ARROW_ASSIGN_OR_RAISE(out_arr->buffers[2], AllocDevice(std::max<int64_t>(total, 8)));
-  ARROW_RETURN_NOT_OK(FromArx(arx_string_slice_data(&vs, offset_width, ws, ws_bytes, d_off, total,
-                                                    reinterpret_cast<void*>(out_arr->buffers[2]->mutable_address()), st)));
-  ARROW_RETURN_NOT_OK(CopyInputValidity(vs, n, st, out_arr));
-  HIP_RETURN_NOT_OK(hipStreamSynchronize(st));   // (this thread's scratch may be released after return)
-  CountGpu(f.fn);
-  return Status::OK();
+  ARROW_RETURN_NOT_OK(DeviceBinarySpan(batch[0].array, &vs));
+  return SubRangeResultOnDevice(
+      f.fn, vs, BinaryOffsetWidth(batch[0].type()->id()), st,
+      [&](const ArxBinarySpan* v, int width, void* ws, size_t ws_bytes, void* d_off, int64_t* total, hipStream_t s) {
+        return arx_string_trim_offsets(v, width, f.sides, f.set_kind, set, set_length, ws, ws_bytes, d_off, total, s);
+      },
+      out->array_data().get());
 }
 
 // one twin per function of the table above for utf8 and large_utf8, appended after the reference's kernels (dispatch
@@ -138,20 +104,10 @@ Status RegisterStringTrim(cp::FunctionRegistry* reg) {
     ARROW_RETURN_NOT_OK(AppendTwins(
         reg, f.name, types, [](const auto& t) { return std::vector<arrow::TypeHolder>{t}; },
         [fp](const ValueType& vt, cp::ScalarKernel* twin) -> arrow::Result<bool> {
-          if (twin->data != nullptr || static_cast<bool>(twin->init) != TrimTakesOptions(*fp)) {
-            return Status::Invalid("arrow_amd: the reference's ", fp->name, " kernel of ", vt.probe->ToString(), " is not of the expected shape");
-          }
           auto data = std::make_shared<StringTrimKernelData>();
           data->f = fp;
-          data->stock_exec = twin->exec;
-          data->stock_init = twin->init;
-          data->contract.null_handling = twin->null_handling;
-          data->contract.mem_allocation = twin->mem_allocation;
-          twin->data = std::move(data);
-          twin->signature = cp::KernelSignature::Make({vt.match}, twin->signature->out_type());
-          if (TrimTakesOptions(*fp)) twin->init = StringTrimInit;
-          twin->exec = StringTrimExecNP;
-          twin->can_write_into_slices = false;
+          ARROW_RETURN_NOT_OK(InstallTwin(fp->name, vt, twin, static_cast<bool>(twin->init) == TrimTakesOptions(*fp), std::move(data), fp->fn,
+                                          TwinInit<cp::TrimOptions, /*kRequired=*/true>, StringTrimExecNP));
           return true;
         }));
   }

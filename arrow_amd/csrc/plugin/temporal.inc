@@ -8,8 +8,8 @@
 // reference's exec behind the executor's preallocation contract (RunStockPrepared) — zoned timestamps included, which
 // stay the reference's business there; on the device a zone is refused by name (it needs the tz database).
 // A reference kernel with an init (day_of_week's DayOfWeekOptions; iso_week keeps week options of its own in a state)
-// gets a twin that runs that init first, so the reference's state serves host batches, and — day_of_week — keeps a copy
-// of the options for the device call (as the substring twins do).
+// gets TwinInit (plugin/twin.inc): the reference's state serves host batches, and day_of_week's options are kept for the
+// device call; iso_week is called without options and keeps the defaults, which nothing reads.
 struct TemporalFunction {
   const char* name;
   int component;   // ARX_TEMPORAL_*
@@ -23,21 +23,9 @@ const TemporalFunction kTemporalFunctions[] = {
     {"second", ARX_TEMPORAL_SECOND, kFnSecond}, {"millisecond", ARX_TEMPORAL_MILLISECOND, kFnMillisecond},
     {"microsecond", ARX_TEMPORAL_MICROSECOND, kFnMicrosecond}, {"nanosecond", ARX_TEMPORAL_NANOSECOND, kFnNanosecond}};
 
-struct TemporalKernelData : public cp::KernelState {
+struct TemporalKernelData : public TwinData {
   int component = 0;
-  Fn fn = kFnYear;
-  cp::ArrayKernelExec stock_exec = nullptr;
-  cp::KernelInit stock_init;   // empty: the reference's kernel has no state
 };
-
-struct DeviceTemporalState : public cp::KernelState {
-  std::unique_ptr<cp::KernelState> stock;
-  cp::DayOfWeekOptions options;   // day_of_week's
-};
-
-const TemporalKernelData* TemporalDataOf(const cp::Kernel* k) {
-  return k != nullptr ? dynamic_cast<const TemporalKernelData*>(k->data.get()) : nullptr;
-}
 
 // ARX_TIME_* of a type of the table, -1 otherwise
 int TemporalInputType(const arrow::DataType& t) {
@@ -57,23 +45,12 @@ int TemporalInputType(const arrow::DataType& t) {
   }
 }
 
-arrow::Result<std::unique_ptr<cp::KernelState>> TemporalInit(cp::KernelContext* ctx, const cp::KernelInitArgs& args) {
-  const TemporalKernelData* data = TemporalDataOf(args.kernel);
-  if (data == nullptr || !data->stock_init) return Status::Invalid("arrow_amd: a date / time kernel was initialised without its data");
-  auto state = std::make_unique<DeviceTemporalState>();
-  ARROW_ASSIGN_OR_RAISE(state->stock, data->stock_init(ctx, args));   // the reference's state and its option checks
-  if (data->component == ARX_TEMPORAL_DAY_OF_WEEK && args.options != nullptr) {
-    state->options = *static_cast<const cp::DayOfWeekOptions*>(args.options);
-  }
-  return state;
-}
-
 Status TemporalExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecResult* out) {
-  const TemporalKernelData* kd = TemporalDataOf(ctx->kernel());
-  if (kd == nullptr || kd->stock_exec == nullptr) return Status::Invalid("arrow_amd: a date / time kernel ran without its data");
-  auto* state = kd->stock_init ? static_cast<DeviceTemporalState*>(ctx->state()) : nullptr;
+  const auto* kd = TwinDataOf<TemporalKernelData>(ctx->kernel());
+  if (kd == nullptr) return TwinWithoutData();
+  auto* state = kd->stock_init ? static_cast<ShimState<cp::DayOfWeekOptions>*>(ctx->state()) : nullptr;
   if (kd->stock_init && state == nullptr) return Status::Invalid("arrow_amd: ", kFnNames[kd->fn], " ran without its state");
-  const DeviceTemporalState* dow = kd->component == ARX_TEMPORAL_DAY_OF_WEEK ? state : nullptr;
+  const ShimState<cp::DayOfWeekOptions>* dow = kd->component == ARX_TEMPORAL_DAY_OF_WEEK ? state : nullptr;
   if (!batch[0].is_array() || !SpanTouchesRocm(batch[0].array)) {
     // ---- a host batch (or a scalar): the executor's preallocation, then the reference's exec
     return RunStockPrepared(kd->fn, kd->stock_exec, state != nullptr ? std::optional<cp::KernelState*>(state->stock.get()) : std::nullopt,
@@ -140,19 +117,11 @@ Status RegisterTemporal(cp::FunctionRegistry* reg) {
         reg, f.name, f.component <= ARX_TEMPORAL_ISO_WEEK ? calendar : time_of_day,
         [](const auto& t) { return std::vector<arrow::TypeHolder>{t}; },
         [=](const ValueType& vt, cp::ScalarKernel* twin) -> arrow::Result<bool> {
-          if (twin->data != nullptr || (f.component == ARX_TEMPORAL_DAY_OF_WEEK && !twin->init)) {
-            return Status::Invalid("arrow_amd: the reference's ", f.name, " kernel of ", vt.probe->ToString(), " is not of the expected shape");
-          }
           auto data = std::make_shared<TemporalKernelData>();
           data->component = f.component;
-          data->fn = f.fn;
-          data->stock_exec = twin->exec;
-          data->stock_init = twin->init;
-          twin->data = std::move(data);
-          twin->signature = cp::KernelSignature::Make({vt.match}, cp::OutputType(arrow::int64()));
-          if (twin->init) twin->init = TemporalInit;
-          twin->exec = TemporalExecNP;
-          twin->can_write_into_slices = false;
+          ARROW_RETURN_NOT_OK(InstallTwin(f.name, vt, twin, f.component != ARX_TEMPORAL_DAY_OF_WEEK || twin->init, std::move(data), f.fn,
+                                          TwinInit<cp::DayOfWeekOptions>, TemporalExecNP,
+                                          cp::KernelSignature::Make({vt.match}, cp::OutputType(arrow::int64()))));
           return true;
         }));
   }

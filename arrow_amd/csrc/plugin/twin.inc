@@ -1,11 +1,13 @@
-// The two halves every NO_PREALLOCATE kernel twin shares: its host fallback and its registration.
+// What every NO_PREALLOCATE kernel twin shares: its registration, the record of the reference's kernel, its init, its host
+// fallback, and the device result of the functions whose rows are sub-ranges of the input's.
 // Part of the Arrow registration shim: included by ../arrow_plugin.cc inside its anonymous
 // namespace (one translation unit; the split is for reading, not for linkage).
 // ---------------------------------------------------------------- kernel twins
 // A scalar function taken over is registered as a twin: a copy of the reference's kernel with NullHandling::
 // COMPUTED_NO_PREALLOCATE + MemAllocation::NO_PREALLOCATE (the ScalarExecutor's own preallocation and null propagation,
 // exec.cc, run on the CPU and cannot touch device buffers).  Its exec runs the device kernel for device-resident
-// operands; for host operands it calls RunStockPrepared below.  AppendTwins registers it.
+// operands; for host operands it calls RunStockPrepared / RunStockVarLength below on the stock exec its TwinData
+// remembers.  AppendTwins registers it, InstallTwin fills it in.
 
 // A value type of a twin (or of array_filter / array_take / array_sort_indices): the concrete type used to find the
 // stock kernel and the matcher the added kernel is registered under (parametric types match by type id).
@@ -34,7 +36,7 @@ std::vector<ValueType> FixedWidthTwinTypes(bool with_decimal128) {
 }
 
 // Says what a twin installs over the copy of the reference's kernel it is handed (which still holds the stock exec, init
-// and data: remember them here): signature, init, exec, data.  false: this type gets no twin.
+// and data): most families call InstallTwin below.  false: this type gets no twin.
 using TwinInstall = std::function<arrow::Result<bool>(const ValueType&, cp::ScalarKernel*)>;
 
 // Append one twin per type to the scalar function `name`: the reference's kernel is found by DispatchExact on probe(type)
@@ -58,6 +60,68 @@ Status AppendTwins(cp::FunctionRegistry* reg, const std::string& name, const std
     ARROW_RETURN_NOT_OK(sfn->AddKernel(std::move(twin)));
   }
   return Status::OK();
+}
+
+// What the executor prepares for the reference's kernel, read off the kernel's own enums.
+struct StockContract {
+  cp::NullHandling::type null_handling = cp::NullHandling::INTERSECTION;
+  cp::MemAllocation::type mem_allocation = cp::MemAllocation::NO_PREALLOCATE;
+};
+
+// What a twin remembers of the reference's kernel it replaces, kept as the twin's Kernel::data.  A family that needs
+// more derives from it (a table row, an op code).
+struct TwinData : public cp::KernelState {
+  Fn fn = kFnFilter;
+  cp::ArrayKernelExec stock_exec = nullptr;
+  cp::KernelInit stock_init;   // empty: the reference's kernel has no state
+  StockContract contract;
+};
+
+// the record of a twin's kernel; null when the kernel carries none, another family's, or one without a stock exec
+template <class Data = TwinData>
+const Data* TwinDataOf(const cp::Kernel* k) {
+  const Data* data = k != nullptr ? dynamic_cast<const Data*>(k->data.get()) : nullptr;
+  return data != nullptr && data->stock_exec != nullptr ? data : nullptr;
+}
+Status TwinWithoutData() { return Status::Invalid("arrow_amd: a kernel twin ran without its data"); }
+
+// What every install does with the copy AppendTwins hands it: check that the reference's kernel carries no data and is
+// of the shape the family expects, remember its exec / init / contract in `data`, and install the twin's own signature
+// ({vt.match} -> the reference's out type unless one is given), init (when the reference has one) and exec.
+Status InstallTwin(const char* name, const ValueType& vt, cp::ScalarKernel* twin, bool shape_ok, std::shared_ptr<TwinData> data, Fn fn,
+                   cp::KernelInit init, cp::ArrayKernelExec exec, std::shared_ptr<cp::KernelSignature> signature = nullptr) {
+  if (twin->data != nullptr || !shape_ok) {
+    return Status::Invalid("arrow_amd: the reference's ", name, " kernel of ", vt.probe->ToString(), " is not of the expected shape");
+  }
+  data->fn = fn;
+  data->stock_exec = twin->exec;
+  data->stock_init = twin->init;
+  data->contract.null_handling = twin->null_handling;
+  data->contract.mem_allocation = twin->mem_allocation;
+  twin->data = std::move(data);
+  twin->signature = signature != nullptr ? std::move(signature) : cp::KernelSignature::Make({vt.match}, twin->signature->out_type());
+  if (twin->init && init) twin->init = std::move(init);
+  twin->exec = exec;
+  twin->can_write_into_slices = false;
+  return Status::OK();
+}
+
+// The init of a twin whose reference kernel has one: the reference's init runs first (its state serves host batches and
+// its option checks stay its own), then the options are copied for the device call.  kRequired: a call without options
+// is the Invalid below; otherwise the copy keeps Options' defaults, as it does for options of another class (a
+// function without options of its own is handed whatever the caller passed).  State: ShimState<Options> or a family's
+// extension of it.
+template <class Options, bool kRequired = false, class State = ShimState<Options>>
+arrow::Result<std::unique_ptr<cp::KernelState>> TwinInit(cp::KernelContext* ctx, const cp::KernelInitArgs& args) {
+  const TwinData* data = TwinDataOf(args.kernel);
+  if (data == nullptr || !data->stock_init) return Status::Invalid("arrow_amd: a kernel twin was initialised without its data");
+  auto state = std::make_unique<State>();
+  ARROW_ASSIGN_OR_RAISE(state->stock, data->stock_init(ctx, args));
+  if (kRequired && args.options == nullptr) return Status::Invalid("arrow_amd: ", kFnNames[data->fn], " without ", Options::kTypeName);
+  if (args.options != nullptr && std::strcmp(args.options->type_name(), Options::kTypeName) == 0) {
+    state->options = *static_cast<const Options*>(args.options);
+  }
+  return state;
 }
 
 // The output validity the executor would have prepared for the reference's kernel.
@@ -159,13 +223,9 @@ Status RunStockPrepared(Fn fn, cp::ArrayKernelExec exec, std::optional<cp::Kerne
 
 // The host half of a twin whose result is a variable-length column (utf8 / binary and their large forms).  Such a
 // reference kernel writes into the ArrayData itself; what the executor prepares for it is read off the kernel's own
-// enums, remembered from the copy AppendTwins hands to `install`: the validity as its null_handling says, and, when its
+// enums (the StockContract its TwinData remembers): the validity as its null_handling says, and, when its
 // mem_allocation is PREALLOCATE, the offsets buffer (batch.length + 1 entries; the executor preallocates no data buffer
 // for a variable-length type).  Whatever is not prepared the exec allocates.
-struct StockContract {
-  cp::NullHandling::type null_handling = cp::NullHandling::INTERSECTION;
-  cp::MemAllocation::type mem_allocation = cp::MemAllocation::NO_PREALLOCATE;
-};
 Status RunStockVarLength(Fn fn, cp::ArrayKernelExec exec, std::optional<cp::KernelState*> stock_state, StockContract contract,
                          cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecResult* out) {
   ArrayData* out_arr = out->array_data().get();
@@ -180,9 +240,7 @@ Status RunStockVarLength(Fn fn, cp::ArrayKernelExec exec, std::optional<cp::Kern
   out_arr->buffers[0] = std::move(p.validity);
   out_arr->null_count = p.null_count;
   if (contract.mem_allocation == cp::MemAllocation::PREALLOCATE) {
-    const Type::type id = out_arr->type->id();
-    const int width = (id == Type::LARGE_STRING || id == Type::LARGE_BINARY) ? 8 : 4;
-    ARROW_ASSIGN_OR_RAISE(out_arr->buffers[1], ctx->Allocate((batch.length + 1) * width));
+    ARROW_ASSIGN_OR_RAISE(out_arr->buffers[1], ctx->Allocate((batch.length + 1) * BinaryOffsetWidth(out_arr->type->id())));
   }
   return RunStock(fn, exec, stock_state, ctx, batch, out);
 }
@@ -197,4 +255,45 @@ int64_t FixedWidthScalarBytes(const arrow::Scalar& sc, int width, void* out) {
   const auto bytes = static_cast<const arrow::internal::PrimitiveScalarBase&>(sc).view();
   if (static_cast<int>(bytes.size()) == width) std::memcpy(out, bytes.data(), bytes.size());
   return static_cast<int64_t>(bytes.size());
+}
+
+// The input's validity at offset 0 into out_arr->buffers[0] (none when it has no nulls) and its null count.
+Status CopyInputValidity(const ArxBinarySpan& vs, int64_t n, hipStream_t st, ArrayData* out_arr) {
+  out_arr->null_count = 0;
+  if (vs.validity == nullptr || vs.null_count == 0) return Status::OK();
+  ARROW_ASSIGN_OR_RAISE(auto valid, AllocDevice(BitmapBytes(n)));
+  ARROW_RETURN_NOT_OK(FromArx(arx_bitmap_copy(vs.validity, vs.offset, n, reinterpret_cast<void*>(valid->mutable_address()), st)));
+  if (vs.null_count > 0) {
+    out_arr->null_count = vs.null_count;
+  } else {
+    ARROW_ASSIGN_OR_RAISE(out_arr->null_count, DeviceNullCount(*valid, n, st));
+  }
+  if (out_arr->null_count != 0) out_arr->buffers[0] = valid;
+  return Status::OK();
+}
+
+// The device result of a function whose every row is a sub-range of the input's row (slices, trims): `offsets_call`
+// (vs, offset_width, ws, ws_bytes, d_off, &total, st) writes the n + 1 offsets and leaves each row's source position in
+// the workspace, arx_string_slice_data copies the bytes, the validity is the input's.  One synchronisation, at the end.
+template <class OffsetsCall>
+Status SubRangeResultOnDevice(Fn fn, const ArxBinarySpan& vs, int offset_width, hipStream_t st, OffsetsCall&& offsets_call,
+                              ArrayData* out_arr) {
+  const int64_t n = vs.length;
+  out_arr->length = n;
+  out_arr->offset = 0;
+  out_arr->buffers.assign(3, nullptr);
+  ARROW_ASSIGN_OR_RAISE(out_arr->buffers[1], AllocDevice((n + 1) * offset_width));
+  const size_t ws_bytes = arx_string_slice_workspace_bytes(n, offset_width);
+  void* ws = nullptr;
+  ARROW_RETURN_NOT_OK(t_scratch.Get(kBinWs, ws_bytes, &ws));
+  void* d_off = reinterpret_cast<void*>(out_arr->buffers[1]->mutable_address());
+  int64_t total = 0;
+  ARROW_RETURN_NOT_OK(FromArx(offsets_call(&vs, offset_width, ws, ws_bytes, d_off, &total, st)));
+  ARROW_ASSIGN_OR_RAISE(out_arr->buffers[2], AllocDevice(std::max<int64_t>(total, 8)));
+  ARROW_RETURN_NOT_OK(FromArx(arx_string_slice_data(&vs, offset_width, ws, ws_bytes, d_off, total,
+                                                    reinterpret_cast<void*>(out_arr->buffers[2]->mutable_address()), st)));
+  ARROW_RETURN_NOT_OK(CopyInputValidity(vs, n, st, out_arr));
+  HIP_RETURN_NOT_OK(hipStreamSynchronize(st));   // (this thread's scratch may be released after return)
+  CountGpu(fn);
+  return Status::OK();
 }

@@ -13,22 +13,13 @@
 // null, unions, run-end encoded, dictionaries — and is_null(nan_is_null = true) of floating columns are refused by
 // name on the device route.
 enum ValidityKind { kIsValid = 0, kIsNull, kTrueUnlessNull };
-StockKernel g_stock_validity[3];
-
-template <int KIND>
-arrow::Result<std::unique_ptr<cp::KernelState>> ValidityInit(cp::KernelContext* ctx, const cp::KernelInitArgs& args) {
-  auto state = std::make_unique<ShimState<cp::NullOptions>>();
-  if (g_stock_validity[KIND].init) {
-    ARROW_ASSIGN_OR_RAISE(state->stock, g_stock_validity[KIND].init(ctx, args));
-  }
-  if (KIND == kIsNull && args.options != nullptr) state->options = *static_cast<const cp::NullOptions*>(args.options);
-  return state;
-}
 
 template <int KIND>
 Status ValidityExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::ExecResult* out) {
   static const char* const kNames[3] = {"is_valid", "is_null", "true_unless_null"};
-  auto* state = static_cast<ShimState<cp::NullOptions>*>(ctx->state());
+  const TwinData* kd = TwinDataOf(ctx->kernel());
+  if (kd == nullptr) return TwinWithoutData();
+  auto* state = static_cast<ShimState<cp::NullOptions>*>(ctx->state());   // (null: the reference's kernel has no init)
   const int64_t n = batch.length;
   ArrayData* out_arr = out->array_data().get();
   out_arr->buffers.resize(2);
@@ -82,7 +73,7 @@ Status ValidityExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::Exe
   ARROW_RETURN_NOT_OK(p.Prepare(ctx, batch, out_arr->type.get(), 0,
                                 all_null ? TwinValidity::kAllocate : propagate ? TwinValidity::kIntersection : TwinValidity::kNone));
   if (all_null) p.null_count = p.tmp.array_span_mutable()->null_count = n;
-  ARROW_RETURN_NOT_OK(RunStock(kFnBoolean, g_stock_validity[KIND].exec,
+  ARROW_RETURN_NOT_OK(RunStock(kFnBoolean, kd->stock_exec,
                                std::optional<cp::KernelState*>(state != nullptr ? state->stock.get() : nullptr), ctx, batch, &p.tmp));
   p.MoveInto(out_arr);
   return Status::OK();
@@ -91,11 +82,9 @@ Status ValidityExecNP(cp::KernelContext* ctx, const cp::ExecSpan& batch, cp::Exe
 template <int KIND>
 Status RegisterValidityNP(cp::FunctionRegistry* reg, const char* name) {
   return AppendTwins(reg, name, {arrow::int64()}, [](const auto& t) { return std::vector<arrow::TypeHolder>{t}; },
-                     [](const ValueType&, cp::ScalarKernel* twin) -> arrow::Result<bool> {
-                       g_stock_validity[KIND].exec = twin->exec;
-                       g_stock_validity[KIND].init = twin->init;
-                       twin->init = ValidityInit<KIND>;
-                       twin->exec = ValidityExecNP<KIND>;   // (the reference's signature stays: any type)
+                     [name](const ValueType& vt, cp::ScalarKernel* twin) -> arrow::Result<bool> {
+                       ARROW_RETURN_NOT_OK(InstallTwin(name, vt, twin, true, std::make_shared<TwinData>(), kFnBoolean, TwinInit<cp::NullOptions>,
+                                                       ValidityExecNP<KIND>, twin->signature));   // (the reference's signature stays: any type)
                        return true;
                      });
 }
