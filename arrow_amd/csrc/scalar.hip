@@ -1059,7 +1059,9 @@ static int cast_generic_pair(const ArxSpan* values, int allow_int_overflow, int 
   InT v{};
   ARX_HIP(hipMemcpyAsync(&v, in + bad, sizeof(InT), hipMemcpyDeviceToHost, st));
   ARX_HIP(hipStreamSynchronize(st));
-  char sv[64], slo[64], shi[64];
+  // "%f" of a double runs to 317 characters (-DBL_MAX: sign, 309 digits, point, 6 decimals); with the longest text
+  // around it (12 + 35 characters) the message stays inside set_error's 512-byte buffer
+  char sv[336], slo[64], shi[64];
   format_num(sv, sizeof(sv), v);
   if (mode == 1) {
     format_num(slo, sizeof(slo), lo);

@@ -624,7 +624,9 @@ def check_temporal_compare(amd, rng, n=4000):
     for t in (pa.timestamp("us"), pa.timestamp("ns", "UTC"), pa.timestamp("s", "Europe/Paris"), pa.duration("ms"),
               pa.time32("s"), pa.time64("ns"), pa.date32(), pa.date64()):
         w = 4 if t in (pa.time32("s"), pa.date32()) else 8
-        raw = rng.integers(0, 80_000 if w == 4 else 10**6, n).astype(np.int32 if w == 4 else np.int64)
+        hi = 80_000 if w == 4 else 10**6
+        lo = 0 if pa.types.is_time(t) else -hi          # instants before the epoch / negative durations; a time of day has none
+        raw = rng.integers(lo, hi, n).astype(np.int32 if w == 4 else np.int64)
         if t == pa.date64():
             raw = raw * 86_400_000
         a = pa.array(raw, pa.int32() if w == 4 else pa.int64(), mask=rng.random(n) < 0.08).cast(t)
@@ -1297,6 +1299,440 @@ def check_cast_numeric_pair(amd, rng, in_name: str, out_name: str, n: int = 3000
                     m &= np.isfinite(xs) & (xs > info.min) & (xs < info.max)
             w = np.asarray(want.fill_null(0)).astype(ot)
             assert np.array_equal(gv[m].view(np.uint8), w[m].view(np.uint8)), tag + " values"
+
+
+# ------------------------------------------------------------------ type boundaries and lone failing rows
+# The element-wise kernels launch one block per tile: 4099 rows are two 2048-row tiles of add_kernel, four 1024-row tiles of
+# the U = 4 kernels (casts, arith_kernel), sixteen blocks of divide_kernel, and a 3-row tail.  The positions are the first
+# and last rows of a wave, a block, a tile, the clamped tail and the array; a slice offset of 3 takes 8-byte operands off
+# their 16-byte alignment (the unaligned greater_kernel / add_kernel / cast_f64_f32_kernel forms) and shifts the bitmaps.
+EDGE_N = 4099
+EDGE_POSITIONS = (0, 1, 63, 64, 255, 256, 1023, 1024, 2047, 2048, 4095, 4096, 4098)
+EDGE_OFFSETS = (0, 3)
+_UVIEW = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}
+
+
+def _bits(x):
+    x = np.ascontiguousarray(x)
+    return x.view(_UVIEW[x.dtype.itemsize])
+
+
+def _pa_type(dt):
+    return pa.from_numpy_dtype(np.dtype(dt))
+
+
+def _safe_int_range(it, ot):
+    """The bounds a safe cast of the integer type `it` checks, or None where it checks nothing: GetSafeMinMax for an
+    integer target (util/int_util.cc), +-2^24 / +-2^53 for float / double (CheckForIntegerToFloatingTruncation: integers
+    of 16 bits and less, and 32-bit ones into a double, always fit)."""
+    ii = np.iinfo(it)
+    if ot.kind in "iu":
+        oi = np.iinfo(ot)
+        return max(int(ii.min), int(oi.min)), min(int(ii.max), int(oi.max))
+    if it.itemsize == 8 or (it.itemsize == 4 and ot.itemsize == 4):
+        limit = 2**24 if ot.itemsize == 4 else 2**53
+        return (-limit if it.kind == "i" else 0), limit
+    return None
+
+
+def _float_to_int_defined(x: float, ot) -> bool:
+    """static_cast<integer>(x) is defined: x is finite and its truncation is a value of the target type."""
+    import math
+
+    oi = np.iinfo(ot)
+    return math.isfinite(x) and int(oi.min) <= math.trunc(x) <= int(oi.max)
+
+
+def cast_expected_error(v, it, ot, out_name):
+    """What a safe cast of the lone value `v` (a numpy scalar of type `it`) must answer, restated in Python integers and
+    independent of both builds: None, or the reference's text for this offender."""
+    it, ot = np.dtype(it), np.dtype(ot)
+    if it.kind in "iu":
+        bounds = _safe_int_range(it, ot)
+        if bounds is None or bounds[0] <= int(v) <= bounds[1]:
+            return None
+        return f"Integer value {int(v)} not in range: {bounds[0]} to {bounds[1]}"
+    if ot.kind == "f":
+        return None
+    x = float(v)       # exact for float32 as well
+    if _float_to_int_defined(x, ot) and x == int(x):         # finite, integral (-0.0 too), inside [min, max] exactly
+        return None
+    return "Float value %f was truncated converting to %s" % (x, out_name)
+
+
+def cast_boundary_candidates(it, ot):
+    """The values on which cast(it -> ot) decides something, as an array of `it` without repeated bit patterns."""
+    it, ot = np.dtype(it), np.dtype(ot)
+    if it.kind in "iu":
+        ii = np.iinfo(it)
+        if ot.kind in "iu":
+            lo, hi = _safe_int_range(it, ot)
+            c = [lo - 1, lo, lo + 1, hi - 1, hi, hi + 1, 0, int(ii.min), int(ii.max)]
+        else:
+            c = [s * 2**k + d for k in (24, 53) for s in (1, -1) for d in (-1, 0, 1)] + [int(ii.min), int(ii.max)]
+        c = [v for v in c if ii.min <= v <= ii.max]
+    else:
+        f, fi = it.type, np.finfo(it)
+        if ot.kind in "iu":
+            oi = np.iinfo(ot)
+            c = []
+            for bound in (int(oi.min), int(oi.max) + 1, 0):           # powers of two: exact in both float types
+                b = f(bound)
+                c += [b, np.nextafter(b, f(np.inf)), np.nextafter(b, f(-np.inf)), f(bound + 1), f(bound - 1), f(bound + 0.5),
+                      f(bound - 0.5)]
+            c += [f(-0.0), f(np.nan), f(np.inf), f(-np.inf), fi.max, -fi.max, fi.tiny]
+            c += [f(1e56), f(-1e55)] if it.itemsize == 8 else [f(1e38), f(-1e38)]
+        else:
+            c = [fi.max, -fi.max, f(np.nan), f(-0.0), f(0.0), f(1.5)]
+            if it.itemsize == 8:
+                f32max = float(np.finfo(np.float32).max)
+                tie = f32max + 2.0**103        # half an ulp above FLT_MAX: rounds (to even) to inf, the double below it to FLT_MAX
+                c += [1e39, -1e39, f32max, tie, np.nextafter(tie, 0.0), -tie, 1e-40, 1e-45, 1e-46, 1e-310]
+            else:
+                c += [f(1e-40), fi.tiny, fi.smallest_subnormal]
+    with np.errstate(over="ignore"):
+        arr = np.array(c, dtype=it)
+    _, first = np.unique(_bits(arr), return_index=True)
+    return arr[np.sort(first)]
+
+
+def _cast_outcome(fn, *args, **kw):
+    try:
+        return fn(*args, **kw), None
+    except Exception as e:       # the caller compares the two builds' exception classes through the texts
+        if type(e).__name__ != "ArrowInvalid":
+            raise
+        return None, str(e)
+
+
+def check_cast_boundaries(amd):
+    """Every (in, out) pair of the ten numeric types, in == out included, on the values at the pair's own limits: the
+    last one a safe cast must accept and the first one it must refuse, each alone in [0, v, 0] so that the text names it.
+    Safe and unsafe: our error is None exactly when the reference's is, with the same text; the decision and the text also
+    equal cast_expected_error's restatement; a result equals the reference's bit for bit.  Unsafe float -> integer of a
+    value that is not finite or truncates out of range is undefined in the reference and is not compared; at least 40 %
+    of every such pair's candidates are."""
+    calls = 0
+    for in_name, it in NUMERIC_TYPES.items():
+        it = np.dtype(it)
+        for out_name, ot in NUMERIC_TYPES.items():
+            ot = np.dtype(ot)
+            to_type, pa_to = amd.array.type_from_name(out_name), pa.from_numpy_dtype(ot)
+            cands = cast_boundary_candidates(it, ot)
+            f2i = it.kind == "f" and ot.kind in "iu"
+            compared_unsafe = 0
+            for v in cands:
+                x = np.zeros(3, dtype=it)
+                x[1] = v
+                expected = cast_expected_error(v, it, ot, out_name)
+                for safe in (True, False):
+                    tag = f"cast {in_name}->{out_name} of {v!r} safe={safe}"
+                    want, werr = _cast_outcome(pc.cast, pa.array(x), pa_to, safe=safe)
+                    got, gerr = _cast_outcome(amd.compute.cast, amd.Array.from_numpy(x), to_type, safe=safe)
+                    calls += 1
+                    assert gerr == werr, f"{tag}: reference {werr!r} vs ours {gerr!r}"
+                    assert gerr == (expected if safe else None), f"{tag}: {gerr!r}, restated {expected!r}"
+                    if got is None:
+                        continue
+                    if f2i and not _float_to_int_defined(float(v), ot):
+                        assert not safe, tag
+                        continue
+                    compared_unsafe += not safe
+                    gv, gvalid = got.to_numpy()
+                    assert gvalid is None and got.type.name == out_name, tag
+                    assert_equal(_bits(gv), _bits(want.to_numpy()), tag)
+            if f2i:
+                share = compared_unsafe / len(cands)
+                assert share >= 0.4, f"cast {in_name}->{out_name}: only {compared_unsafe} of {len(cands)} unsafe results compared"
+    return calls
+
+
+# one pair per checking path of arx_cast_numeric, with two different offenders of the pair
+LONE_OFFENDER_PAIRS = (("int64", "int32", 2**31, -2**31 - 1), ("int64", "double", 2**53 + 1, -2**53 - 1),    # cast_i64_kernel
+                       ("int32", "int8", 128, -129), ("uint16", "int8", 128, 65535),                         # MODE 1, integer
+                       ("uint64", "double", 2**53 + 1, 2**64 - 1), ("int64", "float", 2**24 + 1, -2**24 - 1),  # MODE 1, float bound
+                       ("double", "int32", 0.5, 2.0**31), ("float", "uint8", 256.0, -1.0))                   # MODE 2
+TWO_OFFENDER_ROWS = ((4098, 1), (2048, 1023), (4096, 4095))
+
+
+def check_cast_lone_offender(amd, pair, n=EDGE_N, positions=EDGE_POSITIONS, offsets=EDGE_OFFSETS):
+    """WHERE the failing row is: `n` harmless rows (one of them null) with one offender at each position in turn, at each
+    slice offset.  The safe cast raises the reference's text, the unsafe cast equals the reference; under a null the same
+    value fails nothing; of two offenders in different blocks the smaller row is named, unless a null hides it."""
+    in_name, out_name, bad1, bad2 = pair
+    it, ot = np.dtype(NUMERIC_TYPES[in_name]), np.dtype(NUMERIC_TYPES[out_name])
+    to_type, pa_to = amd.array.type_from_name(out_name), pa.from_numpy_dtype(ot)
+    null_row = 7
+    assert null_row not in positions and all(p < n for p in positions)
+    msg = {b: cast_expected_error(it.type(b), it, ot, out_name) for b in (bad1, bad2)}
+    assert None not in msg.values() and msg[bad1] != msg[bad2]
+
+    def run(off, planted, nulls, expect):
+        """planted: {row: value}, nulls: more null rows; expect: the text of the safe cast's error, or None."""
+        values = (np.arange(n + off) % 100).astype(it)
+        valid = np.ones(n + off, bool)
+        for row, v in planted.items():
+            values[off + row] = v
+        for row in (null_row, *nulls):
+            valid[off + row] = False
+        host = pa.array(values, mask=~valid).slice(off)
+        dev = amd.Array.from_pyarrow(host)
+        tag = f"cast {in_name}->{out_name} off={off} planted={planted} nulls={nulls}"
+        want, werr = _cast_outcome(pc.cast, host, pa_to)
+        got, gerr = _cast_outcome(amd.compute.cast, dev, to_type)
+        assert werr == expect, f"{tag}: the reference says {werr!r}"
+        assert gerr == expect, f"{tag}: {gerr!r}"
+        defined = np.ones(n, bool)
+        if it.kind == "f" and ot.kind in "iu":
+            for row, v in planted.items():
+                defined[row] = _float_to_int_defined(float(v), ot)
+        results = [(amd.compute.cast(dev, to_type, safe=False), pc.cast(host, pa_to, safe=False))]
+        if expect is None:
+            results.append((got, want))
+        for g, w in results:
+            gv, gvalid = g.to_numpy()
+            m = valid[off:] & defined
+            assert_equal(gvalid, valid[off:], tag + " validity")
+            assert_equal(gvalid, ~np.asarray(w.is_null()), tag + " validity vs the reference")
+            assert_equal(_bits(gv)[m], _bits(w.fill_null(0).to_numpy(zero_copy_only=False).astype(ot, copy=False))[m], tag)
+
+    for off in offsets:
+        for p in positions:
+            run(off, {p: bad1}, (), msg[bad1])
+            run(off, {p: bad1}, (p,), None)
+        for late, early in TWO_OFFENDER_ROWS:
+            run(off, {late: bad1, early: bad2}, (), msg[bad2])
+            run(off, {late: bad2, early: bad1}, (), msg[bad1])
+            run(off, {late: bad1, early: bad2}, (early,), msg[bad1])      # the earlier offender under a null
+
+
+def _sliced_pair(amd, values, valid, off):
+    host = pa.array(values, mask=~valid).slice(off)
+    return amd.Array.from_pyarrow(host), host
+
+
+def _arith_outcome(fn, left, right):
+    try:
+        return fn(left, right), None
+    except Exception as e:
+        if type(e).__name__ != "ArrowInvalid":
+            raise
+        return None, str(e)
+
+
+def check_arith_lone_overflow(amd, dtype, n=EDGE_N, positions=EDGE_POSITIONS, offsets=EDGE_OFFSETS):
+    """add / subtract / multiply and their checked forms on ONE integer type where a single row overflows (max + 1,
+    min - 1 -- 0 - 1 for the unsigned types --, max * 2), at each position and slice offset, array x array, array x
+    scalar and scalar x array: the checked form raises "overflow", but not when either operand is null at that row; the
+    unchecked form wraps in the type's width, equal to Python integers and to the reference on every row."""
+    dt = np.dtype(dtype)
+    info = np.iinfo(dt)
+    lo, hi, width = int(info.min), int(info.max), 8 * dt.itemsize
+    cases = {"add": (hi, 1), "subtract": (lo, 1), "multiply": (hi, 2)}
+    pyop = {"add": lambda a, b: a + b, "subtract": lambda a, b: a - b, "multiply": lambda a, b: a * b}
+    null_row = 7
+
+    def wrap(x):
+        x &= (1 << width) - 1
+        return x - (1 << width) if dt.kind == "i" and x >> (width - 1) else x
+
+    def compare(tag, op, out, l_host, r_host, lv, rv, valid):
+        want = np.array([wrap(pyop[op](a, b)) for a, b in zip(lv, rv)], dtype=dt)
+        gv, gvalid = out.to_numpy()
+        assert_equal(gvalid if gvalid is not None else np.ones(n, bool), valid, tag + " validity")
+        assert_equal(gv[valid], want[valid], tag)
+        assert out.to_pyarrow().equals(getattr(pc, op)(l_host, r_host)), tag + " vs the reference"
+
+    for op, (big, other) in cases.items():
+        fn, fn_checked = getattr(amd.compute, op), getattr(amd.compute, op + "_checked")
+        ref_checked = getattr(pc, op + "_checked")
+        for off in offsets:
+            idx = np.arange(n + off)
+            # harmless everywhere: 10..19 (op) 0..6, and for the scalar on the left max (op) 0 | min - 0 | max * {0, 1}
+            l_base, r_base = (10 + idx % 10).astype(dt), (idx % 7).astype(dt)
+            r_for_scalar = (idx % 2 if op == "multiply" else idx * 0).astype(dt)
+            for p in positions:
+                for form in ("aa", "as", "sa"):
+                    for null_side in (None, "left", "right"):
+                        if (form, null_side) in (("as", "right"), ("sa", "left")):
+                            continue        # that side is the scalar
+                        lvals, rvals = l_base.copy(), (r_for_scalar if form == "sa" else r_base).copy()
+                        lvals[off + p], rvals[off + p] = big, other
+                        lvalid, rvalid = np.ones(n + off, bool), np.ones(n + off, bool)
+                        lvalid[off + null_row] = False
+                        rvalid[off + (null_row + 2)] = False
+                        if null_side == "left":
+                            lvalid[off + p] = False
+                        if null_side == "right":
+                            rvalid[off + p] = False
+                        if form == "aa":
+                            (dl, hl), (dr, hr) = _sliced_pair(amd, lvals, lvalid, off), _sliced_pair(amd, rvals, rvalid, off)
+                            lv, rv, valid = lvals[off:].tolist(), rvals[off:].tolist(), lvalid[off:] & rvalid[off:]
+                        elif form == "as":
+                            (dl, hl), (dr, hr) = _sliced_pair(amd, lvals, lvalid, off), (other, pa.scalar(other, _pa_type(dt)))
+                            lv, rv, valid = lvals[off:].tolist(), [other] * n, lvalid[off:]
+                        else:
+                            (dl, hl), (dr, hr) = (big, pa.scalar(big, _pa_type(dt))), _sliced_pair(amd, rvals, rvalid, off)
+                            lv, rv, valid = [big] * n, rvals[off:].tolist(), rvalid[off:]
+                        tag = f"{op}[{dt.name}] {form} row {p} off={off} null={null_side}"
+                        expect = "overflow" if null_side is None else None
+                        out, gerr = _arith_outcome(fn_checked, dl, dr)
+                        _, werr = _arith_outcome(ref_checked, hl, hr)
+                        assert werr == expect, f"{tag}: the reference says {werr!r}"
+                        assert gerr == expect, f"{tag}: {gerr!r}"
+                        if out is not None:
+                            compare(tag + " checked", op, out, hl, hr, lv, rv, valid)
+                        if null_side is None:
+                            compare(tag + " unchecked", op, fn(dl, dr), hl, hr, lv, rv, valid)
+
+
+def check_add_pair_kernel_tail(amd, n=EDGE_N, offsets=EDGE_OFFSETS):
+    """Unchecked add on int64 and float64 (the pair-loading add_kernel), rows that all differ so that a pair stored one row
+    off, or a last row taken from its neighbour, shows: array + array, array + scalar, scalar + array at both offsets, bit
+    for bit against the reference."""
+    for dt in (np.dtype(np.int64), np.dtype(np.float64)):
+        for off in offsets:
+            idx = np.arange(n + off)
+            if dt.kind == "i":
+                lvals, rvals, sc = (idx * 2654435761 - 2**62).astype(dt), (idx * 40503 + 2**62).astype(dt), 2**63 - 5
+            else:
+                lvals, rvals, sc = (idx * 0.37 - 700.0).astype(dt), (1e300 / (idx + 1)).astype(dt), 0.1
+            lvalid, rvalid = idx % 97 != 5, idx % 89 != 11
+            (dl, hl), (dr, hr) = _sliced_pair(amd, lvals, lvalid, off), _sliced_pair(amd, rvals, rvalid, off)
+            for out, ref in ((amd.compute.add(dl, dr), pc.add(hl, hr)), (amd.compute.add(dl, sc), pc.add(hl, pa.scalar(sc, _pa_type(dt)))),
+                             (amd.compute.add(sc, dr), pc.add(pa.scalar(sc, _pa_type(dt)), hr))):
+                gv, gvalid = out.to_numpy()
+                rvalid_ = ~np.asarray(ref.is_null())
+                tag = f"add[{dt.name}] off={off}"
+                assert_equal(gvalid, rvalid_, tag + " validity")
+                assert_equal(_bits(gv)[rvalid_], _bits(ref.fill_null(0).to_numpy(zero_copy_only=False))[rvalid_], tag)
+
+
+DIVIDE_ROW_PAIRS = ((255, 256), (1023, 4098), (0, 4096))
+
+
+def check_divide_ordering(amd, dtype, n=EDGE_N, positions=EDGE_POSITIONS, offsets=EDGE_OFFSETS):
+    """divide / divide_checked on ONE integer type over `n` rows of 6 / 3.  Signed: a zero divisor and min / -1 in different
+    blocks, in both orders -- divide_checked answers with the error of the LATER row ("divide by zero" or "overflow"),
+    divide with "divide by zero" while a zero divisor is valid and else succeeds with 0 at the min / -1 row; both rows
+    under nulls fail nothing.  Unsigned: a lone zero divisor at every position.  All as the reference answers."""
+    dt = np.dtype(dtype)
+    lo = int(np.iinfo(dt).min)
+
+    def run(off, zero_rows, min_rows, null_rows, expect_checked, expect_plain):
+        lvals, rvals = np.full(n + off, 6, dt), np.full(n + off, 3, dt)
+        lvalid, rvalid = np.ones(n + off, bool), np.ones(n + off, bool)
+        lvalid[off + 7] = False
+        for r in zero_rows:
+            rvals[off + r] = 0
+        for r in min_rows:
+            lvals[off + r], rvals[off + r] = lo, -1
+        for r in null_rows:
+            rvalid[off + r] = False
+        (dl, hl), (dr, hr) = _sliced_pair(amd, lvals, lvalid, off), _sliced_pair(amd, rvals, rvalid, off)
+        both = lvalid[off:] & rvalid[off:]
+        for name, expect in (("divide_checked", expect_checked), ("divide", expect_plain)):
+            tag = f"{name}[{dt.name}] off={off} zero={zero_rows} min={min_rows} nulls={null_rows}"
+            out, gerr = _arith_outcome(getattr(amd.compute, name), dl, dr)
+            ref, werr = _arith_outcome(getattr(pc, name), hl, hr)
+            assert werr == expect, f"{tag}: the reference says {werr!r}"
+            assert gerr == expect, f"{tag}: {gerr!r}"
+            if out is None:
+                continue
+            gv, gvalid = out.to_numpy()
+            want = np.full(n, 2, dt)
+            want[list(min_rows)] = 0
+            assert_equal(gvalid, both, tag + " validity")
+            assert_equal(gv[both], want[both], tag)
+            assert out.to_pyarrow().equals(ref), tag + " vs the reference"
+
+    for off in offsets:
+        if dt.kind == "u":
+            for p in positions:
+                run(off, (p,), (), (), "divide by zero", "divide by zero")
+                run(off, (p,), (), (p,), None, None)
+            continue
+        for p1, p2 in DIVIDE_ROW_PAIRS:
+            run(off, (p1,), (p2,), (), "overflow", "divide by zero")            # the min / -1 row is the later one
+            run(off, (p2,), (p1,), (), "divide by zero", "divide by zero")
+            run(off, (p1,), (p2,), (p1,), "overflow", None)                     # only min / -1 is visited
+            run(off, (p2,), (p1,), (p2,), "overflow", None)
+            run(off, (p1,), (p2,), (p2,), "divide by zero", "divide by zero")   # only the zero divisor is visited
+            run(off, (p1,), (p2,), (p1, p2), None, None)
+
+
+def check_compare_whole_range(amd, rng, dtype, n=EDGE_N, offsets=EDGE_OFFSETS):
+    """The six comparisons and unchecked add / subtract / multiply on ONE numeric type with operands from the WHOLE type:
+    half of them its edges (min, min + 1, max, max - 1, max // 2, max // 2 + 1, 0, 1; floats: +-0.0, +-inf, NaN, +-max, a
+    subnormal), the rest uniform over the type (floats: over its bit patterns); 10 % nulls, both slice offsets; array x
+    array and against a scalar at max, min and max // 2 + 1 on either side.  Bits equal Python's comparison of the
+    values, padding bits are zero, validity and the whole result equal the reference's; the arithmetic wraps in the
+    type's width like the reference (unsigned subtract included)."""
+    import operator
+
+    dt = np.dtype(dtype)
+    is_int = dt.kind in "iu"
+    if is_int:
+        info = np.iinfo(dt)
+        lo, hi = int(info.min), int(info.max)
+        edges = np.array([lo, lo + 1, hi, hi - 1, hi // 2, hi // 2 + 1, 0, 1], dtype=dt)
+        scalars = (hi, lo, hi // 2 + 1)
+    else:
+        fi = np.finfo(dt)
+        edges = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, fi.max, -fi.max, fi.smallest_subnormal], dtype=dt)
+        scalars = (float(fi.max), float(-fi.max), -0.0)
+    uview = _UVIEW[dt.itemsize]
+    ops = {"equal": operator.eq, "not_equal": operator.ne, "greater": operator.gt, "greater_equal": operator.ge,
+           "less": operator.lt, "less_equal": operator.le}
+
+    def draw(m):
+        if is_int:
+            v = rng.integers(info.min, info.max, m, dtype=dt, endpoint=True)
+        else:
+            v = rng.integers(0, np.iinfo(uview).max, m, dtype=uview, endpoint=True).view(dt)
+        pick = rng.random(m) < 0.5
+        v[pick] = edges[rng.integers(0, len(edges), int(pick.sum()))]
+        return v
+
+    for off in offsets:
+        lvals, rvals = draw(n + off), draw(n + off)
+        rvals[::5] = lvals[::5]                    # ties on whole-range values too
+        lvalid, rvalid = rng.random(n + off) >= 0.1, rng.random(n + off) >= 0.1
+        (dl, hl), (dr, hr) = _sliced_pair(amd, lvals, lvalid, off), _sliced_pair(amd, rvals, rvalid, off)
+        lpy, rpy = lvals[off:].tolist(), rvals[off:].tolist()
+        operands = [("array x array", dl, hl, lpy, dr, hr, rpy)]
+        for sc in scalars:
+            hs = pa.scalar(sc, _pa_type(dt))
+            operands += [(f"array x {sc!r}", dl, hl, lpy, sc, hs, [sc] * n), (f"{sc!r} x array", sc, hs, [sc] * n, dr, hr, rpy)]
+        for op, pyfn in ops.items():
+            fn, ref_fn = getattr(amd.compute, op), getattr(pc, op)
+            for form, l_dev, l_host, l_py, r_dev, r_host, r_py in operands:
+                tag = f"{op}[{dt.name}] off={off} {form}"
+                out = fn(l_dev, r_dev)
+                bits, pad_ok = device_bitmap_to_bool(out.data, n)
+                assert pad_ok, tag + ": padding bits not zero"
+                assert_equal(bits, np.array([pyfn(a, b) for a, b in zip(l_py, r_py)], dtype=bool), tag + " bits")
+                ref = ref_fn(l_host, r_host)
+                assert_equal(_logical_valid(out)[0], ~np.asarray(ref.is_null()), tag + " validity")
+                assert out.to_pyarrow().equals(ref), tag + " vs the reference"
+        for op in ("add", "subtract", "multiply"):
+            tag = f"{op}[{dt.name}] off={off}"
+            out = getattr(amd.compute, op)(dl, dr)
+            ref = getattr(pc, op)(hl, hr)
+            gv, gvalid = out.to_numpy()
+            rvalid_ = ~np.asarray(ref.is_null())
+            assert_equal(gvalid, rvalid_, tag + " validity")
+            rv = ref.fill_null(0).to_numpy(zero_copy_only=False).copy()
+            gv = gv.copy()
+            if is_int:
+                width = 8 * dt.itemsize
+                py = {"add": operator.add, "subtract": operator.sub, "multiply": operator.mul}[op]
+                wrapped = np.array([py(a, b) & ((1 << width) - 1) for a, b in zip(lpy, rpy)], dtype=uview)
+                assert_equal(_bits(gv)[rvalid_], wrapped[rvalid_], tag + " vs Python integers")
+            else:            # a NaN result is a NaN; its sign / payload is the FPU's (x86 and gfx950 differ)
+                gv[np.isnan(gv)] = np.nan
+                rv[np.isnan(rv)] = np.nan
+            assert_equal(_bits(gv)[rvalid_], _bits(rv)[rvalid_], tag + " vs the reference")
 
 
 def torch_dtype_as_signed(dt):

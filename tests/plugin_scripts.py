@@ -324,8 +324,11 @@ VECTOR_HASH_SCRIPT = textwrap.dedent(r'''
             check(f"cast {a}->{b}", pc.cast(d_small[str(a)], b), want_cast[(str(a), str(b))])
             check(f"cast {a}->{b} (sliced)", pc.cast(d_small[str(a)].slice(9), b), want_cast[(str(a), str(b))].slice(9))
     assert lib.arrow_amd_plugin_calls(b"cast", 1) - c0 >= 150
-    d_wide, d_fr = to_device(wide), to_device(fr)
-    for src, host, target in ((d_wide, wide, pa.int16()), (d_fr, fr, pa.int32()), (d_wide, wide, pa.float32())):
+    # one offender whose "%f" text runs past 300 characters, deep in the array: the message names it in full
+    huge = pa.array(np.where(np.arange(n) == n - 2, 1e300, np.round(rng.standard_normal(n) * 1000)))
+    d_wide, d_fr, d_huge = to_device(wide), to_device(fr), to_device(huge)
+    for src, host, target in ((d_wide, wide, pa.int16()), (d_fr, fr, pa.int32()), (d_wide, wide, pa.float32()),
+                              (d_huge, huge, pa.int64())):
         try:
             pc.cast(host, target)
             raise SystemExit("the reference accepted this cast?")
@@ -335,7 +338,9 @@ VECTOR_HASH_SCRIPT = textwrap.dedent(r'''
             pc.cast(src, target)
             raise SystemExit(f"unsafe device cast to {target} did not fail")
         except pa.ArrowInvalid as e:
-            assert str(e).split(" ")[0:2] == ref_msg.split(" ")[0:2], (str(e), ref_msg)
+            assert str(e) == ref_msg, (str(e), ref_msg)      # the whole text: the first offender's value and the bounds
+        if src is d_huge:      # (1e300 -> int64 is undefined in the reference: the rows before it are compared)
+            src, host = src.slice(0, n - 2), host.slice(0, n - 2)
         check(f"unsafe cast to {target}", pc.cast(src, target, safe=False), pc.cast(host, target, safe=False))
     print("VECTOR_HASH_OK")
 ''')

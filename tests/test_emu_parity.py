@@ -653,6 +653,43 @@ def test_cast_every_numeric_pair(emu_ctx, in_name):
             P.check_cast_numeric_pair(emu_ctx, rng, in_name, out_name, n=3000)
 
 
+def test_cast_at_the_type_boundaries(emu_ctx):
+    """All 100 pairs on the values at their own limits -- hi, hi + 1, lo, lo - 1, +-2^24, +-2^53, 2^31, 2^63, 2^64, NaN, inf,
+    -0.0, DBL_MAX: the decision, the whole error text and the result bits, safe and unsafe (P.check_cast_boundaries)."""
+    assert P.check_cast_boundaries(emu_ctx) > 1500
+
+
+@pytest.mark.parametrize("pair", P.LONE_OFFENDER_PAIRS, ids=lambda p: f"{p[0]}-{p[1]}")
+def test_cast_names_a_lone_offender_wherever_it_is(emu_ctx, pair):
+    """One failing row at the wave / block / tile / tail edges of a 4099-row array, under a null, and two of them in
+    different blocks (the atomicMin over blocks), for one pair per checking path of arx_cast_numeric."""
+    P.check_cast_lone_offender(emu_ctx, pair)
+
+
+@pytest.mark.parametrize("dtype", ["int8", "uint8", "int16", "uint16", "int32", "uint32", "int64", "uint64"])
+def test_checked_arithmetic_with_one_overflowing_row(emu_ctx, dtype):
+    """add / subtract / multiply (+ _checked) with a single overflowing row at every edge position and both slice offsets,
+    array x array and both scalar orders; nulls on either side hide it."""
+    P.check_arith_lone_overflow(emu_ctx, np.dtype(dtype))
+
+
+def test_add_pair_kernel_rows_and_tail(emu_ctx):
+    """Unchecked int64 / float64 add (the pair-loading add_kernel) on rows that all differ, odd length, both offsets."""
+    P.check_add_pair_kernel_tail(emu_ctx)
+
+
+@pytest.mark.parametrize("dtype", ["int8", "uint8", "int16", "uint16", "int32", "uint32", "int64", "uint64"])
+def test_divide_error_of_the_later_row(emu_ctx, dtype):
+    """A zero divisor and min / -1 in different blocks, in both orders: divide_checked names the later one."""
+    P.check_divide_ordering(emu_ctx, np.dtype(dtype))
+
+
+@pytest.mark.parametrize("dtype", list(P.NUMERIC_TYPES))
+def test_compare_and_arithmetic_over_the_whole_type(emu_ctx, dtype):
+    """Operands from the type's edges and its whole range (an unsigned comparison done as signed fails here)."""
+    P.check_compare_whole_range(emu_ctx, rng_for("whole-range", dtype), P.NUMERIC_TYPES[dtype])
+
+
 @pytest.mark.parametrize("key_dtype", [np.int8, np.uint16, np.uint32, np.int64, np.uint64])
 def test_groupby_sum_other_key_and_value_types(emu_ctx, key_dtype):
     rng = rng_for("gbtyped", str(key_dtype))
