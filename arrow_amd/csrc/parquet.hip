@@ -369,6 +369,7 @@ __global__ __launch_bounds__(kBlock) void snappy_decode_kernel(const uint8_t* __
     for (;;) {
       if (ip >= n_in || shift > 28) { err = 1; break; }
       const uint32_t c = in[ip++];
+      if (shift == 28 && c >= 16) { err = 1; break; }   // (the fifth byte holds bits 28..31 and ends the varint, as in the codec)
       ulen |= (c & 0x7Fu) << shift;
       if ((c & 0x80u) == 0) break;
       shift += 7;
@@ -484,6 +485,7 @@ __global__ __launch_bounds__(kBlock) void snappy_decode_lds_kernel(const uint8_t
     for (;;) {
       if (ip >= n_in || ip >= wlen || shift > 28) { err = 1; break; }
       const uint32_t c = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(win[ip++]));
+      if (shift == 28 && c >= 16) { err = 1; break; }   // (the fifth byte holds bits 28..31 and ends the varint, as in the codec)
       ulen |= (c & 0x7Fu) << shift;
       if ((c & 0x80u) == 0) break;
       shift += 7;
@@ -1113,9 +1115,10 @@ __device__ __forceinline__ uint32_t inflate_walk(InflateBits& b, const uint16_t*
   return 0xFFFFu;
 }
 
-// Builds count[] / symbol[] and the lookup table of one code from lengths[0, n).  Returns 0, or 4 for an over-subscribed
-// code (an incomplete code is accepted, as zlib accepts the single-code distance tables real encoders emit; its unassigned
-// codes fail when they are met).  Wave-uniform; lane 0 writes the serial tables, all lanes fill the lookup table.
+// Builds count[] / symbol[] and the lookup table of one code from lengths[0, n).  Returns 0, or 4 for a code zlib's
+// inflate_table rejects: an over-subscribed one, and an incomplete one unless it is a single code of length 1 (the
+// distance tables real encoders emit for one distance; its unassigned code fails when it is met) or has no codes at all.
+// Wave-uniform; lane 0 writes the serial tables, all lanes fill the lookup table.
 __device__ __forceinline__ uint32_t inflate_build(const uint8_t* lengths, int n, uint16_t* count, uint16_t* symbol, uint16_t* lut,
                                                    int lut_bits, int lane) {
   __builtin_amdgcn_wave_barrier();
@@ -1128,6 +1131,8 @@ __device__ __forceinline__ uint32_t inflate_build(const uint8_t* lengths, int n,
     left = (left << 1) - static_cast<int>(cnt[l]);
     if (left < 0) return 4;
   }
+  const int coded = n - static_cast<int>(cnt[0]);
+  if (left > 0 && coded != 0 && !(coded == 1 && cnt[1] == 1)) return 4;
   uint32_t offs[16], next_code[16];
   offs[1] = 0;
   next_code[0] = 0;
@@ -1173,9 +1178,9 @@ __device__ __forceinline__ uint32_t inflate_symbol(InflateBits& b, const uint16_
   return inflate_walk(b, count, symbol);
 }
 
-// status: 0 ok, 1 bad gzip / zlib header or the stream does not produce dst_size bytes, 2 the stream runs past its block or
-// the output, 3 a distance reaches before the output, 4 an invalid Huffman code (over-subscribed table, unassigned code,
-// bad block type or stored-block length)
+// status: 0 ok, 1 bad gzip / zlib header or the stream does not produce dst_size bytes, 2 the stream runs past its block
+// (whatever it then met in the zeros behind it) or the output, 3 a distance reaches before the output, 4 an invalid Huffman
+// code (over-subscribed or incomplete table, unassigned code, bad block type or stored-block length)
 __global__ __launch_bounds__(kInfThreads) void inflate_pages_kernel(const uint8_t* __restrict__ src, const ArxSnappyPage* __restrict__ pages,
                                                                int64_t npages, uint8_t* dst, uint32_t* __restrict__ status) {
   __shared__ InflateLds lds;
@@ -1210,8 +1215,9 @@ __global__ __launch_bounds__(kInfThreads) void inflate_pages_kernel(const uint8_
                              (static_cast<uint32_t>(in[n_in - 1]) << 24);
       if (isize != ulen) err = 1;
     }
-  } else if (n_in >= 6 && (in[0] & 0x0Fu) == 8 && ((static_cast<uint32_t>(in[0]) << 8) | in[1]) % 31u == 0 && (in[1] & 0x20u) == 0) {
-    start = 2;                                                 // zlib stream (RFC 1950), no preset dictionary
+  } else if (n_in >= 6 && (in[0] & 0x0Fu) == 8 && (in[0] >> 4) <= 7 && ((static_cast<uint32_t>(in[0]) << 8) | in[1]) % 31u == 0 &&
+             (in[1] & 0x20u) == 0) {
+    start = 2;                                                 // zlib stream (RFC 1950): a window of at most 32 KB, no preset dictionary
     trailer = 4;
   } else {
     err = 1;
@@ -1366,6 +1372,7 @@ __global__ __launch_bounds__(kInfThreads) void inflate_pages_kernel(const uint8_
     }
   }
   if (!err && (op != ulen || inflate_consumed(b) > b.n_in)) err = op != ulen ? 1 : 2;
+  if (err > 2 && inflate_consumed(b) > b.n_in) err = 2;   // (what the zeros behind a truncated stream decoded to is not the finding)
   if (lane == 0) status[pg] = err;
 }
 
