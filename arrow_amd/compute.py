@@ -1017,6 +1017,8 @@ def _build_registry() -> FunctionRegistry:
         for t in numeric_types:
             f.add_kernel(Kernel((t, t), _exec_compare_numeric(name), bool_))
         f.add_kernel(_temporal_pair_kernel(name))
+        for t in (type_from_name("string"), type_from_name("binary")):      # csrc/string_compare.hip
+            f.add_kernel(Kernel((t, t), _exec_compare_binary(name), bool_))
         reg.add_function(f)
 
     for name, op, checked in (("add", "add", False), ("subtract", "subtract", False), ("multiply", "multiply", False),
@@ -2439,6 +2441,62 @@ def starts_with(values: Array, pattern, *, ignore_case: bool = False) -> Array:
 def ends_with(values: Array, pattern, *, ignore_case: bool = False) -> Array:
     """compute::EndsWith: true where the row's last bytes are `pattern`.  See match_substring."""
     return _call_match_substring("ends_with", values, pattern, ignore_case)
+
+
+# --------------------------------------------------------------------------- string comparisons
+# equal .. less_equal of utf8 / binary operands (CompareKernel on BaseBinaryType, scalar_compare.cc): csrc/string_compare.hip.
+# The `path` handed to arx_compare_binary: 0 = the library chooses (rows, or waves from a mean pair size on), 1 = one
+# lane per row pair, 2 = one wave per row pair.  Tests set it to reach either form.
+STRING_COMPARE_PATH = 0
+
+
+def _literal_bytes(name: str, x: Scalar) -> bytes:
+    v = x.value
+    if isinstance(v, str):
+        return v.encode("utf-8")
+    if isinstance(v, (bytes, bytearray, memoryview)):
+        return bytes(v)
+    raise TypeError(f"{name}: a {x.type.name} scalar must hold str or bytes, not {type(v).__name__}")
+
+
+def _exec_compare_binary(op_name):
+    code = _CMP_CODE[op_name]
+
+    def run(args, options):
+        """CompareKernel<BinaryType / StringType, Op>::Exec (scalar_compare.cc): array x array, array x scalar, scalar x
+        array; one arx_compare_binary call, the validity is the intersection of the operands'."""
+        left, right = args
+        arrays = [a for a in args if isinstance(a, Array)]
+        if not arrays:
+            raise ArrowNotImplementedError(f"arrow_amd: {op_name} of two scalars on the device path")
+        if len(arrays) == 2 and left.length != right.length:
+            raise ArrowInvalid("Array arguments must all be the same length")
+        n, dev = arrays[0].length, arrays[0].device
+        lib, stream = _lib_and_stream(dev)
+        words = alloc(max(1, (n + 63) // 64) * 8, dev, zero=_has_null_scalar(left, right))
+        if not _has_null_scalar(left, right):
+            dlit, m = None, 0
+            for a in args:
+                if isinstance(a, Scalar):
+                    literal = _literal_bytes(op_name, a)
+                    m = len(literal)
+                    dlit = alloc(max(m, 1), dev)
+                    if m:
+                        dlit[:m].copy_(torch.frombuffer(bytearray(literal), dtype=torch.uint8))
+            spans = [a.binary_span() if isinstance(a, Array) else None for a in args]
+            hint = builtins.sum(_data_bytes_hint(a) for a in arrays)
+            with tracing.span("arx_compare_binary"):
+                check(lib.arx_compare_binary(code, *[None if s is None else C.byref(s) for s in spans], 4,
+                                             None if dlit is None else dlit.data_ptr(), m, builtins.max(hint, -1),
+                                             int(STRING_COMPARE_PATH), words.data_ptr(), stream))
+            # (dlit is dropped on return while the kernel may still be queued: see _match_substring)
+        validity, nc = _propagate_validity([left, right], n, dev)
+        out = Array(bool_, n, [validity, words], nc, 0)
+        if nc == kUnknownNullCount:
+            nbytes = (n + 7) // 8
+            out.set_lazy_null_count(lambda: n - int(np.unpackbits(validity[:nbytes].cpu().numpy(), bitorder="little")[:n].sum()))
+        return out
+    return run
 
 
 # --------------------------------------------------------------------------- string lengths and slices

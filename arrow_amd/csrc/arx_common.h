@@ -88,6 +88,7 @@ CounterTable if_else_counters();
 CounterTable temporal_counters();
 CounterTable string_slice_counters();
 CounterTable string_trim_counters();
+CounterTable string_compare_counters();
 
 #define ARX_HIP(call)                                          \
   do {                                                         \

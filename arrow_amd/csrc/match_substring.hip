@@ -17,8 +17,8 @@
 //         row range (offsets staged in LDS when they fit), accepts it if the match ends inside that row and the row is
 //         valid, and ORs the row's bit into the zeroed output.
 //
-// Pattern: a device pointer.  Up to kPatternLdsCap bytes it is staged once per workgroup in LDS; a longer one is read
-// where it lies through the same pointer variable (it stays in L2).  1 KiB holds every literal a filter is written
+// Pattern: a device pointer.  Up to kPatternLdsCap bytes (string_rows.h) it is staged once per workgroup in LDS; a
+// longer one is read where it lies through the same pointer variable (it stays in L2).  1 KiB holds every literal a filter is written
 // with and costs a workgroup 1/160 of the CU's LDS, no occupancy.
 //
 // Granule rule: a load touches only an aligned 8- or 16-byte piece that holds at least one referenced byte (of the row
@@ -27,16 +27,12 @@
 //
 // Worst case: no KMP / two-way table.  A hit of the 8-byte prefix starts a verify that restarts at the next position, so
 // a pattern a^k b against rows of a's costs O(row bytes x m) — quadratic in the adversarial case, linear for text.
-#include "arx_common.h"
-
-#include <algorithm>
-#include <atomic>
+#include "string_rows.h"
 
 namespace arx {
 
 namespace {
 
-constexpr int kPatternLdsCap = 1024;       // bytes of pattern staged in LDS (see the head comment)
 constexpr int kGranule = 16;               // bytes a lane of the bytes kernel owns
 constexpr int kTileBytes = kBlock * kGranule;   // 4 KiB of data per workgroup step
 constexpr int kStageOffsets = 2048;        // offsets of a tile's row range staged in LDS (a 4 KiB tile of >= 2-byte rows)
@@ -51,33 +47,12 @@ constexpr int64_t kBytesPathMeanRow = 128;
 
 std::atomic<int64_t> g_match_row_launches{0}, g_match_byte_launches{0};
 
-// up to 8 bytes at p (any alignment), of which the first `rem` >= 1 are referenced; the others read as zero.  One or
-// two aligned words, the second only if it holds a referenced byte.
-__device__ __forceinline__ uint64_t load_bytes8(const uint8_t* p, int64_t rem) {
-  const uint64_t addr = reinterpret_cast<uint64_t>(p);
-  const uint64_t* wp = reinterpret_cast<const uint64_t*>(addr & ~uint64_t(7));
-  const int sh = static_cast<int>(addr & 7);
-  uint64_t w = wp[0] >> (sh * 8);
-  if (sh != 0 && (8 - sh) < rem) w |= wp[1] << (64 - sh * 8);
-  if (rem < 8) w &= (uint64_t(1) << (8 * rem)) - 1;
-  return w;
-}
-
 // a[0, len) == b[0, len), len >= 0, every byte of both referenced
 __device__ __forceinline__ bool bytes_equal(const uint8_t* a, const uint8_t* b, int64_t len) {
   for (int64_t k = 0; k < len; k += 8) {
     if (load_bytes8(a + k, len - k) != load_bytes8(b + k, len - k)) return false;
   }
   return true;
-}
-
-// the pattern for this workgroup: staged in `s_pat` (zero-padded to whole words) when it fits, else where it lies
-__device__ __forceinline__ const uint8_t* stage_pattern(uint64_t* s_pat, const uint8_t* g_pat, int64_t m) {
-  if (m > kPatternLdsCap) return g_pat;
-  const int words = static_cast<int>((m + 7) >> 3);
-  for (int i = threadIdx.x; i < words; i += kBlock) s_pat[i] = load_bytes8(g_pat + 8 * i, m - 8 * i);
-  __syncthreads();
-  return reinterpret_cast<const uint8_t*>(s_pat);
 }
 
 struct Prefix {
@@ -254,17 +229,6 @@ __global__ __launch_bounds__(kBlock) void match_bytes_kernel(Bits valid, const O
     }
     r_lo += r_count - 1;                                    // the row of this tile's last byte may go on in the next tile
   }
-}
-
-int device_cus() {
-  static std::atomic<int> cus{0};
-  int c = cus.load(std::memory_order_relaxed);
-  if (c == 0) {
-    int dev = 0, n = 0;
-    c = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-    cus.store(c, std::memory_order_relaxed);
-  }
-  return c;
 }
 
 template <typename O>

@@ -4,7 +4,7 @@
 // ---------------------------------------------------------------- device arrays must not reach a CPU kernel
 // Arrow's executors hand any kernel whatever buffers the arrays hold: a stock CPU kernel given a kROCM array reads
 // Buffer::data() == nullptr (buffer.h:221-226) or an HBM address — a crash inside libarrow.  The shim registers device
-// kernels for the types of its path; for every OTHER type of the functions it touches (strings under `equal`, booleans
+// kernels for the types of its path; for every OTHER type of the functions it touches (fixed_size_binary under `equal`, booleans
 // under `unique`, decimals under `add`, large_utf8 under `array_filter`, ...) the reference kernel is re-registered as a
 // copy whose exec first looks at the operands: device-resident -> NotImplemented naming the function and the type,
 // host -> the reference's exec, untouched (same init, same null handling, same preallocation contract: the copy keeps

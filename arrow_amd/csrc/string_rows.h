@@ -1,5 +1,6 @@
-// What the row-wise string kernels share (string_slice.hip, string_trim.hip): the bit-7 byte masks of a 16-byte granule,
-// the view of a values column, the grid of a one-lane-per-row launch and the argument checks of their C entry points.
+// What the row-wise string kernels share (string_slice.hip, string_trim.hip, match_substring.hip, string_compare.hip):
+// the bit-7 byte masks of a 16-byte granule, the unaligned 8-byte read and the LDS staging of a literal operand, the view
+// of a values column, the grid of a one-lane-per-row launch and the argument checks of their C entry points.
 #pragma once
 #include "binary_scan_copy.h"
 
@@ -18,6 +19,30 @@ __device__ __forceinline__ uint64_t byte_range_bit7(int64_t from, int64_t to) {
   const uint64_t below_to = to >= 8 ? ~uint64_t(0) : ((uint64_t(1) << (8 * to)) - 1);
   const uint64_t below_from = (uint64_t(1) << (8 * from)) - 1;   // from < 8 here
   return below_to & ~below_from & kBit7;
+}
+
+// up to 8 bytes at p (any alignment), of which the first `rem` >= 1 are referenced; the others read as zero.  One or
+// two aligned words, the second only if it holds a referenced byte.
+__device__ __forceinline__ uint64_t load_bytes8(const uint8_t* p, int64_t rem) {
+  const uint64_t addr = reinterpret_cast<uint64_t>(p);
+  const uint64_t* wp = reinterpret_cast<const uint64_t*>(addr & ~uint64_t(7));
+  const int sh = static_cast<int>(addr & 7);
+  uint64_t w = wp[0] >> (sh * 8);
+  if (sh != 0 && (8 - sh) < rem) w |= wp[1] << (64 - sh * 8);
+  if (rem < 8) w &= (uint64_t(1) << (8 * rem)) - 1;
+  return w;
+}
+
+// A literal operand (the pattern of match_substring.hip, the scalar side of string_compare.hip): a device pointer.  Up to
+// kPatternLdsCap bytes it is staged once per workgroup in LDS; a longer one is read where it lies (it stays in L2).
+constexpr int kPatternLdsCap = 1024;
+// the literal for this workgroup: staged in `s_pat` (zero-padded to whole words) when it fits, else where it lies
+__device__ __forceinline__ const uint8_t* stage_pattern(uint64_t* s_pat, const uint8_t* g_pat, int64_t m) {
+  if (m > kPatternLdsCap) return g_pat;
+  const int words = static_cast<int>((m + 7) >> 3);
+  for (int i = threadIdx.x; i < words; i += kBlock) s_pat[i] = load_bytes8(g_pat + 8 * i, m - 8 * i);
+  __syncthreads();
+  return reinterpret_cast<const uint8_t*>(s_pat);
 }
 
 inline int device_cus() {

@@ -1375,6 +1375,36 @@ enum {
 int arx_string_trim_offsets(const ArxBinarySpan* values, int offset_width, int sides, int set_kind, const void* set,
                             int64_t set_length, void* ws, size_t ws_bytes, void* out_offsets, int64_t* out_total_bytes,
                             void* stream);
+/* Comparisons of utf8 / binary rows — equal, not_equal, greater, greater_equal, less, less_equal (CompareKernel on
+ * BaseBinaryType, compute/kernels/scalar_compare.cc; csrc/string_compare.hip).  The order is the reference's
+ * (std::string_view): bytes compare as unsigned bytes over the common length, then the shorter row is less.  No UTF-8
+ * awareness; a '\0' is an ordinary byte.
+ * op: ARX_CMP_EQUAL .. ARX_CMP_LESS_EQUAL, out = left op right.  The sides are array x array, array x literal
+ * (right == NULL) or literal x array (left == NULL); `literal` is a DEVICE pointer to literal_length >= 0 bytes, alive
+ * until the stream reaches the call's end, and stands for the NULL side.  offset_width (4: utf8 / binary, 8: the large
+ * forms) holds for both arrays; each has its own offset; two arrays have the same length.
+ * out_bits: ceil(length / 64) 64-bit words at offset 0; bit i = the answer of row i, 0 where either side is null (a null
+ * row's bytes are never read, whatever its offsets span).  The result's validity is the intersection of the inputs':
+ * the caller makes it (arx_bitmap_copy / arx_bitmap_and).
+ * path: ARX_COMPARE_PATH_ROWS = one lane per row pair, walking 8-byte pieces up to the first difference (equal /
+ * not_equal of rows of different length read no data byte); ARX_COMPARE_PATH_WAVES = one wave per row pair, its lanes on
+ * consecutive 16-byte granules (long rows with long shared prefixes); ARX_COMPARE_PATH_AUTO = waves when the bytes a
+ * pair may have to read, data_bytes_hint / length (with a literal: twice the smaller of that and literal_length),
+ * reach a fixed threshold.  data_bytes_hint: the size of the arrays' data buffers (summed for two arrays) or -1 if
+ * unknown (auto then takes rows).
+ * A load touches only aligned 16-byte granules that hold at least one referenced byte of a valid row (of the literal for
+ * literal reads).
+ * ARX_INVALID, with nothing launched or written, for both sides NULL, an op, path or offset_width outside the above,
+ * unequal or negative lengths, a negative literal_length or a NULL literal with literal_length > 0, and for length > 0
+ * NULL out_bits or NULL offsets.  length == 0 succeeds and launches nothing.  Asynchronous; no read-back.
+ * arx_get_counter("string_compare_row_launches" / "string_compare_wave_launches") counts the launches of each form. */
+enum {
+  ARX_COMPARE_PATH_AUTO = 0,
+  ARX_COMPARE_PATH_ROWS = 1,
+  ARX_COMPARE_PATH_WAVES = 2
+};
+int arx_compare_binary(int op, const ArxBinarySpan* left, const ArxBinarySpan* right, int offset_width, const void* literal,
+                       int64_t literal_length, int64_t data_bytes_hint, int path, void* out_bits, void* stream);
 /* if_else(cond, left, right) of ONE fixed-width type or boolean (IfElseFunctor, compute/kernels/scalar_if_else.cc; csrc/if_else.hip):
  * out[i] = cond[i] ? left[i] : right[i]; out is null where cond is null (whatever its data bit says), else it takes the
  * validity of the chosen operand: valid = cv & ((c & lv) | (~c & rv)), booleans data = (c & l) | (~c & r).
