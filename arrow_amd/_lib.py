@@ -239,6 +239,9 @@ SIGNATURES = {
     "arx_string_slice_offsets": (_int, [_bspan, _int, _int, _i64, _i64, _i64, _int, _p, _sz, _p, C.POINTER(_i64), _p]),
     "arx_string_slice_data": (_int, [_bspan, _int, _p, _sz, _p, _i64, _p, _p]),
     "arx_string_trim_offsets": (_int, [_bspan, _int, _int, _int, _p, _i64, _p, _sz, _p, C.POINTER(_i64), _p]),
+    "arx_replace_substring_workspace_bytes": (_sz, [_i64, _int]),
+    "arx_replace_substring_offsets": (_int, [_bspan, _int, _p, _i64, _i64, _i64, _i64, _int, _p, _sz, _p, C.POINTER(_i64), _p]),
+    "arx_replace_substring_data": (_int, [_bspan, _int, _p, _i64, _p, _i64, _i64, _int, _p, _sz, _p, _i64, _p, _p]),
     "arx_compare_binary": (_int, [_int, _bspan, _bspan, _int, _p, _i64, _i64, _int, _p, _p]),
     "arx_if_else": (_int, [_int, _span, _span, _p, _span, _p, _i64, _p, _p, _p]),
     "arx_temporal_component": (_int, [_int, _int, _span, _i64, _int, _int, _p, _p, _p]),

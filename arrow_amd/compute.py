@@ -110,6 +110,16 @@ class TrimOptions(FunctionOptions):
         self.characters = characters
 
 
+class ReplaceSubstringOptions(FunctionOptions):
+    """api_scalar.h ReplaceSubstringOptions: the literal `pattern` and its `replacement` (str, UTF-8 encoded, or bytes) and
+    max_replacements, the matches replaced in each row (None or negative: all of them)."""
+
+    def __init__(self, pattern="", replacement="", max_replacements=None):
+        self.pattern = pattern
+        self.replacement = replacement
+        self.max_replacements = None if max_replacements is None else int(max_replacements)
+
+
 class DayOfWeekOptions(FunctionOptions):
     """api_scalar.h DayOfWeekOptions: count_from_zero (Monday = 0 rather than 1 at the defaults) and week_start, the ISO
     weekday (Monday = 1 .. Sunday = 7) the numbering starts at."""
@@ -1064,6 +1074,11 @@ def _build_registry() -> FunctionRegistry:
         f = Function(name, Function.SCALAR, 1, SliceOptions())
         f.add_kernel(Kernel((_STRING_INPUT[name],), _exec_string_slice(name)))
         reg.add_function(f)
+    # replace_substring of utf8 / binary rows (csrc/string_replace.hip)
+    f = Function("replace_substring", Function.SCALAR, 1)
+    for t in (type_from_name("string"), type_from_name("binary")):
+        f.add_kernel(Kernel((t,), _exec_replace_substring))
+    reg.add_function(f)
     # the twelve trims of utf8 rows (csrc/string_trim.hip)
     for name in _TRIMS:
         f = Function(name, Function.SCALAR, 1)
@@ -2505,6 +2520,8 @@ def _exec_compare_binary(op_name):
 # the codepoint walk: 0 = the library chooses (rows, or waves from a mean row size on), 1 = one lane per row, 2 = one
 # wave per row.  Tests set it to reach either form.
 STRING_SLICE_PATH = 0
+# the same for arx_replace_substring_offsets / _data (csrc/string_replace.hip): 0 = the library chooses, 1 = rows, 2 = waves
+STRING_REPLACE_PATH = 0
 _STRING_UNIT = {"binary_length": 0, "utf8_length": 1, "binary_slice": 0, "utf8_slice_codeunits": 1}
 _NO_STOP = 2**63 - 1            # stop = INT64_MAX: to the row's end
 _BINARY_ONLY = lambda t: t.name == "binary"  # noqa: E731
@@ -2572,23 +2589,29 @@ def _exec_string_slice(name: str):
     return run
 
 
-def _sub_range_result(values: Array, span_name: str, offsets_call) -> Array:
-    """The result of a function whose every row is a sub-range of the input's row (slices, trims).
-    `offsets_call(lib, vspan, ws, ws_bytes, out_offsets, total, stream)` writes the n + 1 offsets and leaves each row's
-    source position in the workspace; arx_string_slice_data copies the bytes and the validity is the input's."""
+def _slice_data_call(lib, vspan, *rest):
+    return lib.arx_string_slice_data(vspan, 4, *rest)
+
+
+def _sub_range_result(values: Array, span_name: str, offsets_call, data_name: str = "arx_string_slice_data",
+                      data_call=_slice_data_call, workspace_bytes: str = "arx_string_slice_workspace_bytes") -> Array:
+    """The result of a function whose rows are made from the input's rows, one for one (slices, trims, replace_substring).
+    `offsets_call(lib, vspan, ws, ws_bytes, out_offsets, total, stream)` writes the n + 1 offsets and leaves in the
+    workspace what `data_call(lib, vspan, ws, ws_bytes, out_offsets, total_bytes, out_data, stream)` needs to write the
+    bytes: for a row that is a sub-range of the input's row its source position, and arx_string_slice_data copies.  The
+    validity is the input's."""
     dev = values.device
     lib, stream = _lib_and_stream(dev)
     n = values.length
     out_offsets = alloc((n + 1) * 4, dev)
-    ws = _workspace(dev, lib.arx_string_slice_workspace_bytes(n, 4), "string_slice")
+    ws = _workspace(dev, getattr(lib, workspace_bytes)(n, 4), "string_slice")
     total = C.c_int64(0)
     vspan = values.binary_span()
     with tracing.span(span_name):
         check(offsets_call(lib, C.byref(vspan), ws.data_ptr(), ws.numel(), out_offsets.data_ptr(), C.byref(total), stream))
     out_data = alloc(total.value, dev)
-    with tracing.span("arx_string_slice_data"):
-        check(lib.arx_string_slice_data(C.byref(vspan), 4, ws.data_ptr(), ws.numel(), out_offsets.data_ptr(), total.value,
-                                        out_data.data_ptr(), stream))
+    with tracing.span(data_name):
+        check(data_call(lib, C.byref(vspan), ws.data_ptr(), ws.numel(), out_offsets.data_ptr(), total.value, out_data.data_ptr(), stream))
     valid, count = _input_validity(values, lib, stream)
     return _with_null_count(Array(values.type, n, [valid, out_offsets, out_data], kUnknownNullCount, 0), count)
 
@@ -2607,7 +2630,7 @@ def _call_string_function(name: str, values, options, *reference_args) -> Array:
 
 _STRING_INPUT = {"binary_length": is_base_binary, "utf8_length": _UTF8_ONLY, "binary_slice": _BINARY_ONLY,
                  "utf8_slice_codeunits": _UTF8_ONLY, "match_substring": is_base_binary, "starts_with": is_base_binary,
-                 "ends_with": is_base_binary}
+                 "ends_with": is_base_binary, "replace_substring": is_base_binary}
 
 
 def binary_length(values: Array) -> Array:
@@ -2633,6 +2656,55 @@ def utf8_slice_codeunits(values: Array, start: int, stop=None, step: int = 1) ->
     """compute::UTF8SliceCodeunits under SliceOptions: Python's s[start:stop] of each row of a utf8 array, counted in
     codepoints.  See binary_slice."""
     return _call_string_function("utf8_slice_codeunits", values, SliceOptions(start, stop, step), 0)
+
+
+# --------------------------------------------------------------------------- replace_substring
+# compute::ReplaceSubstring with a literal pattern (PlainSubstringReplacer, scalar_string_ascii.cc):
+# csrc/string_replace.hip.  The rows are assembled, not sub-ranges: arx_replace_substring_offsets counts every row's
+# matches, arx_replace_substring_data writes "gap, replacement, gap, ...".
+def _literal_operand(name: str, what: str, x) -> bytes:
+    if isinstance(x, str):
+        return x.encode("utf-8")
+    if isinstance(x, (bytes, bytearray, memoryview)):
+        return bytes(x)
+    raise TypeError(f"{name}: {what} must be str or bytes, not {type(x).__name__}")
+
+
+def _exec_replace_substring(args, options):
+    name = "replace_substring"
+    (values,) = args
+    if not isinstance(values, Array):
+        raise ArrowNotImplementedError(f"arrow_amd: {name} of a scalar on the device path")
+    if options is None:
+        raise ArrowInvalid(f"Function '{name}' cannot be called without options")
+    pattern = _literal_operand(name, "pattern", options.pattern)
+    replacement = _literal_operand(name, "replacement", options.replacement)
+    if not pattern:
+        raise ArrowNotImplementedError(f"arrow_amd: {name} with an empty pattern on device-resident arrays: there is no device "
+                                       "kernel (the reference does not terminate on it with unlimited replacements)")
+    cap = -1 if options.max_replacements is None or options.max_replacements < 0 else min(int(options.max_replacements), 2**63 - 1)
+    dev = values.device
+    m, r = len(pattern), len(replacement)
+    literals = alloc(m + max(r, 1), dev)                          # copied to the device once per call: pattern, replacement
+    literals[:m + r].copy_(torch.frombuffer(bytearray(pattern + replacement), dtype=torch.uint8))
+    dpat, drep = literals.data_ptr(), literals.data_ptr() + m
+    path = int(STRING_REPLACE_PATH)
+    # (literals is dropped on return while the kernels may still be queued: see _match_substring)
+    return _sub_range_result(
+        values, "arx_replace_substring_offsets",
+        lambda lib, vspan, *rest: lib.arx_replace_substring_offsets(vspan, 4, dpat, m, r, cap, _data_bytes_hint(values), path, *rest),
+        "arx_replace_substring_data",
+        lambda lib, vspan, *rest: lib.arx_replace_substring_data(vspan, 4, dpat, m, drep, r, cap, path, *rest),
+        "arx_replace_substring_workspace_bytes")
+
+
+def replace_substring(values: Array, pattern, replacement, *, max_replacements=None) -> Array:
+    """compute::ReplaceSubstring under ReplaceSubstringOptions: each row of a utf8 / binary array with the non-overlapping
+    matches of the literal `pattern` (str, UTF-8 encoded, or bytes), found left to right, replaced by `replacement`;
+    max_replacements None or negative replaces all of them, 0 none, k > 0 the first k of each row.  Bytes are bytes; a null
+    row stays null and holds no bytes.  The empty pattern raises ArrowNotImplementedError (there is no CPU fallback); a
+    result past int32 offsets raises ArrowInvalid ("offset overflow").  The result stays on the device."""
+    return _call_string_function("replace_substring", values, ReplaceSubstringOptions(pattern, replacement, max_replacements), "x", "y")
 
 
 # --------------------------------------------------------------------------- string trimming

@@ -89,6 +89,7 @@ CounterTable temporal_counters();
 CounterTable string_slice_counters();
 CounterTable string_trim_counters();
 CounterTable string_compare_counters();
+CounterTable string_replace_counters();
 
 #define ARX_HIP(call)                                          \
   do {                                                         \

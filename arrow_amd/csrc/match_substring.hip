@@ -47,44 +47,9 @@ constexpr int64_t kBytesPathMeanRow = 128;
 
 std::atomic<int64_t> g_match_row_launches{0}, g_match_byte_launches{0};
 
-// a[0, len) == b[0, len), len >= 0, every byte of both referenced
-__device__ __forceinline__ bool bytes_equal(const uint8_t* a, const uint8_t* b, int64_t len) {
-  for (int64_t k = 0; k < len; k += 8) {
-    if (load_bytes8(a + k, len - k) != load_bytes8(b + k, len - k)) return false;
-  }
-  return true;
-}
-
-struct Prefix {
-  uint64_t bytes, mask;   // the pattern's first min(m, 8) bytes and the mask of those bytes
-};
-__device__ __forceinline__ Prefix pattern_prefix(const uint8_t* pat, int64_t m) {
-  Prefix p;
-  p.mask = m >= 8 ? ~uint64_t(0) : ((uint64_t(1) << (8 * m)) - 1);
-  p.bytes = load_bytes8(pat, m < 8 ? m : 8);
-  return p;
-}
-
-// does row[0, len) contain pat[0, m)?  1 <= m <= len.
+// does row[0, len) contain pat[0, m)?  1 <= m <= len.  (the window walk: row_find of string_rows.h)
 __device__ __forceinline__ bool row_contains(const uint8_t* row, int64_t len, const uint8_t* pat, int64_t m, Prefix pfx) {
-  const uint64_t addr = reinterpret_cast<uint64_t>(row);
-  const uint64_t end = addr + static_cast<uint64_t>(len);
-  const uint64_t* wp = reinterpret_cast<const uint64_t*>(addr & ~uint64_t(7));
-  int b = static_cast<int>(addr & 7);
-  const int64_t last = len - m;          // the last start position
-  uint64_t cur = wp[0];
-  for (int64_t p = 0; p <= last;) {
-    // the next word only if it holds a byte of the row
-    const uint64_t next = reinterpret_cast<uint64_t>(wp + 1) < end ? wp[1] : 0;
-    for (; b < 8 && p <= last; ++b, ++p) {
-      const uint64_t win = b == 0 ? cur : ((cur >> (8 * b)) | (next << (64 - 8 * b)));
-      if (((win ^ pfx.bytes) & pfx.mask) == 0 && (m <= 8 || bytes_equal(row + p + 8, pat + 8, m - 8))) return true;
-    }
-    b = 0;
-    cur = next;
-    ++wp;
-  }
-  return false;
+  return row_find(row, len, pat, m, pfx, 0) >= 0;
 }
 
 // ---------------------------------------------------------------- rows

@@ -272,28 +272,37 @@ Status CopyInputValidity(const ArxBinarySpan& vs, int64_t n, hipStream_t st, Arr
   return Status::OK();
 }
 
-// The device result of a function whose every row is a sub-range of the input's row (slices, trims): `offsets_call`
-// (vs, offset_width, ws, ws_bytes, d_off, &total, st) writes the n + 1 offsets and leaves each row's source position in
-// the workspace, arx_string_slice_data copies the bytes, the validity is the input's.  One synchronisation, at the end.
-template <class OffsetsCall>
-Status SubRangeResultOnDevice(Fn fn, const ArxBinarySpan& vs, int offset_width, hipStream_t st, OffsetsCall&& offsets_call,
-                              ArrayData* out_arr) {
+// The device result of a function that makes one variable-length row from each row of the input (slices, trims,
+// replace_substring): `offsets_call` (vs, offset_width, ws, ws_bytes, d_off, &total, st) writes the n + 1 offsets and
+// leaves in the workspace of ws_bytes bytes what `data_call` (vs, offset_width, ws, ws_bytes, d_off, total, d_data, st)
+// needs to write the bytes; the validity is the input's.  One synchronisation, at the end.
+template <class OffsetsCall, class DataCall>
+Status VarLengthResultOnDevice(Fn fn, const ArxBinarySpan& vs, int offset_width, hipStream_t st, size_t ws_bytes, OffsetsCall&& offsets_call,
+                               DataCall&& data_call, ArrayData* out_arr) {
   const int64_t n = vs.length;
   out_arr->length = n;
   out_arr->offset = 0;
   out_arr->buffers.assign(3, nullptr);
   ARROW_ASSIGN_OR_RAISE(out_arr->buffers[1], AllocDevice((n + 1) * offset_width));
-  const size_t ws_bytes = arx_string_slice_workspace_bytes(n, offset_width);
   void* ws = nullptr;
   ARROW_RETURN_NOT_OK(t_scratch.Get(kBinWs, ws_bytes, &ws));
   void* d_off = reinterpret_cast<void*>(out_arr->buffers[1]->mutable_address());
   int64_t total = 0;
   ARROW_RETURN_NOT_OK(FromArx(offsets_call(&vs, offset_width, ws, ws_bytes, d_off, &total, st)));
   ARROW_ASSIGN_OR_RAISE(out_arr->buffers[2], AllocDevice(std::max<int64_t>(total, 8)));
-  ARROW_RETURN_NOT_OK(FromArx(arx_string_slice_data(&vs, offset_width, ws, ws_bytes, d_off, total,
-                                                    reinterpret_cast<void*>(out_arr->buffers[2]->mutable_address()), st)));
+  ARROW_RETURN_NOT_OK(FromArx(data_call(&vs, offset_width, ws, ws_bytes, d_off, total,
+                                        reinterpret_cast<void*>(out_arr->buffers[2]->mutable_address()), st)));
   ARROW_RETURN_NOT_OK(CopyInputValidity(vs, n, st, out_arr));
   HIP_RETURN_NOT_OK(hipStreamSynchronize(st));   // (this thread's scratch may be released after return)
   CountGpu(fn);
   return Status::OK();
+}
+
+// The same for a function whose every row is a sub-range of the input's row (slices, trims): the offsets call leaves each
+// row's source position in the workspace and arx_string_slice_data copies the bytes.
+template <class OffsetsCall>
+Status SubRangeResultOnDevice(Fn fn, const ArxBinarySpan& vs, int offset_width, hipStream_t st, OffsetsCall&& offsets_call,
+                              ArrayData* out_arr) {
+  return VarLengthResultOnDevice(fn, vs, offset_width, st, arx_string_slice_workspace_bytes(vs.length, offset_width),
+                                 std::forward<OffsetsCall>(offsets_call), arx_string_slice_data, out_arr);
 }

@@ -1,5 +1,6 @@
-// What the row-wise string kernels share (string_slice.hip, string_trim.hip, match_substring.hip, string_compare.hip):
-// the bit-7 byte masks of a 16-byte granule, the unaligned 8-byte read and the LDS staging of a literal operand, the view
+// What the row-wise string kernels share (string_slice.hip, string_trim.hip, match_substring.hip, string_compare.hip,
+// string_replace.hip): the bit-7 byte masks of a 16-byte granule, the unaligned 8-byte read and the LDS staging of a
+// literal operand, the window walk that finds a pattern's next match in a row, the view
 // of a values column, the grid of a one-lane-per-row launch and the argument checks of their C entry points.
 #pragma once
 #include "binary_scan_copy.h"
@@ -33,7 +34,8 @@ __device__ __forceinline__ uint64_t load_bytes8(const uint8_t* p, int64_t rem) {
   return w;
 }
 
-// A literal operand (the pattern of match_substring.hip, the scalar side of string_compare.hip): a device pointer.  Up to
+// A literal operand (the pattern of match_substring.hip, the scalar side of string_compare.hip, the pattern and the
+// replacement of string_replace.hip): a device pointer.  Up to
 // kPatternLdsCap bytes it is staged once per workgroup in LDS; a longer one is read where it lies (it stays in L2).
 constexpr int kPatternLdsCap = 1024;
 // the literal for this workgroup: staged in `s_pat` (zero-padded to whole words) when it fits, else where it lies
@@ -43,6 +45,49 @@ __device__ __forceinline__ const uint8_t* stage_pattern(uint64_t* s_pat, const u
   for (int i = threadIdx.x; i < words; i += kBlock) s_pat[i] = load_bytes8(g_pat + 8 * i, m - 8 * i);
   __syncthreads();
   return reinterpret_cast<const uint8_t*>(s_pat);
+}
+
+// a[0, len) == b[0, len), len >= 0, every byte of both referenced
+__device__ __forceinline__ bool bytes_equal(const uint8_t* a, const uint8_t* b, int64_t len) {
+  for (int64_t k = 0; k < len; k += 8) {
+    if (load_bytes8(a + k, len - k) != load_bytes8(b + k, len - k)) return false;
+  }
+  return true;
+}
+
+struct Prefix {
+  uint64_t bytes, mask;   // the pattern's first min(m, 8) bytes and the mask of those bytes
+};
+__device__ __forceinline__ Prefix pattern_prefix(const uint8_t* pat, int64_t m) {
+  Prefix p;
+  p.mask = m >= 8 ? ~uint64_t(0) : ((uint64_t(1) << (8 * m)) - 1);
+  p.bytes = load_bytes8(pat, m < 8 ? m : 8);
+  return p;
+}
+
+// the first position p >= from at which row[p, p + m) == pat[0, m), or -1.  1 <= m, 0 <= from.  The lane walks the
+// aligned 8-byte words of row[from, len) with a two-word sliding window: at every byte position one masked 64-bit compare
+// tests the pattern's first min(m, 8) bytes, a hit verifies the remaining m - 8 bytes word by word.
+__device__ __forceinline__ int64_t row_find(const uint8_t* row, int64_t len, const uint8_t* pat, int64_t m, Prefix pfx, int64_t from) {
+  const int64_t last = len - m;          // the last start position
+  if (from > last) return -1;
+  const uint64_t addr = reinterpret_cast<uint64_t>(row) + static_cast<uint64_t>(from);
+  const uint64_t end = reinterpret_cast<uint64_t>(row) + static_cast<uint64_t>(len);
+  const uint64_t* wp = reinterpret_cast<const uint64_t*>(addr & ~uint64_t(7));
+  int b = static_cast<int>(addr & 7);
+  uint64_t cur = wp[0];
+  for (int64_t p = from; p <= last;) {
+    // the next word only if it holds a byte of the row
+    const uint64_t next = reinterpret_cast<uint64_t>(wp + 1) < end ? wp[1] : 0;
+    for (; b < 8 && p <= last; ++b, ++p) {
+      const uint64_t win = b == 0 ? cur : ((cur >> (8 * b)) | (next << (64 - 8 * b)));
+      if (((win ^ pfx.bytes) & pfx.mask) == 0 && (m <= 8 || bytes_equal(row + p + 8, pat + 8, m - 8))) return p;
+    }
+    b = 0;
+    cur = next;
+    ++wp;
+  }
+  return -1;
 }
 
 inline int device_cus() {

@@ -1375,6 +1375,51 @@ enum {
 int arx_string_trim_offsets(const ArxBinarySpan* values, int offset_width, int sides, int set_kind, const void* set,
                             int64_t set_length, void* ws, size_t ws_bytes, void* out_offsets, int64_t* out_total_bytes,
                             void* stream);
+/* replace_substring of utf8 / binary rows with a literal pattern — the reference's PlainSubstringReplacer under
+ * ReplaceSubstringOptions{pattern, replacement, max_replacements} (compute/kernels/scalar_string_ascii.cc;
+ * csrc/string_replace.hip).  Bytes are bytes: no UTF-8 awareness, '\0' and 0xff are ordinary bytes.
+ * values: utf8 / binary (offset_width 4) or large_utf8 / large_binary (offset_width 8), any offset.  The output type is
+ * the input's; a null row stays null and holds no bytes whatever its offsets span (its bytes are never read); the
+ * result's validity is the input's: the caller copies it (arx_bitmap_copy).  Outputs start at offset 0.
+ * Matches are found left to right and do not overlap: after a match at p the search resumes at p + pattern_length, the
+ * replacement is never searched, and a match lies wholly inside its row.  max_replacements < 0: every match; 0: the rows
+ * unchanged; k > 0: the first k matches of each row.  An empty replacement deletes the matches.  The empty pattern has
+ * no kernel (pattern_length <= 0: ARX_INVALID) — the reference does not terminate on it with unlimited replacements.
+ * pattern / replacement: DEVICE pointers to pattern_length >= 1 / replacement_length >= 0 bytes, alive until the stream
+ * reaches the call's end (the offsets call reads the pattern only).
+ * path: ARX_REPLACE_PATH_ROWS = one lane per row, ARX_REPLACE_PATH_WAVES = one wave per row, its lanes on consecutive
+ * 16-byte granules (long or skewed rows), ARX_REPLACE_PATH_AUTO = waves when the mean row size reaches a fixed
+ * threshold: data_bytes_hint / length in the offsets call (data_bytes_hint: the size of the values' data buffer or -1 if
+ * unknown, auto then takes rows), total_bytes / length in the data call.  The two calls need not take the same form.
+ * A load touches only aligned 8- or 16-byte pieces that hold at least one referenced byte of a valid row or of a literal.
+ * arx_replace_substring_offsets: step one.  ws: arx_replace_substring_workspace_bytes(length, offset_width) device bytes,
+ * 8-byte aligned; it receives every row's number of replacements and serves the data call.  out_offsets: length + 1
+ * entries of offset_width bytes, the result's offsets; *out_total_bytes = their last entry.  Row lengths are computed in
+ * 64 bits; a total that does not fit int32 offsets (offset_width 4) is ARX_INVALID "offset overflow while ..." before
+ * any offset is written (the reference raises ArrowCapacityError from its builder).  Synchronous (one read-back: the
+ * total).
+ * arx_replace_substring_data: step two, writes total_bytes bytes into out_data with the same values, pattern,
+ * max_replacements, ws and out_offsets.  Asynchronous.
+ * ARX_INVALID, with nothing launched or written, for a path or offset_width outside the above, a negative length or
+ * total_bytes, pattern_length <= 0, a negative replacement_length, a NULL pattern, a NULL replacement with
+ * replacement_length > 0, NULL values / out_offsets / out_total_bytes, and for length > 0 NULL offsets, a ws that is
+ * NULL, unaligned or too small, and NULL out_data / data with total_bytes > 0.  length == 0 succeeds and launches
+ * nothing; the offsets call then writes out_offsets[0] = 0 and *out_total_bytes = 0, the data call nothing.
+ * arx_get_counter("string_replace_row_launches" / "string_replace_wave_launches") counts the launches of each form (one
+ * per call with length > 0). */
+enum {
+  ARX_REPLACE_PATH_AUTO = 0,
+  ARX_REPLACE_PATH_ROWS = 1,
+  ARX_REPLACE_PATH_WAVES = 2
+};
+size_t arx_replace_substring_workspace_bytes(int64_t length, int offset_width);
+int arx_replace_substring_offsets(const ArxBinarySpan* values, int offset_width, const void* pattern, int64_t pattern_length,
+                                  int64_t replacement_length, int64_t max_replacements, int64_t data_bytes_hint, int path,
+                                  void* ws, size_t ws_bytes, void* out_offsets, int64_t* out_total_bytes, void* stream);
+int arx_replace_substring_data(const ArxBinarySpan* values, int offset_width, const void* pattern, int64_t pattern_length,
+                               const void* replacement, int64_t replacement_length, int64_t max_replacements, int path,
+                               const void* ws, size_t ws_bytes, const void* out_offsets, int64_t total_bytes, void* out_data,
+                               void* stream);
 /* Comparisons of utf8 / binary rows — equal, not_equal, greater, greater_equal, less, less_equal (CompareKernel on
  * BaseBinaryType, compute/kernels/scalar_compare.cc; csrc/string_compare.hip).  The order is the reference's
  * (std::string_view): bytes compare as unsigned bytes over the common length, then the shorter row is less.  No UTF-8
