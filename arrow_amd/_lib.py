@@ -210,6 +210,9 @@ SIGNATURES = {
     "arx_compare_numeric": (_int, [_int, _int, _p, _p, _p, _p, _i64, _p, _p]),
     "arx_arith_numeric": (_int, [_int, _int, _int, _p, _p, _p, _i64, _p, _p, _p, _i64, _i64, _p, _p, _p]),
     "arx_divide_numeric": (_int, [_int, _int, _p, _p, _p, _i64, _p, _p, _p, _i64, _i64, _p, _p, _p]),
+    "arx_unary_numeric": (_int, [_int, _int, _int, _span, _p, _p, _p]),
+    "arx_round_numeric": (_int, [_int, _int, _int, _span, _i64, _p, _p, _p, _p]),
+    "arx_round_status": (_int, [_int, _int, _int, _span, _i64, _p, _p, _p]),
     "arx_delta_decode_pages": (_int, [_p, _p, _p, _i64, _i64, _int, _p, _sz, _p, _p]),
     "arx_copy_segments": (_int, [_p, _i64, _u64, _p]),
     "arx_bitmap_copy_segments": (_int, [_p, _i64, _i64, _p]),

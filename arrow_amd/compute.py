@@ -129,6 +129,34 @@ class DayOfWeekOptions(FunctionOptions):
         self.week_start = int(week_start)
 
 
+# RoundMode of api_scalar.h, in the enum's order (= ARX_ROUND_*)
+_ROUND_MODES = ("down", "up", "towards_zero", "towards_infinity", "half_down", "half_up", "half_towards_zero",
+                "half_towards_infinity", "half_to_even", "half_to_odd")
+
+
+def _round_mode(round_mode) -> str:
+    if round_mode not in _ROUND_MODES:
+        raise ArrowInvalid(f'"{round_mode}" is not a valid round mode')
+    return round_mode
+
+
+class RoundOptions(FunctionOptions):
+    """api_scalar.h RoundOptions: ndigits (negative: to tens, hundreds, ...) and one of the ten round modes."""
+
+    def __init__(self, ndigits: int = 0, round_mode: str = "half_to_even"):
+        self.ndigits = int(ndigits)
+        self.round_mode = _round_mode(round_mode)
+
+
+class RoundToMultipleOptions(FunctionOptions):
+    """api_scalar.h RoundToMultipleOptions: multiple (a Python number or an arrow_amd.Scalar; cast to the column's type
+    by the function) and one of the ten round modes."""
+
+    def __init__(self, multiple=1.0, round_mode: str = "half_to_even"):
+        self.multiple = multiple
+        self.round_mode = _round_mode(round_mode)
+
+
 # --------------------------------------------------------------------------- scratch space
 _tls = threading.local()
 
@@ -1094,6 +1122,19 @@ def _build_registry() -> FunctionRegistry:
     for name in _TEMPORAL_COMPONENTS:
         f = Function(name, Function.SCALAR, 1, DayOfWeekOptions() if name == "day_of_week" else None)
         f.add_kernel(Kernel((_temporal_input(name),), _exec_temporal(name), int64))
+        reg.add_function(f)
+
+    # negate .. trunc, round and round_to_multiple of the numeric types (csrc/unary_arith.hip)
+    for name in _UNARY_OPS:
+        f = Function(name, Function.SCALAR, 1)
+        for t in numeric_types:
+            if _unary_input(name)(t):
+                f.add_kernel(Kernel((t,), _exec_unary_arith(name), int8 if name == "sign" and not _FLOATING(t) else t))
+        reg.add_function(f)
+    for name, default in (("round", RoundOptions()), ("round_to_multiple", RoundToMultipleOptions())):
+        f = Function(name, Function.SCALAR, 1, default)
+        for t in numeric_types:
+            f.add_kernel(Kernel((t,), _exec_round(name), t))
         reg.add_function(f)
 
     f = Function("hash_sum", Function.HASH_AGGREGATE, 2, ScalarAggregateOptions())
@@ -2240,7 +2281,7 @@ def _hash_mean_from_dense(st: "GroupedSumInt64State", values: Array) -> Array:
     g = st.num_groups
     mm = min_max(values)
     lo, hi = mm if mm else (0, 0)
-    bound = builtins.max(abs(int(lo)), abs(int(hi)))
+    bound = builtins.max(builtins.abs(int(lo)), builtins.abs(int(hi)))
     lib, stream = _lib_and_stream(st.device)
     bits = alloc(bitmap_nbytes(g), st.device, zero=True)
     counter = torch.zeros(8, dtype=torch.uint8, device=st.device)
@@ -2953,6 +2994,159 @@ def day_of_week(values: Array, *, count_from_zero: bool = True, week_start: int 
     """compute::DayOfWeek: (ISO weekday - week_start + 7) % 7, plus 1 unless count_from_zero; Monday = 0 at the defaults.
     week_start outside 1 .. 7 raises ArrowInvalid with the reference's text.  See year."""
     return call_function("day_of_week", [values], DayOfWeekOptions(count_from_zero, week_start))
+
+
+# --------------------------------------------------------------------------- one-operand arithmetic and rounding
+# Negate .. Sign (base_arithmetic_internal.h), Floor / Ceil / Trunc / Round / RoundToMultiple (scalar_round.cc):
+# csrc/unary_arith.hip.  name -> (ARX_UNARY_*, checked)
+_UNARY_OPS = {"negate": (0, False), "negate_checked": (0, True), "abs": (1, False), "abs_checked": (1, True), "sign": (2, False),
+              "floor": (3, False), "ceil": (4, False), "trunc": (5, False)}
+_ROUND_KINDS = {"round": 0, "round_to_multiple": 1}
+_NUM_NP_DTYPE = {"int8": np.int8, "uint8": np.uint8, "int16": np.int16, "uint16": np.uint16, "int32": np.int32, "uint32": np.uint32,
+                 "int64": np.int64, "uint64": np.uint64, "float": np.float32, "double": np.float64}
+_FLOATING = lambda t: t.name in ("float", "double")  # noqa: E731
+_SIGNED_OR_FLOATING = lambda t: t.name in _NUM_TYPE_ID and not t.name.startswith("u")  # noqa: E731
+
+
+def _unary_input(name: str):
+    """The reference's kernel lists: negate_checked has no unsigned kernels, floor / ceil / trunc only the two float ones
+    (its DispatchBest casts an integer column to double first; the mirror casts nothing implicitly)."""
+    return _SIGNED_OR_FLOATING if name == "negate_checked" else _FLOATING if name in ("floor", "ceil", "trunc") else _NUMERIC
+
+
+def _with_input_validity(values: Array, out_type: DataType, out) -> Array:
+    """The result of a one-operand kernel: `out` under the input's validity re-based to offset 0 (no bitmap when the input
+    has none); the input's null count where it is known, a count on first use otherwise."""
+    n = values.length
+    known = values._null_count          # (a pending device-side count stays pending: no read-back here)
+    if values.validity is None or not (callable(known) or known != 0):
+        return Array(out_type, n, [None, out], 0, 0)
+    if values.offset == 0:
+        valid = values.validity         # (shared, like the two-operand kernels do)
+    else:
+        lib, stream = _lib_and_stream(values.device)
+        valid = alloc(bitmap_nbytes(n), values.device)
+        check(lib.arx_bitmap_copy(values.validity.data_ptr(), values.offset, n, valid.data_ptr(), stream))
+    res = Array(out_type, n, [valid, out], kUnknownNullCount, 0)
+    if callable(known) or known == kUnknownNullCount:
+        nbytes = (n + 7) // 8
+        res.set_lazy_null_count(lambda: n - int(np.unpackbits(valid[:nbytes].cpu().numpy(), bitorder="little")[:n].sum()) if n else 0)
+    else:
+        res._null_count = int(known)
+    return res
+
+
+def _unary_span(values: Array):
+    known = values._null_count
+    nulls = values.validity is not None and (callable(known) or known != 0)
+    return _lib.ArxSpan(values.validity.data_ptr() if nulls else None, values.data.data_ptr(), values.offset, values.length,
+                        kUnknownNullCount if callable(known) else int(known))
+
+
+def _exec_unary_arith(name: str):
+    op, checked = _UNARY_OPS[name]
+
+    def run(args, options):
+        (values,) = args
+        if not isinstance(values, Array):
+            raise ArrowNotImplementedError(f"arrow_amd: {name} of a scalar on the device path")
+        t = values.type
+        integral = not _FLOATING(t)
+        out_type = int8 if name == "sign" and integral else t
+        can_fail = checked and integral and not t.name.startswith("u")
+        n = values.length
+        dev = values.device
+        lib, stream = _lib_and_stream(dev)
+        out = alloc(max(n * out_type.byte_width, 8), dev)
+        errors = torch.zeros(1, dtype=torch.int64, device=dev) if can_fail else None
+        vspan = _unary_span(values)
+        with tracing.span("arx_unary_numeric"):
+            check(lib.arx_unary_numeric(op, 1 if checked else 0, _NUM_TYPE_ID[t.name], C.byref(vspan), out.data_ptr(),
+                                        None if errors is None else errors.data_ptr(), stream))
+        if errors is not None and int(errors.cpu()[0]) != 0:
+            raise ArrowInvalid("overflow")   # NegateChecked / AbsoluteValueChecked::Call
+        return _with_input_validity(values, out_type, out)
+    return run
+
+
+def _round_multiple_as(multiple, t: DataType):
+    """RoundToMultipleOptions::multiple cast to the column's type, with the reference's cast errors (a Python int is an
+    int64 scalar there, a Python float a double)."""
+    if isinstance(multiple, Scalar):
+        multiple = multiple.value if multiple.is_valid else None
+    if multiple is None:
+        raise ArrowInvalid("Rounding multiple must be non-null and valid")
+    if not multiple > 0:      # (the reference looks at the sign before it casts: -2 for a uint32 column is this error)
+        raise ArrowInvalid("Rounding multiple must be positive")
+    dtype = _NUM_NP_DTYPE[t.name]
+    if _FLOATING(t):
+        with np.errstate(over="ignore"):
+            return np.array([multiple], dtype=np.float64).astype(dtype)
+    info = np.iinfo(dtype)
+    if isinstance(multiple, (float, np.floating)):
+        if multiple != multiple or multiple in (float("inf"), float("-inf")) or int(multiple) != multiple or not info.min <= int(multiple) <= info.max:
+            raise ArrowInvalid(f"Float value {float(multiple):f} was truncated converting to {t.name}")
+    elif not info.min <= int(multiple) <= info.max:
+        raise ArrowInvalid(f"Integer value {int(multiple)} not in range: {info.min} to {info.max}")
+    return np.array([int(multiple)], dtype=dtype)
+
+
+def _exec_round(name: str):
+    kind = _ROUND_KINDS[name]
+
+    def run(args, options):
+        (values,) = args
+        if not isinstance(values, Array):
+            raise ArrowNotImplementedError(f"arrow_amd: {name} of a scalar on the device path")
+        options = options or (RoundOptions() if kind == 0 else RoundToMultipleOptions())
+        t = values.type
+        mode = _ROUND_MODES.index(options.round_mode)
+        ndigits, multiple = (int(options.ndigits), None) if kind == 0 else (0, _round_multiple_as(options.multiple, t))
+        n = values.length
+        dev = values.device
+        lib, stream = _lib_and_stream(dev)
+        out = alloc(max(n * t.byte_width, 8), dev)
+        errors = torch.zeros(1, dtype=torch.int64, device=dev)
+        vspan = _unary_span(values)
+        call = (kind, mode, _NUM_TYPE_ID[t.name], C.byref(vspan), ndigits, None if multiple is None else multiple.ctypes.data)
+        with tracing.span("arx_round_numeric"):
+            check(lib.arx_round_numeric(*call, out.data_ptr(), errors.data_ptr(), stream))
+            check(lib.arx_round_status(*call, errors.data_ptr(), stream))
+        return _with_input_validity(values, t, out)
+    return run
+
+
+def _unary_wrapper(name: str, doc: str):
+    def f(values: Array) -> Array:
+        return call_function(name, [values])
+    f.__name__ = f.__qualname__ = name
+    f.__doc__ = (f"compute::{doc}: an Array on the device, null where `values` is null (no validity buffer when `values` has "
+                 "none; the null count is the input's).  See csrc/unary_arith.hip for the semantics.")
+    return f
+
+
+negate = _unary_wrapper("negate", "Negate (integers wrap: negate(uint8 1) == 255)")
+negate_checked = _unary_wrapper("negate_checked", "NegateChecked (the signed minimum in a valid slot raises ArrowInvalid 'overflow')")
+abs = _unary_wrapper("abs", "AbsoluteValue (abs(int8 -128) == -128)")  # noqa: A001
+abs_checked = _unary_wrapper("abs_checked", "AbsoluteValueChecked (the signed minimum in a valid slot raises ArrowInvalid 'overflow')")
+sign = _unary_wrapper("sign", "Sign (int8 for an integer column, the same float type for a float one)")
+floor = _unary_wrapper("floor", "Floor (float32 / float64)")
+ceil = _unary_wrapper("ceil", "Ceil (float32 / float64)")
+trunc = _unary_wrapper("trunc", "Trunc (float32 / float64)")
+
+
+def round(values: Array, ndigits: int = 0, round_mode: str = "half_to_even") -> Array:  # noqa: A001
+    """compute::Round (scalar_round.cc): the reference's IEEE operations one by one for floats, its `%` rule for integers
+    (ndigits >= 0 returns an integer column as it is).  A row that overflows raises ArrowInvalid with the reference's
+    text, naming the last failing row; an integer multiple above half the type's maximum in a half_* mode raises
+    ArrowNotImplementedError."""
+    return call_function("round", [values], RoundOptions(ndigits, round_mode))
+
+
+def round_to_multiple(values: Array, multiple=1.0, round_mode: str = "half_to_even") -> Array:
+    """compute::RoundToMultiple: `multiple` (a Python number or an arrow_amd.Scalar) is cast to the column's type with the
+    reference's cast errors; it must be valid and positive.  See round."""
+    return call_function("round_to_multiple", [values], RoundToMultipleOptions(multiple, round_mode))
 
 
 # --------------------------------------------------------------------------- hash join

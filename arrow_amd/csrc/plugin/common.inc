@@ -94,7 +94,8 @@ enum Fn { kFnFilter = 0, kFnTake, kFnGreater, kFnSort, kFnCast, kFnHashSum, kFnA
           kFnDayOfYear, kFnIsoYear, kFnIsoWeek, kFnHour, kFnMinute, kFnSecond, kFnMillisecond, kFnMicrosecond, kFnNanosecond,
           kFnBinaryLength, kFnUtf8Length, kFnBinarySlice, kFnUtf8SliceCodeunits, kFnAsciiTrimWhitespace, kFnAsciiLtrimWhitespace,
           kFnAsciiRtrimWhitespace, kFnUtf8TrimWhitespace, kFnUtf8LtrimWhitespace, kFnUtf8RtrimWhitespace, kFnAsciiTrim, kFnAsciiLtrim,
-          kFnAsciiRtrim, kFnUtf8Trim, kFnUtf8Ltrim, kFnUtf8Rtrim, kFnCompareString, kFnReplaceSubstring, kNumFn };
+          kFnAsciiRtrim, kFnUtf8Trim, kFnUtf8Ltrim, kFnUtf8Rtrim, kFnCompareString, kFnReplaceSubstring, kFnUnaryArith, kFnRound,
+          kNumFn };
 const char* const kFnNames[kNumFn] = {"array_filter", "array_take", "greater", "array_sort_indices",
                                       "cast", "hash_sum", "add", "boolean", "compare", "parquet", "reduce", "order_by",
                                       "take_columns", "unique", "coalesce", "is_in", "index_in", "hashjoin",
@@ -104,7 +105,7 @@ const char* const kFnNames[kNumFn] = {"array_filter", "array_take", "greater", "
                                       "utf8_slice_codeunits", "ascii_trim_whitespace", "ascii_ltrim_whitespace",
                                       "ascii_rtrim_whitespace", "utf8_trim_whitespace", "utf8_ltrim_whitespace",
                                       "utf8_rtrim_whitespace", "ascii_trim", "ascii_ltrim", "ascii_rtrim", "utf8_trim", "utf8_ltrim",
-                                      "utf8_rtrim", "compare_string", "replace_substring"};
+                                      "utf8_rtrim", "compare_string", "replace_substring", "unary_arith", "round"};
 std::atomic<int64_t> g_fn_gpu[kNumFn];
 std::atomic<int64_t> g_fn_stock[kNumFn];
 void CountGpu(Fn f) {

@@ -335,6 +335,51 @@ int arx_divide_numeric(int checked, int num_type, const void* left, const void* 
                        int64_t left_offset, const void* right, const void* right_scalar, const void* right_validity,
                        int64_t right_offset, int64_t length, void* out, uint64_t* errors, void* stream);
 
+/* The one-operand half of the family (csrc/unary_arith.hip): negate, abs (+ _checked), sign, floor, ceil, trunc — Negate,
+ * NegateChecked, AbsoluteValue, AbsoluteValueChecked, Sign (base_arithmetic_internal.h), Floor / Ceil / Trunc
+ * (scalar_round.cc).  values: a span of num_type whose offset is honoured; out: values->length results from row 0 on, of
+ * num_type — but int8 for sign of an integer type.  Every row is computed from the bytes it holds, null or not; the
+ * result's validity is the input's and the caller's to copy (arx_bitmap_copy).
+ *   negate   integers wrap in the type's width (negate(uint8 1) == 255), floats flip the sign bit;
+ *   abs      abs(int8 -128) == -128, unsigned types come back as they are, floats clear the sign bit;
+ *   sign     -1 / 0 / 1; of a float the same float type, sign(+-0.0) == +0.0, a NaN stays the NaN it is;
+ *   floor, ceil, trunc   float32 / float64 only.
+ * checked != 0 (negate, abs): the signed minimum fails with "overflow" where the row is VALID (values->validity at
+ * values->offset; NULL or null_count == 0: all valid): *errors (one device uint64 zeroed by the caller) holds 1 + the
+ * LAST failing row once the stream has drained.  errors may be NULL when no row can fail (unchecked, floats, abs_checked
+ * of an unsigned type).  ARX_INVALID: a code out of range, checked with an op that has no checked form, negate_checked of
+ * an unsigned type, floor / ceil / trunc of an integer type (the reference has no such kernels).  Asynchronous. */
+enum { ARX_UNARY_NEGATE = 0, ARX_UNARY_ABS = 1, ARX_UNARY_SIGN = 2, ARX_UNARY_FLOOR = 3, ARX_UNARY_CEIL = 4, ARX_UNARY_TRUNC = 5 };
+int arx_unary_numeric(int op, int checked, int num_type, const ArxSpan* values, void* out, uint64_t* errors, void* stream);
+
+/* round (kind ARX_ROUND_DIGITS: RoundOptions::ndigits) and round_to_multiple (ARX_ROUND_MULTIPLE: *multiple, a host
+ * pointer to one value of num_type — the caller has cast RoundToMultipleOptions::multiple to the column's type) in
+ * the ten RoundModes of compute/api_scalar.h, in that enum's order; Round / RoundToMultiple of scalar_round.cc, operation
+ * by operation.  values / out as for arx_unary_numeric; out has num_type.
+ *   floats     p = pow10(|ndigits|) — a table of float literals up to 10^15, also for double, then `*= 10` per step —
+ *              or the multiple; rv = x * p (ndigits > 0) or x / p; a value that is not finite or whose rv is whole comes
+ *              back with its bits; otherwise the mode's rule on rv and back through / p or * p.  A result that is not
+ *              finite fails the row: "overflow occurred during rounding".
+ *   integers   round with ndigits >= 0 returns the input; otherwise m = 10^-ndigits ("Rounding to N digits is out of range
+ *              for type T" when that does not fit, ARX_INVALID) or the multiple; rem = v % m, the mode's rule, and a result
+ *              outside the type fails the row: "Rounding V up|down to multiple[s] of M would overflow".
+ * A multiple that is not positive (floats: or NaN): ARX_INVALID "Rounding multiple must be positive".  An integer m above
+ * half the type's maximum in a half_* mode: ARX_NOT_IMPLEMENTED (the reference's own arithmetic wraps there).
+ * errors: one device uint64 zeroed by the caller; once the stream has drained it holds 1 + the LAST failing VALID row.
+ * arx_round_numeric is asynchronous.  arx_round_status, given the same arguments after it, waits for the stream, reads
+ * the word — and, for an integer type, the one value it names — and returns ARX_OK or ARX_INVALID with the reference's
+ * text in arx_last_error (8-bit values are printed as numbers). */
+enum { ARX_ROUND_DIGITS = 0, ARX_ROUND_MULTIPLE = 1 };
+enum {
+  ARX_ROUND_DOWN = 0, ARX_ROUND_UP = 1, ARX_ROUND_TOWARDS_ZERO = 2, ARX_ROUND_TOWARDS_INFINITY = 3, ARX_ROUND_HALF_DOWN = 4,
+  ARX_ROUND_HALF_UP = 5, ARX_ROUND_HALF_TOWARDS_ZERO = 6, ARX_ROUND_HALF_TOWARDS_INFINITY = 7, ARX_ROUND_HALF_TO_EVEN = 8,
+  ARX_ROUND_HALF_TO_ODD = 9
+};
+int arx_round_numeric(int kind, int mode, int num_type, const ArxSpan* values, int64_t ndigits, const void* multiple, void* out,
+                      uint64_t* errors, void* stream);
+int arx_round_status(int kind, int mode, int num_type, const ArxSpan* values, int64_t ndigits, const void* multiple,
+                     const uint64_t* errors, void* stream);
+
 /* ---------------------------------------------------------------------------
  * Validity plumbing — what ScalarExecutor's null propagation does on the host
  * (PropagateNullsSpans, cpp/src/arrow/compute/exec.cc:1222-1281; BitmapAnd /
