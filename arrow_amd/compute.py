@@ -2417,9 +2417,7 @@ def _set_lookup(values: Array, value_set, skip_nulls: bool, index: bool):
     if not index:
         return Array(bool_, n, [None, words], 0, 0)
     out = Array(int32, n, [words, out_index], kUnknownNullCount, 0)
-    nbytes = (n + 7) // 8
-    out.set_lazy_null_count(
-        lambda: n - int(np.unpackbits(words[:nbytes].cpu().numpy(), bitorder="little")[:n].sum()) if n else 0)
+    out.set_lazy_null_count(_lazy_null_count(words, n))
     return out
 
 
@@ -2434,6 +2432,87 @@ def index_in(values: Array, value_set, *, skip_nulls: bool = False) -> Array:
     """compute::IndexIn (scalar_set_lookup.cc): int32, the index of the row's value's first occurrence in `value_set`
     (chunks counted one after the other), null where the value is absent.  The result stays on the device."""
     return _set_lookup(values, value_set, skip_nulls, True)
+
+
+# --------------------------------------------------------------------------- what the scalar kernels below share
+def _lazy_null_count(bitmap, n: int):
+    """For set_lazy_null_count: the zeros among the first n bits of the device bitmap, read back on first use."""
+    nbytes = (n + 7) // 8
+    return lambda: n - int(np.unpackbits(bitmap[:nbytes].cpu().numpy(), bitorder="little")[:n].sum()) if n else 0
+
+
+def _require_array(name: str, x) -> None:
+    if not isinstance(x, Array):
+        raise ArrowNotImplementedError(f"arrow_amd: {name} of a scalar on the device path")
+
+
+def _input_has_nulls(values: Array) -> bool:
+    """Whether a one-operand kernel has to look at its input's bitmap: there is one, and the null count is not known to
+    be 0 (a pending device-side count stays pending: no read-back here)."""
+    known = values._null_count
+    return values.validity is not None and (callable(known) or known != 0)
+
+
+def _unary_span(values: Array):
+    """The ArxSpan of a one-operand fixed-width kernel's input: no bitmap unless _input_has_nulls."""
+    known = values._null_count
+    return _lib.ArxSpan(values.validity.data_ptr() if _input_has_nulls(values) else None, values.data.data_ptr(), values.offset,
+                        values.length, kUnknownNullCount if callable(known) else int(known))
+
+
+def _carry_null_count(res: Array, values: Array) -> Array:
+    """`res`, whose validity is that of `values` at offset 0: the input's null count where it is known, a count on first
+    use otherwise."""
+    known = values._null_count
+    if callable(known) or known == kUnknownNullCount:
+        res.set_lazy_null_count(_lazy_null_count(res.validity, res.length))
+    else:
+        res._null_count = int(known)
+    return res
+
+
+def _under_input_validity(values: Array, out_type: DataType, *out) -> Array:
+    """The result of a one-operand kernel: the buffers `out` under the input's validity at offset 0.  No bitmap unless
+    _input_has_nulls; the input's own bitmap, shared like the two-operand kernels do, when it is at offset 0 already, a
+    re-based copy otherwise."""
+    n = values.length
+    if not _input_has_nulls(values):
+        return Array(out_type, n, [None, *out], 0, 0)
+    valid = values.validity
+    if values.offset != 0:
+        lib, stream = _lib_and_stream(values.device)
+        valid = alloc(bitmap_nbytes(n), values.device)
+        check(lib.arx_bitmap_copy(values.validity.data_ptr(), values.offset, n, valid.data_ptr(), stream))
+    return _carry_null_count(Array(out_type, n, [valid, *out], kUnknownNullCount, 0), values)
+
+
+def _literal_operand(name: str, what: str, x) -> bytes:
+    """A literal operand as bytes (str: UTF-8 encoded); `what` opens the TypeError, as in "pattern must be"."""
+    if isinstance(x, str):
+        return x.encode("utf-8")
+    if isinstance(x, (bytes, bytearray, memoryview)):
+        return bytes(x)
+    raise TypeError(f"{name}: {what} str or bytes, not {type(x).__name__}")
+
+
+def _device_literal(dev, *parts: bytes):
+    """The literal operands of a call back to back in one device tensor of at least one byte.  The caller drops it on
+    return while its kernels may still be queued: torch's caching allocator hands a freed block out again only to work
+    queued behind this call on the same stream."""
+    raw = b"".join(parts)
+    out = alloc(max(len(raw), 1), dev)
+    if raw:
+        out[:len(raw)].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+    return out
+
+
+def _values_wrapper(name: str, doc: str, what: str):
+    """The public function `name(values)` of a kernel that takes no options; its docstring is doc.format(what)."""
+    def f(values: Array) -> Array:
+        return call_function(name, [values])
+    f.__name__ = f.__qualname__ = name
+    f.__doc__ = doc.format(what)
+    return f
 
 
 # --------------------------------------------------------------------------- substring predicates
@@ -2456,29 +2535,18 @@ def _call_match_substring(name: str, values, pattern, ignore_case: bool) -> Arra
 
 
 def _match_substring(name: str, values: Array, pattern, ignore_case: bool) -> Array:
-    if isinstance(pattern, str):
-        pattern = pattern.encode("utf-8")
-    elif not isinstance(pattern, (bytes, bytearray, memoryview)):
-        raise TypeError(f"{name}: pattern must be str or bytes, not {type(pattern).__name__}")
-    pattern = bytes(pattern)
+    pattern = _literal_operand(name, "pattern must be", pattern)
     if ignore_case:
         raise ArrowNotImplementedError(f"arrow_amd: {name} with ignore_case=True on device-resident arrays")
     dev = values.device
     lib, stream = _lib_and_stream(dev)
     n = values.length
     words = alloc(max(1, (n + 63) // 64) * 8, dev)
-    m = len(pattern)
-    dpat = alloc(max(m, 1), dev)
-    if m:
-        dpat[:m].copy_(torch.frombuffer(bytearray(pattern), dtype=torch.uint8))
+    dpat = _device_literal(dev, pattern)
     vspan = values.binary_span()
-    hint = int(values.buffers[2].numel()) if values.buffers[2] is not None else -1
-    check(lib.arx_match_substring(C.byref(vspan), 4, _MATCH_OPS[name], dpat.data_ptr(), m, hint, int(MATCH_SUBSTRING_PATH),
-                                  words.data_ptr(), stream))
-    # (dpat is dropped on return while the kernel may still be queued: torch's caching allocator hands a freed block out
-    # again only to work queued behind this call on the same stream)
-    valid, count = _input_validity(values, lib, stream)
-    return _with_null_count(Array(bool_, n, [valid, words], kUnknownNullCount, 0), count)
+    check(lib.arx_match_substring(C.byref(vspan), 4, _MATCH_OPS[name], dpat.data_ptr(), len(pattern), _data_bytes_hint(values),
+                                  int(MATCH_SUBSTRING_PATH), words.data_ptr(), stream))
+    return _under_input_validity(values, bool_, words)
 
 
 def match_substring(values: Array, pattern, *, ignore_case: bool = False) -> Array:
@@ -2506,15 +2574,6 @@ def ends_with(values: Array, pattern, *, ignore_case: bool = False) -> Array:
 STRING_COMPARE_PATH = 0
 
 
-def _literal_bytes(name: str, x: Scalar) -> bytes:
-    v = x.value
-    if isinstance(v, str):
-        return v.encode("utf-8")
-    if isinstance(v, (bytes, bytearray, memoryview)):
-        return bytes(v)
-    raise TypeError(f"{name}: a {x.type.name} scalar must hold str or bytes, not {type(v).__name__}")
-
-
 def _exec_compare_binary(op_name):
     code = _CMP_CODE[op_name]
 
@@ -2534,23 +2593,18 @@ def _exec_compare_binary(op_name):
             dlit, m = None, 0
             for a in args:
                 if isinstance(a, Scalar):
-                    literal = _literal_bytes(op_name, a)
-                    m = len(literal)
-                    dlit = alloc(max(m, 1), dev)
-                    if m:
-                        dlit[:m].copy_(torch.frombuffer(bytearray(literal), dtype=torch.uint8))
+                    literal = _literal_operand(op_name, f"a {a.type.name} scalar must hold", a.value)
+                    dlit, m = _device_literal(dev, literal), len(literal)
             spans = [a.binary_span() if isinstance(a, Array) else None for a in args]
             hint = builtins.sum(_data_bytes_hint(a) for a in arrays)
             with tracing.span("arx_compare_binary"):
                 check(lib.arx_compare_binary(code, *[None if s is None else C.byref(s) for s in spans], 4,
                                              None if dlit is None else dlit.data_ptr(), m, builtins.max(hint, -1),
                                              int(STRING_COMPARE_PATH), words.data_ptr(), stream))
-            # (dlit is dropped on return while the kernel may still be queued: see _match_substring)
         validity, nc = _propagate_validity([left, right], n, dev)
         out = Array(bool_, n, [validity, words], nc, 0)
         if nc == kUnknownNullCount:
-            nbytes = (n + 7) // 8
-            out.set_lazy_null_count(lambda: n - int(np.unpackbits(validity[:nbytes].cpu().numpy(), bitorder="little")[:n].sum()))
+            out.set_lazy_null_count(_lazy_null_count(validity, n))
         return out
     return run
 
@@ -2569,28 +2623,6 @@ _BINARY_ONLY = lambda t: t.name == "binary"  # noqa: E731
 _UTF8_ONLY = lambda t: t.name == "string"  # noqa: E731
 
 
-def _input_validity(values: Array, lib, stream):
-    """The input's validity at offset 0 for a result of the same rows: (buffer | None, null count | a lazy count)."""
-    n = values.length
-    if values.validity is None:
-        return None, 0
-    valid = alloc(bitmap_nbytes(n), values.device)
-    check(lib.arx_bitmap_copy(values.validity.data_ptr(), values.offset, n, valid.data_ptr(), stream))
-    known = values._null_count
-    if not callable(known) and known != kUnknownNullCount:
-        return valid, int(known)
-    nbytes = (n + 7) // 8
-    return valid, (lambda: n - int(np.unpackbits(valid[:nbytes].cpu().numpy(), bitorder="little")[:n].sum()) if n else 0)
-
-
-def _with_null_count(out: Array, count) -> Array:
-    if callable(count):
-        out.set_lazy_null_count(count)
-    else:
-        out._null_count = count
-    return out
-
-
 def _data_bytes_hint(values: Array) -> int:
     return int(values.buffers[2].numel()) if values.buffers[2] is not None else -1
 
@@ -2598,25 +2630,21 @@ def _data_bytes_hint(values: Array) -> int:
 def _exec_string_length(name: str):
     def run(args, options):
         (values,) = args
-        if not isinstance(values, Array):
-            raise ArrowNotImplementedError(f"arrow_amd: {name} of a scalar on the device path")
+        _require_array(name, values)
         lib, stream = _lib_and_stream(values.device)
-        n = values.length
-        out = alloc(max(n, 1) * 4, values.device)
+        out = alloc(max(values.length, 1) * 4, values.device)
         vspan = values.binary_span()
         with tracing.span("arx_string_length"):
             check(lib.arx_string_length(C.byref(vspan), 4, _STRING_UNIT[name], _data_bytes_hint(values), int(STRING_SLICE_PATH),
                                         out.data_ptr(), stream))
-        valid, count = _input_validity(values, lib, stream)
-        return _with_null_count(Array(int32, n, [valid, out], kUnknownNullCount, 0), count)
+        return _under_input_validity(values, int32, out)
     return run
 
 
 def _exec_string_slice(name: str):
     def run(args, options):
         (values,) = args
-        if not isinstance(values, Array):
-            raise ArrowNotImplementedError(f"arrow_amd: {name} of a scalar on the device path")
+        _require_array(name, values)
         options = options or SliceOptions(0)
         if options.step == 0:
             raise ArrowInvalid("Slice step cannot be zero")
@@ -2653,8 +2681,7 @@ def _sub_range_result(values: Array, span_name: str, offsets_call, data_name: st
     out_data = alloc(total.value, dev)
     with tracing.span(data_name):
         check(data_call(lib, C.byref(vspan), ws.data_ptr(), ws.numel(), out_offsets.data_ptr(), total.value, out_data.data_ptr(), stream))
-    valid, count = _input_validity(values, lib, stream)
-    return _with_null_count(Array(values.type, n, [valid, out_offsets, out_data], kUnknownNullCount, 0), count)
+    return _under_input_validity(values, values.type, out_offsets, out_data)
 
 
 def _call_string_function(name: str, values, options, *reference_args) -> Array:
@@ -2703,34 +2730,22 @@ def utf8_slice_codeunits(values: Array, start: int, stop=None, step: int = 1) ->
 # compute::ReplaceSubstring with a literal pattern (PlainSubstringReplacer, scalar_string_ascii.cc):
 # csrc/string_replace.hip.  The rows are assembled, not sub-ranges: arx_replace_substring_offsets counts every row's
 # matches, arx_replace_substring_data writes "gap, replacement, gap, ...".
-def _literal_operand(name: str, what: str, x) -> bytes:
-    if isinstance(x, str):
-        return x.encode("utf-8")
-    if isinstance(x, (bytes, bytearray, memoryview)):
-        return bytes(x)
-    raise TypeError(f"{name}: {what} must be str or bytes, not {type(x).__name__}")
-
-
 def _exec_replace_substring(args, options):
     name = "replace_substring"
     (values,) = args
-    if not isinstance(values, Array):
-        raise ArrowNotImplementedError(f"arrow_amd: {name} of a scalar on the device path")
+    _require_array(name, values)
     if options is None:
         raise ArrowInvalid(f"Function '{name}' cannot be called without options")
-    pattern = _literal_operand(name, "pattern", options.pattern)
-    replacement = _literal_operand(name, "replacement", options.replacement)
+    pattern = _literal_operand(name, "pattern must be", options.pattern)
+    replacement = _literal_operand(name, "replacement must be", options.replacement)
     if not pattern:
         raise ArrowNotImplementedError(f"arrow_amd: {name} with an empty pattern on device-resident arrays: there is no device "
                                        "kernel (the reference does not terminate on it with unlimited replacements)")
     cap = -1 if options.max_replacements is None or options.max_replacements < 0 else min(int(options.max_replacements), 2**63 - 1)
-    dev = values.device
     m, r = len(pattern), len(replacement)
-    literals = alloc(m + max(r, 1), dev)                          # copied to the device once per call: pattern, replacement
-    literals[:m + r].copy_(torch.frombuffer(bytearray(pattern + replacement), dtype=torch.uint8))
+    literals = _device_literal(values.device, pattern, replacement)   # copied to the device once per call
     dpat, drep = literals.data_ptr(), literals.data_ptr() + m
     path = int(STRING_REPLACE_PATH)
-    # (literals is dropped on return while the kernels may still be queued: see _match_substring)
     return _sub_range_result(
         values, "arx_replace_substring_offsets",
         lambda lib, vspan, *rest: lib.arx_replace_substring_offsets(vspan, 4, dpat, m, r, cap, _data_bytes_hint(values), path, *rest),
@@ -2782,8 +2797,7 @@ def _exec_string_trim(name: str):
 
     def run(args, options):
         (values,) = args
-        if not isinstance(values, Array):
-            raise ArrowNotImplementedError(f"arrow_amd: {name} of a scalar on the device path")
+        _require_array(name, values)
         members, count = None, 0
         if kind >= 2:
             if options is None:
@@ -2872,9 +2886,7 @@ def _exec_if_else(args, options):
     if all(null_scalars):
         res._null_count = n
     else:
-        nbytes = (n + 7) // 8
-        res.set_lazy_null_count(
-            lambda: n - int(np.unpackbits(valid[:nbytes].cpu().numpy(), bitorder="little")[:n].sum()) if n else 0)
+        res.set_lazy_null_count(_lazy_null_count(valid, n))
     return res
 
 
@@ -2931,8 +2943,7 @@ def _exec_temporal(name: str):
 
     def run(args, options):
         (values,) = args
-        if not isinstance(values, Array):
-            raise ArrowNotImplementedError(f"arrow_amd: {name} of a scalar on the device path")
+        _require_array(name, values)
         if _without_zone(values.type.name) != values.type.name:
             raise ArrowNotImplementedError(f"arrow_amd: {name} of {values.type.name} on device-resident arrays: time zones need "
                                            "the tz database, which has no device kernel")
@@ -2943,51 +2954,35 @@ def _exec_temporal(name: str):
         n = values.length
         dev = values.device
         lib, stream = _lib_and_stream(dev)
-        known = values._null_count          # (a pending device-side count stays pending: no read-back here)
-        nulls = values.validity is not None and (callable(known) or known != 0)
-        vspan = _lib.ArxSpan(values.validity.data_ptr() if nulls else None, values.data.data_ptr(), values.offset, n,
-                             kUnknownNullCount if callable(known) else int(known))
+        nulls = _input_has_nulls(values)
+        vspan = _unary_span(values)
         out = alloc(n * 8, dev)
-        valid = alloc(bitmap_nbytes(n), dev) if nulls else None
+        valid = alloc(bitmap_nbytes(n), dev) if nulls else None   # (the kernel writes the validity at offset 0 itself)
         with tracing.span("arx_temporal_component"):
             check(lib.arx_temporal_component(component, _temporal_input_code(values.type), C.byref(vspan), n, week_start,
                                              1 if count_from_zero else 0, out.data_ptr(), _ptr_or_none(valid), stream))
         if not nulls:
             return Array(int64, n, [None, out], 0, 0)
-        res = Array(int64, n, [valid, out], kUnknownNullCount, 0)
-        if callable(known) or known == kUnknownNullCount:
-            nbytes = (n + 7) // 8
-            res.set_lazy_null_count(
-                lambda: n - int(np.unpackbits(valid[:nbytes].cpu().numpy(), bitorder="little")[:n].sum()) if n else 0)
-        else:
-            res._null_count = int(known)
-        return res
+        return _carry_null_count(Array(int64, n, [valid, out], kUnknownNullCount, 0), values)
     return run
 
 
-def _temporal_wrapper(name: str, doc: str):
-    def f(values: Array) -> Array:
-        return call_function(name, [values])
-    f.__name__ = f.__qualname__ = name
-    f.__doc__ = (f"compute::{doc} (scalar_temporal_unary.cc): an int64 Array on the device, null where `values` is null (no "
-                 "validity buffer when `values` has none; the null count is the input's).  Proleptic Gregorian calendar, floor "
-                 "division before the epoch, no time zones (a zoned timestamp raises ArrowNotImplementedError).")
-    return f
-
-
-year = _temporal_wrapper("year", "Year")
-quarter = _temporal_wrapper("quarter", "Quarter")
-month = _temporal_wrapper("month", "Month")
-day = _temporal_wrapper("day", "Day")
-day_of_year = _temporal_wrapper("day_of_year", "DayOfYear")
-iso_year = _temporal_wrapper("iso_year", "ISOYear")
-iso_week = _temporal_wrapper("iso_week", "ISOWeek")
-hour = _temporal_wrapper("hour", "Hour")
-minute = _temporal_wrapper("minute", "Minute")
-second = _temporal_wrapper("second", "Second")
-millisecond = _temporal_wrapper("millisecond", "Millisecond")
-microsecond = _temporal_wrapper("microsecond", "Microsecond")
-nanosecond = _temporal_wrapper("nanosecond", "Nanosecond")
+_TEMPORAL_DOC = ("compute::{} (scalar_temporal_unary.cc): an int64 Array on the device, null where `values` is null (no validity "
+                 "buffer when `values` has none; the null count is the input's).  Proleptic Gregorian calendar, floor division "
+                 "before the epoch, no time zones (a zoned timestamp raises ArrowNotImplementedError).")
+year = _values_wrapper("year", _TEMPORAL_DOC, "Year")
+quarter = _values_wrapper("quarter", _TEMPORAL_DOC, "Quarter")
+month = _values_wrapper("month", _TEMPORAL_DOC, "Month")
+day = _values_wrapper("day", _TEMPORAL_DOC, "Day")
+day_of_year = _values_wrapper("day_of_year", _TEMPORAL_DOC, "DayOfYear")
+iso_year = _values_wrapper("iso_year", _TEMPORAL_DOC, "ISOYear")
+iso_week = _values_wrapper("iso_week", _TEMPORAL_DOC, "ISOWeek")
+hour = _values_wrapper("hour", _TEMPORAL_DOC, "Hour")
+minute = _values_wrapper("minute", _TEMPORAL_DOC, "Minute")
+second = _values_wrapper("second", _TEMPORAL_DOC, "Second")
+millisecond = _values_wrapper("millisecond", _TEMPORAL_DOC, "Millisecond")
+microsecond = _values_wrapper("microsecond", _TEMPORAL_DOC, "Microsecond")
+nanosecond = _values_wrapper("nanosecond", _TEMPORAL_DOC, "Nanosecond")
 
 
 def day_of_week(values: Array, *, count_from_zero: bool = True, week_start: int = 1) -> Array:
@@ -3014,42 +3009,12 @@ def _unary_input(name: str):
     return _SIGNED_OR_FLOATING if name == "negate_checked" else _FLOATING if name in ("floor", "ceil", "trunc") else _NUMERIC
 
 
-def _with_input_validity(values: Array, out_type: DataType, out) -> Array:
-    """The result of a one-operand kernel: `out` under the input's validity re-based to offset 0 (no bitmap when the input
-    has none); the input's null count where it is known, a count on first use otherwise."""
-    n = values.length
-    known = values._null_count          # (a pending device-side count stays pending: no read-back here)
-    if values.validity is None or not (callable(known) or known != 0):
-        return Array(out_type, n, [None, out], 0, 0)
-    if values.offset == 0:
-        valid = values.validity         # (shared, like the two-operand kernels do)
-    else:
-        lib, stream = _lib_and_stream(values.device)
-        valid = alloc(bitmap_nbytes(n), values.device)
-        check(lib.arx_bitmap_copy(values.validity.data_ptr(), values.offset, n, valid.data_ptr(), stream))
-    res = Array(out_type, n, [valid, out], kUnknownNullCount, 0)
-    if callable(known) or known == kUnknownNullCount:
-        nbytes = (n + 7) // 8
-        res.set_lazy_null_count(lambda: n - int(np.unpackbits(valid[:nbytes].cpu().numpy(), bitorder="little")[:n].sum()) if n else 0)
-    else:
-        res._null_count = int(known)
-    return res
-
-
-def _unary_span(values: Array):
-    known = values._null_count
-    nulls = values.validity is not None and (callable(known) or known != 0)
-    return _lib.ArxSpan(values.validity.data_ptr() if nulls else None, values.data.data_ptr(), values.offset, values.length,
-                        kUnknownNullCount if callable(known) else int(known))
-
-
 def _exec_unary_arith(name: str):
     op, checked = _UNARY_OPS[name]
 
     def run(args, options):
         (values,) = args
-        if not isinstance(values, Array):
-            raise ArrowNotImplementedError(f"arrow_amd: {name} of a scalar on the device path")
+        _require_array(name, values)
         t = values.type
         integral = not _FLOATING(t)
         out_type = int8 if name == "sign" and integral else t
@@ -3065,7 +3030,7 @@ def _exec_unary_arith(name: str):
                                         None if errors is None else errors.data_ptr(), stream))
         if errors is not None and int(errors.cpu()[0]) != 0:
             raise ArrowInvalid("overflow")   # NegateChecked / AbsoluteValueChecked::Call
-        return _with_input_validity(values, out_type, out)
+        return _under_input_validity(values, out_type, out)
     return run
 
 
@@ -3096,8 +3061,7 @@ def _exec_round(name: str):
 
     def run(args, options):
         (values,) = args
-        if not isinstance(values, Array):
-            raise ArrowNotImplementedError(f"arrow_amd: {name} of a scalar on the device path")
+        _require_array(name, values)
         options = options or (RoundOptions() if kind == 0 else RoundToMultipleOptions())
         t = values.type
         mode = _ROUND_MODES.index(options.round_mode)
@@ -3112,27 +3076,20 @@ def _exec_round(name: str):
         with tracing.span("arx_round_numeric"):
             check(lib.arx_round_numeric(*call, out.data_ptr(), errors.data_ptr(), stream))
             check(lib.arx_round_status(*call, errors.data_ptr(), stream))
-        return _with_input_validity(values, t, out)
+        return _under_input_validity(values, t, out)
     return run
 
 
-def _unary_wrapper(name: str, doc: str):
-    def f(values: Array) -> Array:
-        return call_function(name, [values])
-    f.__name__ = f.__qualname__ = name
-    f.__doc__ = (f"compute::{doc}: an Array on the device, null where `values` is null (no validity buffer when `values` has "
-                 "none; the null count is the input's).  See csrc/unary_arith.hip for the semantics.")
-    return f
-
-
-negate = _unary_wrapper("negate", "Negate (integers wrap: negate(uint8 1) == 255)")
-negate_checked = _unary_wrapper("negate_checked", "NegateChecked (the signed minimum in a valid slot raises ArrowInvalid 'overflow')")
-abs = _unary_wrapper("abs", "AbsoluteValue (abs(int8 -128) == -128)")  # noqa: A001
-abs_checked = _unary_wrapper("abs_checked", "AbsoluteValueChecked (the signed minimum in a valid slot raises ArrowInvalid 'overflow')")
-sign = _unary_wrapper("sign", "Sign (int8 for an integer column, the same float type for a float one)")
-floor = _unary_wrapper("floor", "Floor (float32 / float64)")
-ceil = _unary_wrapper("ceil", "Ceil (float32 / float64)")
-trunc = _unary_wrapper("trunc", "Trunc (float32 / float64)")
+_UNARY_DOC = ("compute::{}: an Array on the device, null where `values` is null (no validity buffer when `values` has none; the "
+              "null count is the input's).  See csrc/unary_arith.hip for the semantics.")
+negate = _values_wrapper("negate", _UNARY_DOC, "Negate (integers wrap: negate(uint8 1) == 255)")
+negate_checked = _values_wrapper("negate_checked", _UNARY_DOC, "NegateChecked (the signed minimum in a valid slot raises ArrowInvalid 'overflow')")
+abs = _values_wrapper("abs", _UNARY_DOC, "AbsoluteValue (abs(int8 -128) == -128)")  # noqa: A001
+abs_checked = _values_wrapper("abs_checked", _UNARY_DOC, "AbsoluteValueChecked (the signed minimum in a valid slot raises ArrowInvalid 'overflow')")
+sign = _values_wrapper("sign", _UNARY_DOC, "Sign (int8 for an integer column, the same float type for a float one)")
+floor = _values_wrapper("floor", _UNARY_DOC, "Floor (float32 / float64)")
+ceil = _values_wrapper("ceil", _UNARY_DOC, "Ceil (float32 / float64)")
+trunc = _values_wrapper("trunc", _UNARY_DOC, "Trunc (float32 / float64)")
 
 
 def round(values: Array, ndigits: int = 0, round_mode: str = "half_to_even") -> Array:  # noqa: A001

@@ -269,10 +269,10 @@ int arx_match_substring(const ArxBinarySpan* values, int offset_width, int op, c
     bytes = path == ARX_MATCH_PATH_BYTES ||
             (path == ARX_MATCH_PATH_AUTO && data_bytes_hint >= 0 && data_bytes_hint / values->length >= kBytesPathMeanRow);
   }
-  hipStream_t st = as_stream(stream);
   const auto* pat = static_cast<const uint8_t*>(pattern);
-  return offset_width == 4 ? match_launch<int32_t>(values, op, pat, pattern_length, data_bytes_hint, bytes, out_bits, st)
-                           : match_launch<int64_t>(values, op, pat, pattern_length, data_bytes_hint, bytes, out_bits, st);
+  return with_offset_type(offset_width, [&](auto o) {
+    return match_launch<decltype(o)>(values, op, pat, pattern_length, data_bytes_hint, bytes, out_bits, as_stream(stream));
+  });
 }
 
 }  // extern "C"

@@ -238,10 +238,6 @@ __global__ __launch_bounds__(kBlock) void compare_waves_kernel(int op, Side<O> l
   }
 }
 
-unsigned waves_grid(int64_t n) {   // a wave takes 64 pairs a step
-  return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, kBlock), static_cast<int64_t>(device_cus()) * 8)));
-}
-
 template <typename O>
 Side<O> side_of(const ArxBinarySpan* span, const void* literal, int64_t literal_length, int64_t n) {
   Side<O> s;
@@ -270,7 +266,7 @@ int compare_launch(int op, const ArxBinarySpan* left, const ArxBinarySpan* right
   }
   const Side<O> l = side_of<O>(left, literal, literal_length, n), r = side_of<O>(right, literal, literal_length, n);
   if (waves) {
-    hipLaunchKernelGGL(compare_waves_kernel<O>, dim3(waves_grid(n)), dim3(kBlock), 0, st, op, l, r, n, static_cast<uint64_t*>(out_bits));
+    hipLaunchKernelGGL(compare_waves_kernel<O>, dim3(waves_grid(n, kWave)), dim3(kBlock), 0, st, op, l, r, n, static_cast<uint64_t*>(out_bits));
     ARX_CHECK_LAUNCH("compare_waves_kernel");
     g_compare_wave_launches.fetch_add(1, std::memory_order_relaxed);
   } else {
@@ -305,11 +301,9 @@ int arx_compare_binary(int op, const ArxBinarySpan* left, const ArxBinarySpan* r
     set_error("compare_binary: op %d is not 0 (equal) .. 5 (less_equal)", op);
     return ARX_INVALID;
   }
-  if (path != ARX_COMPARE_PATH_AUTO && path != ARX_COMPARE_PATH_ROWS && path != ARX_COMPARE_PATH_WAVES) {
-    set_error("compare_binary: path %d is not 0 (auto), 1 (rows) or 2 (waves)", path);
-    return ARX_INVALID;
-  }
-  int rc = check_common("compare_binary", left != nullptr ? left : right, offset_width);
+  int rc = check_path("compare_binary", path);
+  if (rc != ARX_OK) return rc;
+  rc = check_common("compare_binary", left != nullptr ? left : right, offset_width);
   if (rc == ARX_OK && left != nullptr && right != nullptr) rc = check_common("compare_binary", right, offset_width);
   if (rc != ARX_OK) return rc;
   if (left != nullptr && right != nullptr && left->length != right->length) {
@@ -327,12 +321,12 @@ int arx_compare_binary(int op, const ArxBinarySpan* left, const ArxBinarySpan* r
     set_error("compare_binary: NULL out_bits or NULL offsets");
     return ARX_INVALID;
   }
-  int64_t pair_bytes = data_bytes_hint < 0 ? -1 : data_bytes_hint / n;
+  int64_t pair_bytes = mean_bytes(data_bytes_hint, n);
   if (has_literal && pair_bytes >= 0) pair_bytes = 2 * std::min(pair_bytes, literal_length);
-  const bool waves = path == ARX_COMPARE_PATH_WAVES || (path == ARX_COMPARE_PATH_AUTO && pair_bytes >= kWavesPathMeanPair);
-  hipStream_t st = as_stream(stream);
-  return offset_width == 4 ? compare_launch<int32_t>(op, left, right, literal, literal_length, n, waves, out_bits, st)
-                           : compare_launch<int64_t>(op, left, right, literal, literal_length, n, waves, out_bits, st);
+  const bool waves = take_waves(path, pair_bytes, kWavesPathMeanPair);
+  return with_offset_type(offset_width, [&](auto o) {
+    return compare_launch<decltype(o)>(op, left, right, literal, literal_length, n, waves, out_bits, as_stream(stream));
+  });
 }
 
 }  // extern "C"

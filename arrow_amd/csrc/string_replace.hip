@@ -47,14 +47,8 @@ namespace {
 constexpr int kGranule = 16;                     // bytes a lane of the waves form owns a step
 constexpr int kTileBytes = kWave * kGranule;     // 1 KiB of a row per wave step
 constexpr int64_t kNoCap = INT64_MAX;
-// auto (path 0): the waves form from this mean row size on (the offsets call: data_bytes_hint / length; the data call,
-// which is handed no hint: total_bytes / length, the bytes it writes a row).  Measured on the MI355X
-// (scripts/exp_string_replace.py, profiles/string_replace.txt, 128 MiB of rows with a pattern that never occurs, both
-// calls timed together): the rows form is ahead up to 256 bytes a row (0.960 ms against 1.084 ms; 0.555 ms against
-// 3.909 ms at 64), the waves form from 512 bytes on (0.589 ms against 0.907 ms; 0.284 ms against 1.692 ms at 4 KiB).
-// A frequent pattern does not move it: at 64 bytes a row with two matches each the rows form takes 0.67 ms, the waves
-// form 5.5 ms.
-constexpr int64_t kWavesPathMeanRow = 512;
+// auto (path 0): the waves form from a mean row size of kWavesPathMeanRow on (string_rows.h).  The offsets call:
+// data_bytes_hint / length; the data call, which is handed no hint: total_bytes / length, the bytes it writes a row.
 
 std::atomic<int64_t> g_replace_row_launches{0}, g_replace_wave_launches{0};
 
@@ -354,22 +348,12 @@ int waves_chunk(int64_t n) {
   while (chunk < want && chunk < kWave) chunk <<= 1;
   return chunk;
 }
-unsigned waves_grid(int64_t n, int chunk = 1) {   // a wave takes `chunk` rows a step and strides over what is left
-  return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(ceil_div(ceil_div(n, chunk), kWavesPerBlock), static_cast<int64_t>(device_cus()) * 8)));
-}
 
-bool take_waves(int path, int64_t mean_row_bytes) {
-  return path == ARX_REPLACE_PATH_WAVES || (path == ARX_REPLACE_PATH_AUTO && mean_row_bytes >= kWavesPathMeanRow);
-}
-
+// step one (the `produce` of offsets_call; the workspace's second part holds the counts)
 template <typename O>
-int replace_offsets_launch(const Column& c, bool waves, const uint8_t* pat, int64_t m, int64_t r, int64_t cap, void* ws, void* out_offsets,
-                           int64_t* out_total, hipStream_t st) {
+int replace_offsets_launch(const Column& c, bool waves, const uint8_t* pat, int64_t m, int64_t r, int64_t cap, O* lens, O* cnt,
+                           unsigned long long* sums, hipStream_t st) {
   const O* offsets = static_cast<const O*>(c.offsets);
-  auto* sums = static_cast<unsigned long long*>(ws);
-  O* cnt = reinterpret_cast<O*>(static_cast<uint8_t*>(ws) + bin_sums_bytes(c.n));
-  O* lens = static_cast<O*>(out_offsets);
-  ARX_HIP(hipMemsetAsync(sums, 0, bin_sums_bytes(c.n), st));
   if (waves) {
     const int chunk = waves_chunk(c.n);
     hipLaunchKernelGGL(replace_count_waves_kernel<O>, dim3(waves_grid(c.n, chunk)), dim3(kBlock), 0, st, c.valid, offsets, c.data, c.n, pat, m,
@@ -382,7 +366,7 @@ int replace_offsets_launch(const Column& c, bool waves, const uint8_t* pat, int6
     ARX_CHECK_LAUNCH("replace_count_rows_kernel");
     g_replace_row_launches.fetch_add(1, std::memory_order_relaxed);
   }
-  return bin_scan_lengths<O>(lens, c.n, reinterpret_cast<long long*>(sums), "replacing substrings of a binary array", out_total, st);
+  return ARX_OK;
 }
 
 template <typename O>
@@ -407,11 +391,8 @@ int replace_data_launch(const Column& c, bool waves, const uint8_t* pat, int64_t
 // the checks the two calls share
 int check_replace(const char* who, const ArxBinarySpan* values, int offset_width, const void* pattern, int64_t pattern_length,
                   bool replacement_missing, int64_t replacement_length, int path) {
-  if (path != ARX_REPLACE_PATH_AUTO && path != ARX_REPLACE_PATH_ROWS && path != ARX_REPLACE_PATH_WAVES) {
-    set_error("%s: path %d is not 0 (auto), 1 (rows) or 2 (waves)", who, path);
-    return ARX_INVALID;
-  }
-  const int rc = check_common(who, values, offset_width);
+  int rc = check_path(who, path);
+  if (rc == ARX_OK) rc = check_common(who, values, offset_width);
   if (rc != ARX_OK) return rc;
   if (pattern_length <= 0) {
     set_error("%s: pattern_length %lld is not positive (the empty pattern has no device kernel)", who, static_cast<long long>(pattern_length));
@@ -423,15 +404,6 @@ int check_replace(const char* who, const ArxBinarySpan* values, int offset_width
   }
   if (pattern == nullptr || replacement_missing) {
     set_error("%s: NULL pattern or replacement", who);
-    return ARX_INVALID;
-  }
-  return ARX_OK;
-}
-
-int check_replace_workspace(const char* who, const void* ws, size_t ws_bytes, int64_t length, int offset_width) {
-  if (ws == nullptr || ws_bytes < bin_workspace_bytes(length, offset_width) || (reinterpret_cast<uint64_t>(ws) & 7) != 0) {
-    set_error("%s: ws of %llu bytes is NULL, unaligned or smaller than arx_replace_substring_workspace_bytes = %llu", who,
-              static_cast<unsigned long long>(ws_bytes), static_cast<unsigned long long>(bin_workspace_bytes(length, offset_width)));
     return ARX_INVALID;
   }
   return ARX_OK;
@@ -458,32 +430,17 @@ size_t arx_replace_substring_workspace_bytes(int64_t length, int offset_width) {
 int arx_replace_substring_offsets(const ArxBinarySpan* values, int offset_width, const void* pattern, int64_t pattern_length,
                                   int64_t replacement_length, int64_t max_replacements, int64_t data_bytes_hint, int path, void* ws,
                                   size_t ws_bytes, void* out_offsets, int64_t* out_total_bytes, void* stream) {
-  if (values == nullptr || out_offsets == nullptr || out_total_bytes == nullptr) {
-    set_error("replace_substring_offsets: NULL values, out_offsets or out_total_bytes");
-    return ARX_INVALID;
-  }
-  int rc = check_replace("replace_substring_offsets", values, offset_width, pattern, pattern_length, false, replacement_length, path);
+  int rc = check_offsets_arguments("replace_substring_offsets", values, out_offsets, out_total_bytes);
+  if (rc == ARX_OK) rc = check_replace("replace_substring_offsets", values, offset_width, pattern, pattern_length, false, replacement_length, path);
   if (rc != ARX_OK) return rc;
-  hipStream_t st = as_stream(stream);
-  if (values->length == 0) {
-    *out_total_bytes = 0;
-    ARX_HIP(hipMemsetAsync(out_offsets, 0, static_cast<size_t>(offset_width), st));
-    return ARX_OK;
-  }
-  if (values->offsets == nullptr) {
-    set_error("replace_substring_offsets: NULL offsets of values");
-    return ARX_INVALID;
-  }
-  rc = check_replace_workspace("replace_substring_offsets", ws, ws_bytes, values->length, offset_width);
-  if (rc != ARX_OK) return rc;
-  *out_total_bytes = 0;
-  const Column c = column_of(values, offset_width);
-  const bool waves = take_waves(path, data_bytes_hint < 0 ? -1 : data_bytes_hint / c.n);
   const int64_t cap = max_replacements < 0 ? kNoCap : max_replacements;
   const auto* pat = static_cast<const uint8_t*>(pattern);
-  return offset_width == 4
-             ? replace_offsets_launch<int32_t>(c, waves, pat, pattern_length, replacement_length, cap, ws, out_offsets, out_total_bytes, st)
-             : replace_offsets_launch<int64_t>(c, waves, pat, pattern_length, replacement_length, cap, ws, out_offsets, out_total_bytes, st);
+  return offsets_call("replace_substring_offsets", "arx_replace_substring_workspace_bytes", values, offset_width, ws, ws_bytes, out_offsets,
+                      out_total_bytes, "replacing substrings of a binary array", as_stream(stream),
+                      [&](const Column& c, auto* lens, auto* cnt, unsigned long long* sums, hipStream_t st) {
+                        const bool waves = take_waves(path, mean_bytes(data_bytes_hint, c.n));
+                        return replace_offsets_launch(c, waves, pat, pattern_length, replacement_length, cap, lens, cnt, sums, st);
+                      });
 }
 
 int arx_replace_substring_data(const ArxBinarySpan* values, int offset_width, const void* pattern, int64_t pattern_length,
@@ -506,7 +463,7 @@ int arx_replace_substring_data(const ArxBinarySpan* values, int offset_width, co
     set_error("replace_substring_data: NULL out_offsets, out_data, or offsets or data of values");
     return ARX_INVALID;
   }
-  rc = check_replace_workspace("replace_substring_data", ws, ws_bytes, n, offset_width);
+  rc = check_offsets_workspace("replace_substring_data", "arx_replace_substring_workspace_bytes", ws, ws_bytes, n, offset_width);
   if (rc != ARX_OK) return rc;
   (void)max_replacements;   // (the workspace holds every row's accepted count, the cap applied)
   const Column c = column_of(values, offset_width);
@@ -514,8 +471,9 @@ int arx_replace_substring_data(const ArxBinarySpan* values, int offset_width, co
   hipStream_t st = as_stream(stream);
   const auto* pat = static_cast<const uint8_t*>(pattern);
   const auto* rep = static_cast<const uint8_t*>(replacement);
-  return offset_width == 4 ? replace_data_launch<int32_t>(c, waves, pat, pattern_length, rep, replacement_length, ws, out_offsets, out_data, st)
-                           : replace_data_launch<int64_t>(c, waves, pat, pattern_length, rep, replacement_length, ws, out_offsets, out_data, st);
+  return with_offset_type(offset_width, [&](auto o) {
+    return replace_data_launch<decltype(o)>(c, waves, pat, pattern_length, rep, replacement_length, ws, out_offsets, out_data, st);
+  });
 }
 
 }  // extern "C"

@@ -1,7 +1,9 @@
 // What the row-wise string kernels share (string_slice.hip, string_trim.hip, match_substring.hip, string_compare.hip,
-// string_replace.hip): the bit-7 byte masks of a 16-byte granule, the unaligned 8-byte read and the LDS staging of a
-// literal operand, the window walk that finds a pattern's next match in a row, the view
-// of a values column, the grid of a one-lane-per-row launch and the argument checks of their C entry points.
+// string_replace.hip).  Device side: the bit-7 byte masks of a 16-byte granule, the unaligned 8-byte read and the LDS
+// staging of a literal operand, the window walk that finds a pattern's next match in a row.  Host side: the view of a
+// values column, the grids of a one-lane-per-row and a one-wave-per-row launch, the choice between the two forms, the
+// offset type of a call from its offset_width, the argument checks of the C entry points, and offsets_call: the frame of
+// the first of the two calls that make a variable-length result (slices, trims, replace_substring).
 #pragma once
 #include "binary_scan_copy.h"
 
@@ -121,6 +123,47 @@ inline Column column_of(const ArxBinarySpan* values, int offset_width) {
   return c;
 }
 
+// one wave per row: a wave takes `chunk` consecutive rows a step (kWave in the slices and the comparisons, whose lane i
+// keeps row i's result) and strides over what is left
+inline unsigned waves_grid(int64_t n, int chunk = 1) {
+  return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(ceil_div(ceil_div(n, chunk), kWavesPerBlock), static_cast<int64_t>(device_cus()) * 8)));
+}
+
+// The `path` of a call: 0 = auto, 1 = rows, 2 = waves, under the three public names of include/arrow_amd.h.
+static_assert(ARX_STRING_PATH_AUTO == 0 && ARX_REPLACE_PATH_AUTO == 0 && ARX_COMPARE_PATH_AUTO == 0, "one auto");
+static_assert(ARX_STRING_PATH_ROWS == 1 && ARX_REPLACE_PATH_ROWS == 1 && ARX_COMPARE_PATH_ROWS == 1, "one rows");
+static_assert(ARX_STRING_PATH_WAVES == 2 && ARX_REPLACE_PATH_WAVES == 2 && ARX_COMPARE_PATH_WAVES == 2, "one waves");
+inline int check_path(const char* who, int path) {
+  if (path != ARX_STRING_PATH_AUTO && path != ARX_STRING_PATH_ROWS && path != ARX_STRING_PATH_WAVES) {
+    set_error("%s: path %d is not 0 (auto), 1 (rows) or 2 (waves)", who, path);
+    return ARX_INVALID;
+  }
+  return ARX_OK;
+}
+// auto: the waves form from this mean row size on.  Measured on the MI355X for the codepoint walk of the slices
+// (scripts/exp_string_slice.py, profiles/string_slice.txt, both forms over 2^28 data bytes: counting a column, the rows
+// form is ahead up to 128 bytes a row, 0.214 ms against 0.533 ms, the waves form from 512 on, 0.142 ms against 0.248 ms;
+// a slice with small bounds reads a granule or two a row in either form and the rows form stays ahead, DESIGN.md 4.21 —
+// the threshold bounds the other case, a bound deep inside long or skewed rows) and for replace_substring
+// (scripts/exp_string_replace.py, profiles/string_replace.txt, 128 MiB of rows with a pattern that never occurs, both
+// calls timed together: the rows form is ahead up to 256 bytes a row, 0.960 ms against 1.084 ms and 0.555 ms against
+// 3.909 ms at 64, the waves form from 512 on, 0.589 ms against 0.907 ms and 0.284 ms against 1.692 ms at 4 KiB; a
+// frequent pattern does not move it: at 64 bytes a row with two matches each the rows form takes 0.67 ms, the waves form
+// 5.5 ms).
+constexpr int64_t kWavesPathMeanRow = 512;
+// the mean row size of a call from its data_bytes_hint (negative: unknown, and so is the mean); n > 0
+inline int64_t mean_bytes(int64_t hint, int64_t n) { return hint < 0 ? -1 : hint / n; }
+// the form of a call: on auto the waves form from the mean `from_mean` > 0 on, so never for an unknown (negative) mean
+inline bool take_waves(int path, int64_t mean, int64_t from_mean = kWavesPathMeanRow) {
+  return path == ARX_STRING_PATH_WAVES || (path == ARX_STRING_PATH_AUTO && mean >= from_mean);
+}
+
+// f(O{}) with O the offset type of a checked offset_width: int32_t for 4, int64_t for 8
+template <typename F>
+inline int with_offset_type(int offset_width, F&& f) {
+  return offset_width == 4 ? f(int32_t{}) : f(int64_t{});
+}
+
 // the checks the calls share; `who` names the call
 inline int check_common(const char* who, const ArxBinarySpan* values, int offset_width) {
   if (offset_width != 4 && offset_width != 8) {
@@ -133,14 +176,60 @@ inline int check_common(const char* who, const ArxBinarySpan* values, int offset
   }
   return ARX_OK;
 }
-// the workspace of an offsets call: [sums][src_start] of binary_scan_copy.h
-inline int check_offsets_workspace(const char* who, const void* ws, size_t ws_bytes, int64_t length, int offset_width) {
+// the workspace of an offsets call, [sums][src_start] of binary_scan_copy.h; `sizing` names the function that sizes it
+inline int check_offsets_workspace(const char* who, const char* sizing, const void* ws, size_t ws_bytes, int64_t length, int offset_width) {
   if (ws == nullptr || ws_bytes < bin_workspace_bytes(length, offset_width) || (reinterpret_cast<uint64_t>(ws) & 7) != 0) {
-    set_error("%s: ws of %llu bytes is NULL, unaligned or smaller than arx_string_slice_workspace_bytes = %llu", who,
-              static_cast<unsigned long long>(ws_bytes), static_cast<unsigned long long>(bin_workspace_bytes(length, offset_width)));
+    set_error("%s: ws of %llu bytes is NULL, unaligned or smaller than %s = %llu", who, static_cast<unsigned long long>(ws_bytes), sizing,
+              static_cast<unsigned long long>(bin_workspace_bytes(length, offset_width)));
     return ARX_INVALID;
   }
   return ARX_OK;
+}
+
+// An OFFSETS CALL (arx_string_slice_offsets, arx_string_trim_offsets, arx_replace_substring_offsets): the first of the two
+// calls that make a variable-length result out of the rows of `values`, one for one.  The entry point refuses its NULL
+// arguments first (check_offsets_arguments) and runs its own checks, in its own order; offsets_call is all the rest.
+//   length 0: *out_total_bytes = 0, out_offsets[0] = 0, nothing launched.
+//   else: the workspace is carved (binary_scan_copy.h), its sums are zeroed, `produce(column, lens, src, sums, stream)`
+//   launches the call's own first kernel under that header's contract (O* lens = out_offsets, O* src = the workspace's
+//   second part, O the offset type) and counts the launch, and bin_scan_lengths turns the lengths into offsets and
+//   returns the total: "offset overflow while <what>" where it does not fit.
+// A refused call has written nothing.
+inline int check_offsets_arguments(const char* who, const ArxBinarySpan* values, const void* out_offsets, const int64_t* out_total_bytes) {
+  if (values == nullptr || out_offsets == nullptr || out_total_bytes == nullptr) {
+    set_error("%s: NULL values, out_offsets or out_total_bytes", who);
+    return ARX_INVALID;
+  }
+  return ARX_OK;
+}
+template <typename F>
+int offsets_call(const char* who, const char* sizing, const ArxBinarySpan* values, int offset_width, void* ws, size_t ws_bytes,
+                 void* out_offsets, int64_t* out_total_bytes, const char* what, hipStream_t st, F&& produce) {
+  int rc = check_common(who, values, offset_width);   // (again, where the entry point's own checks ran it in their place)
+  if (rc != ARX_OK) return rc;
+  if (values->length == 0) {
+    *out_total_bytes = 0;
+    ARX_HIP(hipMemsetAsync(out_offsets, 0, static_cast<size_t>(offset_width), st));
+    return ARX_OK;
+  }
+  if (values->offsets == nullptr) {
+    set_error("%s: NULL offsets of values", who);
+    return ARX_INVALID;
+  }
+  rc = check_offsets_workspace(who, sizing, ws, ws_bytes, values->length, offset_width);
+  if (rc != ARX_OK) return rc;
+  *out_total_bytes = 0;
+  const Column c = column_of(values, offset_width);
+  return with_offset_type(offset_width, [&](auto o) {
+    using O = decltype(o);
+    auto* sums = static_cast<unsigned long long*>(ws);
+    O* src = reinterpret_cast<O*>(static_cast<uint8_t*>(ws) + bin_sums_bytes(c.n));
+    O* lens = static_cast<O*>(out_offsets);
+    ARX_HIP(hipMemsetAsync(sums, 0, bin_sums_bytes(c.n), st));
+    const int launched = produce(c, lens, src, sums, st);
+    if (launched != ARX_OK) return launched;
+    return bin_scan_lengths<O>(lens, c.n, reinterpret_cast<long long*>(sums), what, out_total_bytes, st);
+  });
 }
 
 }  // namespace arx

@@ -22,7 +22,7 @@
 //           and one ballot find the lane and the byte of the k-th lead.  Long or skewed rows: a lane of the rows form
 //           would walk its row alone while 63 idle.  A wave takes 64 consecutive rows one after the other and lane i
 //           keeps row i's result, so results are stored coalesced and a sum gets one atomic per 64 rows in both forms.
-// Auto takes the waves form from a mean row size (data_bytes_hint / length) of kWavesPathMeanRow bytes on.
+// Auto takes the waves form from a mean row size (data_bytes_hint / length) of kWavesPathMeanRow bytes on (string_rows.h).
 //
 // Slicing is two calls, since the output size depends on the data: arx_string_slice_offsets writes every row's source
 // begin into the workspace and its length into out_offsets, adds the lengths of every kBinRows rows into the
@@ -34,12 +34,6 @@ namespace arx {
 
 namespace {
 
-// auto (path 0): the waves form from this mean row size (data_bytes_hint / length) on.  Measured on the MI355X
-// (scripts/exp_string_slice.py, profiles/string_slice.txt, both forms over 2^28 data bytes): counting a column, the rows
-// form is ahead up to 128 bytes a row (0.214 ms against 0.533 ms), the waves form from 512 on (0.142 ms against 0.248 ms).
-// A slice with small bounds reads a granule or two a row in either form and the rows form stays ahead;
-// the threshold bounds the other case, a bound deep inside long or skewed rows.
-constexpr int64_t kWavesPathMeanRow = 512;
 constexpr int64_t kNoStop = INT64_MAX;
 constexpr int kLengthMaxBlocks = 1 << 20;   // workgroups of a binary_length launch (a workgroup strides over what is left)
 
@@ -332,14 +326,6 @@ __global__ __launch_bounds__(kBlock) void slice_waves_kernel(Bits valid, const O
   }
 }
 
-unsigned waves_grid(int64_t n) {   // a wave takes 64 rows a step
-  return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, kBlock), static_cast<int64_t>(device_cus()) * 8)));
-}
-
-bool take_waves(int path, int64_t hint, int64_t n) {
-  return path == ARX_STRING_PATH_WAVES || (path == ARX_STRING_PATH_AUTO && hint >= 0 && hint / n >= kWavesPathMeanRow);
-}
-
 template <typename O>
 int length_launch(const Column& c, int unit, bool waves, void* out, hipStream_t st) {
   const O* offsets = static_cast<const O*>(c.offsets);
@@ -349,7 +335,7 @@ int length_launch(const Column& c, int unit, bool waves, void* out, hipStream_t 
     hipLaunchKernelGGL(byte_length_kernel<O>, dim3(grid), dim3(kBlock), 0, st, c.valid, offsets, c.n, static_cast<O*>(out));
     ARX_CHECK_LAUNCH("byte_length_kernel");
   } else if (waves) {
-    hipLaunchKernelGGL(codepoint_length_waves_kernel<O>, dim3(waves_grid(c.n)), dim3(kBlock), 0, st, c.valid, offsets, c.data, c.n,
+    hipLaunchKernelGGL(codepoint_length_waves_kernel<O>, dim3(waves_grid(c.n, kWave)), dim3(kBlock), 0, st, c.valid, offsets, c.data, c.n,
                        static_cast<O*>(out));
     ARX_CHECK_LAUNCH("codepoint_length_waves_kernel");
     g_slice_wave_launches.fetch_add(1, std::memory_order_relaxed);
@@ -362,20 +348,17 @@ int length_launch(const Column& c, int unit, bool waves, void* out, hipStream_t 
   return ARX_OK;
 }
 
+// step one of a slice (the `produce` of offsets_call)
 template <typename O>
-int slice_offsets_launch(const Column& c, int unit, bool waves, int64_t start, int64_t stop, void* ws, void* out_offsets,
-                         int64_t* out_total, hipStream_t st) {
+int slice_offsets_launch(const Column& c, int unit, bool waves, int64_t start, int64_t stop, O* lens, O* src, unsigned long long* sums,
+                         hipStream_t st) {
   const O* offsets = static_cast<const O*>(c.offsets);
-  auto* sums = static_cast<unsigned long long*>(ws);
-  O* src = reinterpret_cast<O*>(static_cast<uint8_t*>(ws) + bin_sums_bytes(c.n));
-  O* lens = static_cast<O*>(out_offsets);
-  ARX_HIP(hipMemsetAsync(sums, 0, bin_sums_bytes(c.n), st));
   if (unit == ARX_STRING_UNIT_BYTES) {
     hipLaunchKernelGGL((slice_rows_kernel<O, ARX_STRING_UNIT_BYTES>), dim3(rows_grid(c.n)), dim3(kBlock), 0, st, c.valid, offsets, c.data,
                        c.n, start, stop, lens, src, sums);
     ARX_CHECK_LAUNCH("slice_rows_kernel (bytes)");
   } else if (waves) {
-    hipLaunchKernelGGL(slice_waves_kernel<O>, dim3(waves_grid(c.n)), dim3(kBlock), 0, st, c.valid, offsets, c.data, c.n, start, stop,
+    hipLaunchKernelGGL(slice_waves_kernel<O>, dim3(waves_grid(c.n, kWave)), dim3(kBlock), 0, st, c.valid, offsets, c.data, c.n, start, stop,
                        lens, src, sums);
     ARX_CHECK_LAUNCH("slice_waves_kernel");
     g_slice_wave_launches.fetch_add(1, std::memory_order_relaxed);
@@ -385,7 +368,7 @@ int slice_offsets_launch(const Column& c, int unit, bool waves, int64_t start, i
     ARX_CHECK_LAUNCH("slice_rows_kernel (codepoints)");
     g_slice_row_launches.fetch_add(1, std::memory_order_relaxed);
   }
-  return bin_scan_lengths<O>(lens, c.n, reinterpret_cast<long long*>(sums), "slicing a binary array", out_total, st);
+  return ARX_OK;
 }
 
 int check_unit_path(const char* who, int unit, int path) {
@@ -393,11 +376,7 @@ int check_unit_path(const char* who, int unit, int path) {
     set_error("%s: unit %d is not 0 (bytes) or 1 (codepoints)", who, unit);
     return ARX_INVALID;
   }
-  if (path != ARX_STRING_PATH_AUTO && path != ARX_STRING_PATH_ROWS && path != ARX_STRING_PATH_WAVES) {
-    set_error("%s: path %d is not 0 (auto), 1 (rows) or 2 (waves)", who, path);
-    return ARX_INVALID;
-  }
-  return ARX_OK;
+  return check_path(who, path);
 }
 
 }  // namespace
@@ -429,9 +408,8 @@ int arx_string_length(const ArxBinarySpan* values, int offset_width, int unit, i
     return ARX_INVALID;
   }
   const Column c = column_of(values, offset_width);
-  const bool waves = take_waves(path, data_bytes_hint, c.n);
-  hipStream_t st = as_stream(stream);
-  return offset_width == 4 ? length_launch<int32_t>(c, unit, waves, out_lengths, st) : length_launch<int64_t>(c, unit, waves, out_lengths, st);
+  const bool waves = take_waves(path, mean_bytes(data_bytes_hint, c.n));
+  return with_offset_type(offset_width, [&](auto o) { return length_launch<decltype(o)>(c, unit, waves, out_lengths, as_stream(stream)); });
 }
 
 size_t arx_string_slice_workspace_bytes(int64_t length, int offset_width) {
@@ -440,29 +418,15 @@ size_t arx_string_slice_workspace_bytes(int64_t length, int offset_width) {
 
 int arx_string_slice_offsets(const ArxBinarySpan* values, int offset_width, int unit, int64_t start, int64_t stop, int64_t data_bytes_hint,
                              int path, void* ws, size_t ws_bytes, void* out_offsets, int64_t* out_total_bytes, void* stream) {
-  if (values == nullptr || out_offsets == nullptr || out_total_bytes == nullptr) {
-    set_error("string_slice_offsets: NULL values, out_offsets or out_total_bytes");
-    return ARX_INVALID;
-  }
-  int rc = check_unit_path("string_slice_offsets", unit, path);
-  if (rc == ARX_OK) rc = check_common("string_slice_offsets", values, offset_width);
+  int rc = check_offsets_arguments("string_slice_offsets", values, out_offsets, out_total_bytes);
+  if (rc == ARX_OK) rc = check_unit_path("string_slice_offsets", unit, path);
   if (rc != ARX_OK) return rc;
-  hipStream_t st = as_stream(stream);
-  *out_total_bytes = 0;
-  if (values->length == 0) {
-    ARX_HIP(hipMemsetAsync(out_offsets, 0, static_cast<size_t>(offset_width), st));
-    return ARX_OK;
-  }
-  if (values->offsets == nullptr) {
-    set_error("string_slice_offsets: NULL offsets of values");
-    return ARX_INVALID;
-  }
-  rc = check_offsets_workspace("string_slice_offsets", ws, ws_bytes, values->length, offset_width);
-  if (rc != ARX_OK) return rc;
-  const Column c = column_of(values, offset_width);
-  const bool waves = take_waves(path, data_bytes_hint, c.n);
-  return offset_width == 4 ? slice_offsets_launch<int32_t>(c, unit, waves, start, stop, ws, out_offsets, out_total_bytes, st)
-                           : slice_offsets_launch<int64_t>(c, unit, waves, start, stop, ws, out_offsets, out_total_bytes, st);
+  return offsets_call("string_slice_offsets", "arx_string_slice_workspace_bytes", values, offset_width, ws, ws_bytes, out_offsets,
+                      out_total_bytes, "slicing a binary array", as_stream(stream),
+                      [&](const Column& c, auto* lens, auto* src, unsigned long long* sums, hipStream_t st) {
+                        const bool waves = take_waves(path, mean_bytes(data_bytes_hint, c.n));
+                        return slice_offsets_launch(c, unit, waves, start, stop, lens, src, sums, st);
+                      });
 }
 
 int arx_string_slice_data(const ArxBinarySpan* values, int offset_width, const void* ws, size_t ws_bytes, const void* out_offsets,
@@ -492,10 +456,11 @@ int arx_string_slice_data(const ArxBinarySpan* values, int offset_width, const v
   const auto* data = static_cast<const uint8_t*>(values->data);
   const uint8_t* src = static_cast<const uint8_t*>(ws) + bin_sums_bytes(n);
   hipStream_t st = as_stream(stream);
-  return offset_width == 4 ? bin_copy_rows<int32_t>(data, reinterpret_cast<const int32_t*>(src), static_cast<const int32_t*>(out_offsets), n,
-                                                    total_bytes, static_cast<uint8_t*>(out_data), 0, st)
-                           : bin_copy_rows<int64_t>(data, reinterpret_cast<const int64_t*>(src), static_cast<const int64_t*>(out_offsets), n,
-                                                    total_bytes, static_cast<uint8_t*>(out_data), 0, st);
+  return with_offset_type(offset_width, [&](auto o) {
+    using O = decltype(o);
+    return bin_copy_rows<O>(data, reinterpret_cast<const O*>(src), static_cast<const O*>(out_offsets), n, total_bytes,
+                            static_cast<uint8_t*>(out_data), 0, st);
+  });
 }
 
 }  // extern "C"

@@ -209,35 +209,32 @@ __global__ __launch_bounds__(kBlock) void trim_rows_kernel(Bits valid, const O* 
   }
 }
 
+// step one of a trim (the `produce` of offsets_call), by its sides and its set kind
 template <typename O, int SIDES, int KIND>
-int trim_launch(const Column& c, const TrimSet& set, void* ws, void* out_offsets, int64_t* out_total, hipStream_t st) {
-  auto* sums = static_cast<unsigned long long*>(ws);
-  O* src = reinterpret_cast<O*>(static_cast<uint8_t*>(ws) + bin_sums_bytes(c.n));
-  O* lens = static_cast<O*>(out_offsets);
-  ARX_HIP(hipMemsetAsync(sums, 0, bin_sums_bytes(c.n), st));
+int trim_launch(const Column& c, const TrimSet& set, O* lens, O* src, unsigned long long* sums, hipStream_t st) {
   hipLaunchKernelGGL((trim_rows_kernel<O, SIDES, KIND>), dim3(rows_grid(c.n)), dim3(kBlock), 0, st, c.valid, static_cast<const O*>(c.offsets),
                      c.data, c.n, set, lens, src, sums);
   ARX_CHECK_LAUNCH("trim_rows_kernel");
   g_trim_launches.fetch_add(1, std::memory_order_relaxed);
-  return bin_scan_lengths<O>(lens, c.n, reinterpret_cast<long long*>(sums), "trimming a string array", out_total, st);
+  return ARX_OK;
 }
 
 template <typename O, int SIDES>
-int trim_by_kind(int kind, const Column& c, const TrimSet& set, void* ws, void* out_offsets, int64_t* out_total, hipStream_t st) {
+int trim_by_kind(int kind, const Column& c, const TrimSet& set, O* lens, O* src, unsigned long long* sums, hipStream_t st) {
   switch (kind) {
-    case ARX_TRIM_ASCII_WHITESPACE: return trim_launch<O, SIDES, ARX_TRIM_ASCII_WHITESPACE>(c, set, ws, out_offsets, out_total, st);
-    case ARX_TRIM_UTF8_WHITESPACE: return trim_launch<O, SIDES, ARX_TRIM_UTF8_WHITESPACE>(c, set, ws, out_offsets, out_total, st);
-    case ARX_TRIM_BYTES: return trim_launch<O, SIDES, ARX_TRIM_BYTES>(c, set, ws, out_offsets, out_total, st);
-    default: return trim_launch<O, SIDES, ARX_TRIM_CODEPOINTS>(c, set, ws, out_offsets, out_total, st);
+    case ARX_TRIM_ASCII_WHITESPACE: return trim_launch<O, SIDES, ARX_TRIM_ASCII_WHITESPACE>(c, set, lens, src, sums, st);
+    case ARX_TRIM_UTF8_WHITESPACE: return trim_launch<O, SIDES, ARX_TRIM_UTF8_WHITESPACE>(c, set, lens, src, sums, st);
+    case ARX_TRIM_BYTES: return trim_launch<O, SIDES, ARX_TRIM_BYTES>(c, set, lens, src, sums, st);
+    default: return trim_launch<O, SIDES, ARX_TRIM_CODEPOINTS>(c, set, lens, src, sums, st);
   }
 }
 
 template <typename O>
-int trim_by_sides(int sides, int kind, const Column& c, const TrimSet& set, void* ws, void* out_offsets, int64_t* out_total, hipStream_t st) {
+int trim_by_sides(int sides, int kind, const Column& c, const TrimSet& set, O* lens, O* src, unsigned long long* sums, hipStream_t st) {
   switch (sides) {
-    case ARX_TRIM_LEFT: return trim_by_kind<O, ARX_TRIM_LEFT>(kind, c, set, ws, out_offsets, out_total, st);
-    case ARX_TRIM_RIGHT: return trim_by_kind<O, ARX_TRIM_RIGHT>(kind, c, set, ws, out_offsets, out_total, st);
-    default: return trim_by_kind<O, ARX_TRIM_BOTH>(kind, c, set, ws, out_offsets, out_total, st);
+    case ARX_TRIM_LEFT: return trim_by_kind<O, ARX_TRIM_LEFT>(kind, c, set, lens, src, sums, st);
+    case ARX_TRIM_RIGHT: return trim_by_kind<O, ARX_TRIM_RIGHT>(kind, c, set, lens, src, sums, st);
+    default: return trim_by_kind<O, ARX_TRIM_BOTH>(kind, c, set, lens, src, sums, st);
   }
 }
 
@@ -284,10 +281,8 @@ extern "C" {
 
 int arx_string_trim_offsets(const ArxBinarySpan* values, int offset_width, int sides, int set_kind, const void* set, int64_t set_length,
                             void* ws, size_t ws_bytes, void* out_offsets, int64_t* out_total_bytes, void* stream) {
-  if (values == nullptr || out_offsets == nullptr || out_total_bytes == nullptr) {
-    set_error("string_trim_offsets: NULL values, out_offsets or out_total_bytes");
-    return ARX_INVALID;
-  }
+  int rc = check_offsets_arguments("string_trim_offsets", values, out_offsets, out_total_bytes);
+  if (rc != ARX_OK) return rc;
   if (sides != ARX_TRIM_LEFT && sides != ARX_TRIM_RIGHT && sides != ARX_TRIM_BOTH) {
     set_error("string_trim_offsets: sides %d is not 1 (left), 2 (right) or 3 (both)", sides);
     return ARX_INVALID;
@@ -296,7 +291,7 @@ int arx_string_trim_offsets(const ArxBinarySpan* values, int offset_width, int s
     set_error("string_trim_offsets: set_kind %d is not 0 (ascii whitespace), 1 (utf8 whitespace), 2 (bytes) or 3 (codepoints)", set_kind);
     return ARX_INVALID;
   }
-  int rc = check_common("string_trim_offsets", values, offset_width);
+  rc = check_common("string_trim_offsets", values, offset_width);
   if (rc != ARX_OK) return rc;
   const bool takes_set = set_kind == ARX_TRIM_BYTES || set_kind == ARX_TRIM_CODEPOINTS;
   if (takes_set && (set_length < 0 || (set == nullptr && set_length > 0))) {
@@ -306,22 +301,11 @@ int arx_string_trim_offsets(const ArxBinarySpan* values, int offset_width, int s
   TrimSet trim_set;
   rc = make_set(set_kind, set, set_length, &trim_set);
   if (rc != ARX_OK) return rc;
-  hipStream_t st = as_stream(stream);
-  if (values->length == 0) {
-    *out_total_bytes = 0;
-    ARX_HIP(hipMemsetAsync(out_offsets, 0, static_cast<size_t>(offset_width), st));
-    return ARX_OK;
-  }
-  if (values->offsets == nullptr) {
-    set_error("string_trim_offsets: NULL offsets of values");
-    return ARX_INVALID;
-  }
-  rc = check_offsets_workspace("string_trim_offsets", ws, ws_bytes, values->length, offset_width);
-  if (rc != ARX_OK) return rc;
-  *out_total_bytes = 0;
-  const Column c = column_of(values, offset_width);
-  return offset_width == 4 ? trim_by_sides<int32_t>(sides, set_kind, c, trim_set, ws, out_offsets, out_total_bytes, st)
-                           : trim_by_sides<int64_t>(sides, set_kind, c, trim_set, ws, out_offsets, out_total_bytes, st);
+  return offsets_call("string_trim_offsets", "arx_string_slice_workspace_bytes", values, offset_width, ws, ws_bytes, out_offsets,
+                      out_total_bytes, "trimming a string array", as_stream(stream),
+                      [&](const Column& c, auto* lens, auto* src, unsigned long long* sums, hipStream_t st) {
+                        return trim_by_sides(sides, set_kind, c, trim_set, lens, src, sums, st);
+                      });
 }
 
 }  // extern "C"

@@ -1363,6 +1363,7 @@ enum {
   ARX_STRING_UNIT_BYTES = 0,
   ARX_STRING_UNIT_CODEPOINTS = 1
 };
+/* (ARX_STRING_PATH_*, ARX_REPLACE_PATH_* and ARX_COMPARE_PATH_* carry the same three values: 0 auto, 1 rows, 2 waves) */
 enum {
   ARX_STRING_PATH_AUTO = 0,
   ARX_STRING_PATH_ROWS = 1,

@@ -6,10 +6,12 @@ MI355X plus one column of 10^6 rows built from numpy buffers.  Both kernels are 
 compute.MATCH_SUBSTRING_PATH (1 = one lane per row, 2 = the lanes walk the bytes); large offsets go through the C ABI,
 since the mirror's Array does not carry them."""
 import ctypes as C
-import zlib
 
 import numpy as np
 import pytest
+
+from . import string_util
+from .string_util import c_buffers, path_set
 
 pa = pytest.importorskip("pyarrow")
 pc = pytest.importorskip("pyarrow.compute")
@@ -19,10 +21,12 @@ OP_CODE = {"match_substring": 0, "starts_with": 1, "ends_with": 2}
 LENGTHS = [0, 1, 63, 64, 65, 4097, 100_000]
 LDS_CAP = 1024          # kPatternLdsCap of csrc/match_substring.hip
 TILE = 4096             # kTileBytes: 256 lanes x 16 bytes
+SEED = 0x5B5
+KNOB = "MATCH_SUBSTRING_PATH"              # the global of arrow_amd.compute that selects the kernel form
 
 
 def rng_for(*key):
-    return np.random.default_rng([0x5B5, *[zlib.crc32(str(k).encode()) for k in key]])
+    return string_util.rng_for(SEED, *key)
 
 
 def pattern_of(m):
@@ -46,20 +50,6 @@ def column(rng, pat, n, null_p, typ):
     return pa.array([pool[i] for i in rng.integers(0, len(pool), n)], pa.binary(), mask=mask).cast(typ)
 
 
-class path_set:
-    """compute.MATCH_SUBSTRING_PATH for the length of a with block."""
-
-    def __init__(self, amd, path):
-        self.amd, self.path = amd, path
-
-    def __enter__(self):
-        self.saved = self.amd.compute.MATCH_SUBSTRING_PATH
-        self.amd.compute.MATCH_SUBSTRING_PATH = self.path
-
-    def __exit__(self, *exc):
-        self.amd.compute.MATCH_SUBSTRING_PATH = self.saved
-
-
 def check(amd, arr, pat, offset=0, ops=OPS, paths=(1, 2)):
     """Every op on both paths equals the reference (computed once per op) on arr.slice(offset)."""
     host = arr.slice(offset) if offset else arr
@@ -68,7 +58,7 @@ def check(amd, arr, pat, offset=0, ops=OPS, paths=(1, 2)):
     for op in ops:
         want = getattr(pc, op)(host, pat)
         for path in paths:
-            with path_set(amd, path):
+            with path_set(amd, KNOB, path):
                 got = getattr(amd.compute, op)(dev, pat)
             assert got.to_pyarrow().equals(want), (op, path, host.type, offset, len(host), pat[:20])
             assert got.null_count == want.null_count, (op, path)
@@ -158,22 +148,6 @@ def _one_long_row(amd):
 
 
 # ---------------------------------------------------------------- the C ABI directly
-def c_buffers(amd, arr, owidth):
-    """The device buffers of a (possibly sliced) binary array with offsets of `owidth` bytes and its ArxBinarySpan."""
-    from arrow_amd import _lib
-    from arrow_amd.array import to_device
-
-    vb, ob, db = arr.buffers()
-    odt = np.int32 if owidth == 4 else np.int64
-    offs = np.frombuffer(ob, dtype=odt)[: arr.offset + len(arr) + 1]
-    nbytes = int(offs[-1])
-    keep = [to_device(np.frombuffer(vb, dtype=np.uint8)[: (arr.offset + len(arr) + 7) // 8]) if vb is not None else None,
-            to_device(offs), to_device(np.frombuffer(db, dtype=np.uint8)[:nbytes] if db is not None and nbytes else np.zeros(0, np.uint8))]
-    span = _lib.ArxBinarySpan(keep[0].data_ptr() if keep[0] is not None else None, keep[1].data_ptr(), keep[2].data_ptr(),
-                              arr.offset, len(arr), arr.null_count if vb is not None else 0)
-    return span, keep, nbytes
-
-
 def c_match(amd, arr, owidth, op, pat, path, hint=None):
     """arx_match_substring on `arr`: the raw output bits as a bool array of len(arr)."""
     import torch
@@ -182,7 +156,7 @@ def c_match(amd, arr, owidth, op, pat, path, hint=None):
     from arrow_amd.array import to_device
 
     lib = _lib.get_lib()
-    span, keep, nbytes = c_buffers(amd, arr, owidth)
+    span, keep, nbytes = c_buffers(arr, owidth)
     n = len(arr)
     dpat = to_device(np.frombuffer(pat, dtype=np.uint8) if pat else np.zeros(0, np.uint8))
     out = to_device(np.full(((n + 63) // 64) * 8 + 8, 0xEE, np.uint8))
@@ -230,7 +204,7 @@ def _invalid_arguments(amd):
 
     lib = _lib.get_lib()
     arr = pa.array(["abc", "b"], pa.string())
-    span, keep, nbytes = c_buffers(amd, arr, 4)
+    span, keep, nbytes = c_buffers(arr, 4)
     dpat = to_device(np.frombuffer(b"b", dtype=np.uint8))
     out = to_device(np.full(16, 0xEE, np.uint8))
 
@@ -265,17 +239,17 @@ def _counters(amd):
     short = amd.Array.from_pyarrow(pa.array([bytes(r) for r in np.split(rng.integers(97, 100, 16 * 2000, dtype=np.uint8), 2000)]))
     wide = amd.Array.from_pyarrow(pa.array([bytes(r) for r in np.split(rng.integers(97, 100, 4096 * 64, dtype=np.uint8), 64)]))
     r0, b0 = count()
-    with path_set(amd, 1):
+    with path_set(amd, KNOB, 1):
         for op in OPS:
             getattr(amd.compute, op)(short, "ab")
     assert count() == (r0 + 3, b0)
-    with path_set(amd, 2):              # starts_with / ends_with and the empty pattern always take rows
+    with path_set(amd, KNOB, 2):              # starts_with / ends_with and the empty pattern always take rows
         for op in OPS:
             getattr(amd.compute, op)(short, "ab")
         amd.compute.match_substring(short, "")
     assert count() == (r0 + 6, b0 + 1)
     # auto: rows for a 16-byte-mean column, bytes for a 4 KiB-mean column
-    with path_set(amd, 0):
+    with path_set(amd, KNOB, 0):
         got_short = amd.compute.match_substring(short, "abcab")
         assert count() == (r0 + 7, b0 + 1)
         got_wide = amd.compute.match_substring(wide, "abcabcab")

@@ -8,12 +8,12 @@ MI355X plus one column pair of 10^6 rows built from numpy buffers.  Large offset
 launch counters go through the C ABI, since the mirror's Array carries no large offsets."""
 import ctypes as C
 import operator
-import zlib
 
 import numpy as np
 import pytest
 
-from .test_string_slice import c_buffers, sync
+from . import string_util
+from .string_util import c_buffers, path_set, sync
 
 pa = pytest.importorskip("pyarrow")
 pc = pytest.importorskip("pyarrow.compute")
@@ -26,24 +26,12 @@ ROW_COUNTER, WAVE_COUNTER = b"string_compare_row_launches", b"string_compare_wav
 PREFIXES = [0, 1, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2049]   # 1024 = one step of the wave form
 ALIGNMENTS = [0, 1, 7, 8, 15]
 LITERAL_SIZES = [0, 1, 16, 1024, 1025, 5000]                                        # 1024 = the LDS cap of a literal
+SEED = 0xC09A
+KNOB = "STRING_COMPARE_PATH"              # the global of arrow_amd.compute that selects the kernel form
 
 
 def rng_for(*key):
-    return np.random.default_rng([0xC09A, *[zlib.crc32(str(k).encode()) for k in key]])
-
-
-class path_set:
-    """compute.STRING_COMPARE_PATH for the length of a with block."""
-
-    def __init__(self, amd, path):
-        self.amd, self.path = amd, path
-
-    def __enter__(self):
-        self.saved = self.amd.compute.STRING_COMPARE_PATH
-        self.amd.compute.STRING_COMPARE_PATH = self.path
-
-    def __exit__(self, *exc):
-        self.amd.compute.STRING_COMPARE_PATH = self.saved
+    return string_util.rng_for(SEED, *key)
 
 
 def pattern(k, salt=0):
@@ -83,7 +71,7 @@ def check(amd, left, right, dleft, dright, what, paths=(ROWS, WAVES)):
     for name in OPS:
         want = getattr(pc, name)(left, right)
         for path in paths:
-            with path_set(amd, path):
+            with path_set(amd, KNOB, path):
                 got = getattr(amd.compute, name)(dleft, dright)
             same(got, want, (left, right), (name, path, what))
 

@@ -8,12 +8,12 @@ row over bytes that hold the pattern, the refused arguments and the int32 overfl
 
 The reference is never called with an empty pattern and unlimited replacements: it does not terminate."""
 import ctypes as C
-import zlib
 
 import numpy as np
 import pytest
 
-from .test_string_slice import c_buffers, same, sync
+from . import string_util
+from .string_util import c_buffers, path_set, same, sync
 
 pa = pytest.importorskip("pyarrow")
 pc = pytest.importorskip("pyarrow.compute")
@@ -24,24 +24,12 @@ AUTO, ROWS, WAVES = 0, 1, 2
 PATTERNS = {1: "a", 2: "ab", 8: "abcdefgh", 9: "aabaabaac", 17: "0123456789abcdefg"}   # by length; the 9 overlaps itself
 LONG = "".join(chr(65 + (i * 7 + i // 26) % 26) for i in range(1025))                   # 1025 bytes: past the LDS cap
 ROW_BYTES = [0, 1, 7, 8, 9, 15, 16, 17, 63, 64, 65, 1023, 1024, 1025, 4097]
+SEED = 0x4E91
+KNOB = "STRING_REPLACE_PATH"              # the global of arrow_amd.compute that selects the kernel form
 
 
 def rng_for(*key):
-    return np.random.default_rng([0x4E91, *[zlib.crc32(str(k).encode()) for k in key]])
-
-
-class path_set:
-    """compute.STRING_REPLACE_PATH for the length of a with block."""
-
-    def __init__(self, amd, path):
-        self.amd, self.path = amd, path
-
-    def __enter__(self):
-        self.saved = self.amd.compute.STRING_REPLACE_PATH
-        self.amd.compute.STRING_REPLACE_PATH = self.path
-
-    def __exit__(self, *exc):
-        self.amd.compute.STRING_REPLACE_PATH = self.saved
+    return string_util.rng_for(SEED, *key)
 
 
 def replacements(pattern):
@@ -68,7 +56,7 @@ def check(amd, host, dev, todo, paths=(ROWS, WAVES)):
             pattern, rep = pattern.encode(), rep.encode()
         want = pc.replace_substring(host, pattern, rep, max_replacements=cap)
         for path in paths:
-            with path_set(amd, path):
+            with path_set(amd, KNOB, path):
                 got = amd.compute.replace_substring(dev, pattern, rep, max_replacements=cap)
             same(got, want, host, (host.type, pattern[:20], rep[:20], cap, path, len(host)))
             assert got.type == dev.type
@@ -134,7 +122,7 @@ def _constructed(amd):
     arr = pa.array(rows, pa.string())
     dev = amd.Array.from_pyarrow(arr)
     for path in (ROWS, WAVES):
-        with path_set(amd, path):
+        with path_set(amd, KNOB, path):
             cp = amd.compute
             assert cp.replace_substring(dev, "aa", "b").to_pyarrow().to_pylist() == ["ba", "bb", "bba", "abababa", "a", "", "b", "bbb", "bbb"]
             assert cp.replace_substring(dev, "aba", "X").to_pyarrow().to_pylist()[3] == "XbX"
@@ -187,7 +175,7 @@ def _auto_and_counters(amd):
         want = pc.replace_substring(arr, "ab", "<ab>")
         for path, counter in ((ROWS, ROW_COUNTER), (WAVES, WAVE_COUNTER), (AUTO, auto_counter)):
             before = {c: lib.arx_get_counter(c) for c in (ROW_COUNTER, WAVE_COUNTER)}
-            with path_set(amd, path):
+            with path_set(amd, KNOB, path):
                 got = amd.compute.replace_substring(dev, "ab", "<ab>")
             same(got, want, arr, (path, len(arr)))
             for c in (ROW_COUNTER, WAVE_COUNTER):

@@ -10,10 +10,12 @@ One known departure from the reference: pc.binary_slice(arr, start >= 0, stop=No
 ("Negative buffer resize") from two rows on; those cases are checked against Python's b[start:] instead, and
 test_reference_binary_slice_without_stop_still_raises notices a pyarrow that no longer does."""
 import ctypes as C
-import zlib
 
 import numpy as np
 import pytest
+
+from . import string_util
+from .string_util import c_buffers, path_set, same, sync
 
 pa = pytest.importorskip("pyarrow")
 pc = pytest.importorskip("pyarrow.compute")
@@ -24,10 +26,12 @@ STOPS = [None, 0, 1, 3, 100, -1, -2, -100]
 BYTES, CODEPOINTS = 0, 1
 NO_STOP = 2**63 - 1
 ROW_COUNTER, WAVE_COUNTER = b"string_slice_row_launches", b"string_slice_wave_launches"
+SEED = 0x51CE
+KNOB = "STRING_SLICE_PATH"              # the global of arrow_amd.compute that selects the kernel form
 
 
 def rng_for(*key):
-    return np.random.default_rng([0x51CE, *[zlib.crc32(str(k).encode()) for k in key]])
+    return string_util.rng_for(SEED, *key)
 
 
 def row_pool():
@@ -43,29 +47,6 @@ def column(rng, n, null_p, typ, pool=None):
     return pa.array([pool[i] for i in rng.integers(0, len(pool), n)], pa.string(), mask=mask).cast(typ)
 
 
-class path_set:
-    """compute.STRING_SLICE_PATH for the length of a with block."""
-
-    def __init__(self, amd, path):
-        self.amd, self.path = amd, path
-
-    def __enter__(self):
-        self.saved = self.amd.compute.STRING_SLICE_PATH
-        self.amd.compute.STRING_SLICE_PATH = self.path
-
-    def __exit__(self, *exc):
-        self.amd.compute.STRING_SLICE_PATH = self.saved
-
-
-def same(got, want, host, what):
-    """The device result equals the reference's: rows, null count, offset 0, and no bitmap when the input has none."""
-    assert got.to_pyarrow().equals(want), what
-    assert got.null_count == want.null_count, what
-    assert got.offset == 0, what
-    if host.buffers()[0] is None:
-        assert got.validity is None, what
-
-
 def want_slice(host, start, stop):
     """The reference's slice of `host`; Python's b[start:] where the reference overflows (module docstring)."""
     if pa.types.is_binary(host.type) and stop is None and start >= 0:
@@ -79,7 +60,7 @@ def check_lengths(amd, host, dev, paths=(1, 2)):
     if pa.types.is_string(host.type):
         want = pc.utf8_length(host)
         for path in paths:
-            with path_set(amd, path):
+            with path_set(amd, KNOB, path):
                 same(amd.compute.utf8_length(dev), want, host, ("utf8_length", path, len(host)))
 
 
@@ -88,7 +69,7 @@ def check_slices(amd, host, dev, bounds, paths=(1, 2)):
     for start, stop in bounds:
         want = want_slice(host, start, stop)
         for path in (paths if utf8 else (0,)):
-            with path_set(amd, path):
+            with path_set(amd, KNOB, path):
                 got = (amd.compute.utf8_slice_codeunits if utf8 else amd.compute.binary_slice)(dev, start, stop)
             same(got, want, host, (host.type, start, stop, path, len(host)))
 
@@ -120,7 +101,7 @@ def _python_slicing(amd):
     dev = amd.Array.from_pyarrow(arr)
     for start, stop in ((0, 2), (1, None), (-3, None), (-3, -1), (2, 1), (-100, 3), (3, 100), (0, 0), (-1, -3), (5, -2)):
         for path in (1, 2):
-            with path_set(amd, path):
+            with path_set(amd, KNOB, path):
                 got = amd.compute.utf8_slice_codeunits(dev, start, stop).to_pylist()
             assert got == [s[start:stop] for s in rows], (start, stop, path)
         assert pc.utf8_slice_codeunits(arr, start, stop).to_pylist() == [s[start:stop] for s in rows]
@@ -228,28 +209,6 @@ def _mirror(amd):
 
 
 # ---------------------------------------------------------------- the C ABI directly
-def c_buffers(arr, owidth):
-    """The device buffers of a (possibly sliced) binary array with offsets of `owidth` bytes and its ArxBinarySpan."""
-    from arrow_amd import _lib
-    from arrow_amd.array import to_device
-
-    vb, ob, db = arr.buffers()
-    offs = np.frombuffer(ob, dtype=np.int32 if owidth == 4 else np.int64)[: arr.offset + len(arr) + 1]
-    nbytes = int(offs[-1])
-    keep = [to_device(np.frombuffer(vb, dtype=np.uint8)[: (arr.offset + len(arr) + 7) // 8]) if vb is not None else None,
-            to_device(offs), to_device(np.frombuffer(db, dtype=np.uint8)[:nbytes] if db is not None and nbytes else np.zeros(0, np.uint8))]
-    span = _lib.ArxBinarySpan(keep[0].data_ptr() if keep[0] is not None else None, keep[1].data_ptr(), keep[2].data_ptr(),
-                              arr.offset, len(arr), arr.null_count if vb is not None else 0)
-    return span, keep, nbytes
-
-
-def sync(t):
-    if t.is_cuda:
-        import torch
-
-        torch.cuda.synchronize()
-
-
 def c_length(amd, arr, owidth, unit, path, hint=None):
     """arx_string_length on `arr`: the raw lengths; the 0xEE guard word after them survives."""
     from arrow_amd import _lib
@@ -426,7 +385,7 @@ def _counters(amd):
     wide_h = pa.array([bytes(r).decode() for r in np.split(rng.integers(97, 100, 4096 * 16, dtype=np.uint8), 16)])
     short, wide = amd.Array.from_pyarrow(short_h), amd.Array.from_pyarrow(wide_h)
     r0, w0 = count()
-    with path_set(amd, 0):
+    with path_set(amd, KNOB, 0):
         got = amd.compute.utf8_length(short)
         assert count() == (r0 + 1, w0)
         same(got, pc.utf8_length(short_h), short_h, "auto short length")
@@ -440,14 +399,14 @@ def _counters(amd):
         assert count() == (r0 + 2, w0 + 2)
         same(got, pc.utf8_slice_codeunits(wide_h, 5, -2), wide_h, "auto wide slice")
     for path in (0, 1, 2):                                   # byte units walk no codepoints
-        with path_set(amd, path):
+        with path_set(amd, KNOB, path):
             amd.compute.binary_length(wide)
             amd.compute.binary_length(short)
             amd.compute.binary_slice(amd.Array.from_pyarrow(wide_h.cast(pa.binary())), 1, 7)
     assert count() == (r0 + 2, w0 + 2)
-    with path_set(amd, 2):
+    with path_set(amd, KNOB, 2):
         amd.compute.utf8_length(short)
-    with path_set(amd, 1):
+    with path_set(amd, KNOB, 1):
         amd.compute.utf8_slice_codeunits(wide, 0, 2)
     assert count() == (r0 + 3, w0 + 3)
 

@@ -10,12 +10,12 @@ input"; the device stops trimming there and returns the row.  Those rows are che
 rule of csrc/string_trim.hip restated, and test_reference_trim_of_invalid_utf8_still_raises notices a pyarrow that no
 longer raises."""
 import ctypes as C
-import zlib
 
 import numpy as np
 import pytest
 
-from .test_string_slice import c_buffers, same, sync
+from . import string_util
+from .string_util import c_buffers, same, sync
 
 pa = pytest.importorskip("pyarrow")
 pc = pytest.importorskip("pyarrow.compute")
@@ -32,10 +32,11 @@ MIXED = "xé 　😀"                                             # 1-, 2-, 1-, 
 WS = {9, 10, 11, 12, 13, 0x1C, 0x1D, 0x1E, 0x1F, 0x20, 0x85, 0xA0, 0x1680, *range(0x2000, 0x200B), 0x2028, 0x2029, 0x202F, 0x205F,
       0x3000}
 ASCII_WS_BYTES = {9, 10, 11, 12, 13, 32}
+SEED = 0x7219
 
 
 def rng_for(*key):
-    return np.random.default_rng([0x7219, *[zlib.crc32(str(k).encode()) for k in key]])
+    return string_util.rng_for(SEED, *key)
 
 
 # ---------------------------------------------------------------- the unit rule of csrc/string_trim.hip
