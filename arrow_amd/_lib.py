@@ -25,6 +25,9 @@ ARX_DEVICE_ERROR = -100
 ABI_VERSION = 5  # ARX_ABI_VERSION of include/arrow_amd.h
 
 FILTER_DROP, FILTER_EMIT_NULL = 0, 1
+JOIN_COLUMN, JOIN_LITERAL, JOIN_NULL = 0, 1, 2          # ARX_JOIN_* operand kinds
+JOIN_NULL_HANDLING = {"emit_null": 0, "skip": 1, "replace": 2}
+JOIN_MAX_OPERANDS = 32                                  # ARX_JOIN_MAX_OPERANDS, the separator included
 SORT_ASCENDING, SORT_DESCENDING = 0, 1
 NULLS_AT_START, NULLS_AT_END = 0, 1
 
@@ -102,6 +105,18 @@ class ArxBinarySpan(C.Structure):
         ("offset", C.c_int64),
         ("length", C.c_int64),
         ("null_count", C.c_int64),
+    ]
+
+
+class ArxJoinOperand(C.Structure):
+    """struct ArxJoinOperand of include/arrow_amd.h (one operand of binary_join_element_wise)."""
+
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("reserved", C.c_int32),
+        ("column", ArxBinarySpan),
+        ("literal", C.c_void_p),
+        ("literal_length", C.c_int64),
     ]
 
 
@@ -245,6 +260,10 @@ SIGNATURES = {
     "arx_replace_substring_workspace_bytes": (_sz, [_i64, _int]),
     "arx_replace_substring_offsets": (_int, [_bspan, _int, _p, _i64, _i64, _i64, _i64, _int, _p, _sz, _p, C.POINTER(_i64), _p]),
     "arx_replace_substring_data": (_int, [_bspan, _int, _p, _i64, _p, _i64, _i64, _int, _p, _sz, _p, _i64, _p, _p]),
+    "arx_binary_join_workspace_bytes": (_sz, [_i64, _int]),
+    "arx_binary_join_offsets": (_int, [C.POINTER(ArxJoinOperand), _int, _i64, _int, _int, _i64, _p, _sz, _p, _p, C.POINTER(_i64),
+                                       C.POINTER(_i64), _p]),
+    "arx_binary_join_data": (_int, [C.POINTER(ArxJoinOperand), _int, _i64, _int, _int, _p, _i64, _p, _i64, _p, _p]),
     "arx_compare_binary": (_int, [_int, _bspan, _bspan, _int, _p, _i64, _i64, _int, _p, _p]),
     "arx_if_else": (_int, [_int, _span, _span, _p, _span, _p, _i64, _p, _p, _p]),
     "arx_temporal_component": (_int, [_int, _int, _span, _i64, _int, _int, _p, _p, _p]),

@@ -120,6 +120,17 @@ class ReplaceSubstringOptions(FunctionOptions):
         self.max_replacements = None if max_replacements is None else int(max_replacements)
 
 
+class JoinOptions(FunctionOptions):
+    """api_scalar.h JoinOptions: null_handling ("emit_null": a null value makes the row null, "skip": it is left out with
+    one separator, "replace": it contributes `null_replacement`, str, UTF-8 encoded, or bytes)."""
+
+    def __init__(self, null_handling="emit_null", null_replacement=""):
+        if null_handling not in _lib.JOIN_NULL_HANDLING:
+            raise ValueError(f'"{null_handling}" is not a valid null handling')
+        self.null_handling = null_handling
+        self.null_replacement = null_replacement
+
+
 class DayOfWeekOptions(FunctionOptions):
     """api_scalar.h DayOfWeekOptions: count_from_zero (Monday = 0 rather than 1 at the defaults) and week_start, the ISO
     weekday (Monday = 1 .. Sunday = 7) the numbering starts at."""
@@ -637,12 +648,16 @@ def _exec_array_sort_indices_bool(args, options):
 class Kernel:
     """arrow::compute::Kernel twin: a signature (tuple of DataType or None = any) + exec."""
 
-    def __init__(self, in_types, exec_fn, out_type=None):
+    def __init__(self, in_types, exec_fn, out_type=None, is_varargs: bool = False):
         self.in_types = tuple(in_types)
         self.exec = exec_fn
         self.out_type = out_type
+        self.is_varargs = is_varargs    # KernelSignature::is_varargs: the last in_type takes every further argument
 
     def matches(self, types) -> bool:
+        if getattr(self, "is_varargs", False):         # (HashAggregateKernel borrows this method and has no such field)
+            want = self.in_types + self.in_types[-1:] * (len(types) - len(self.in_types))
+            return len(types) >= len(self.in_types) and all(w is None or (callable(w) and w(t)) or w == t for w, t in zip(want, types))
         if len(types) != len(self.in_types):
             return False
         return all(want is None or (callable(want) and want(t)) or want == t
@@ -652,10 +667,11 @@ class Kernel:
 class Function:
     SCALAR, VECTOR, SCALAR_AGGREGATE, HASH_AGGREGATE, META = range(5)  # function.h:146-168
 
-    def __init__(self, name: str, kind: int, arity: int, default_options=None, meta_impl=None):
+    def __init__(self, name: str, kind: int, arity: int, default_options=None, meta_impl=None, is_varargs: bool = False):
         self.name = name
         self.kind = kind
-        self.arity = arity
+        self.arity = arity              # Arity::VarArgs(arity) when is_varargs: at least that many
+        self.is_varargs = is_varargs
         self.default_options = default_options
         self.kernels: list[Kernel] = []
         self._meta_impl = meta_impl
@@ -680,7 +696,10 @@ class Function:
             f"Function '{self.name}' has no kernel matching input types ({names})")
 
     def execute(self, args, options=None):
-        if len(args) != self.arity:
+        if self.is_varargs and len(args) < self.arity:      # function.cc CheckArity
+            raise ArrowInvalid(f"VarArgs function '{self.name}' needs at least {self.arity} arguments but only "
+                               f"{len(args)} passed")
+        if not self.is_varargs and len(args) != self.arity:
             raise ArrowInvalid(f"Function '{self.name}' accepts {self.arity} arguments but "
                                f"{len(args)} passed")
         options = options if options is not None else self.default_options
@@ -1106,6 +1125,11 @@ def _build_registry() -> FunctionRegistry:
     f = Function("replace_substring", Function.SCALAR, 1)
     for t in (type_from_name("string"), type_from_name("binary")):
         f.add_kernel(Kernel((t,), _exec_replace_substring))
+    reg.add_function(f)
+    # binary_join_element_wise(v_1, ..., v_k, separator) of utf8 / binary operands of one type (csrc/string_join.hip)
+    f = Function("binary_join_element_wise", Function.SCALAR, 1, JoinOptions(), is_varargs=True)
+    for t in (type_from_name("string"), type_from_name("binary")):
+        f.add_kernel(Kernel((t,), _exec_binary_join_element_wise, t, is_varargs=True))
     reg.add_function(f)
     # the twelve trims of utf8 rows (csrc/string_trim.hip)
     for name in _TRIMS:
@@ -2761,6 +2785,79 @@ def replace_substring(values: Array, pattern, replacement, *, max_replacements=N
     row stays null and holds no bytes.  The empty pattern raises ArrowNotImplementedError (there is no CPU fallback); a
     result past int32 offsets raises ArrowInvalid ("offset overflow").  The result stays on the device."""
     return _call_string_function("replace_substring", values, ReplaceSubstringOptions(pattern, replacement, max_replacements), "x", "y")
+
+
+# --------------------------------------------------------------------------- binary_join_element_wise
+# compute::BinaryJoinElementWise under JoinOptions (scalar_string_ascii.cc): csrc/string_join.hip.  Every operand, the
+# separator (the last) included, is an Array, a valid Scalar (a literal) or a null Scalar.  arx_binary_join_offsets makes
+# the offsets, the validity and the null count from the operands' offsets and validity bits, arx_binary_join_data gathers
+# the bytes.
+def _exec_binary_join_element_wise(args, options):
+    name = "binary_join_element_wise"
+    options = options if options is not None else JoinOptions()
+    arrays = [a for a in args if isinstance(a, Array)]
+    if not arrays:
+        raise ArrowNotImplementedError(f"arrow_amd: {name} of scalars only on the device path")
+    n, dev, out_type = arrays[0].length, arrays[0].device, arrays[0].type
+    if any(a.length != n for a in arrays):
+        raise ArrowInvalid("Array arguments must all be the same length")
+    replacement = _literal_operand(name, "null_replacement must be", options.null_replacement)
+    parts = [replacement] + [_literal_operand(name, f"a {a.type.name} scalar must hold", a.value) if isinstance(a, Scalar) and a.is_valid
+                             else b"" for a in args]
+    literals = _device_literal(dev, *parts)                         # copied to the device once per call
+    at = literals.data_ptr() + len(replacement)
+    operands = (_lib.ArxJoinOperand * len(args))()
+    for op, a, part in zip(operands, args, parts[1:]):
+        if isinstance(a, Array):
+            op.kind, op.column = _lib.JOIN_COLUMN, a.binary_span()
+        elif a.is_valid:
+            op.kind, op.literal, op.literal_length = _lib.JOIN_LITERAL, at if part else None, len(part)
+        else:
+            op.kind = _lib.JOIN_NULL
+        at += len(part)
+    mode = _lib.JOIN_NULL_HANDLING[options.null_handling]
+    lib, stream = _lib_and_stream(dev)
+    out_offsets = alloc((n + 1) * 4, dev)
+    out_valid = alloc(max(1, (n + 63) // 64) * 8, dev)
+    ws = _workspace(dev, lib.arx_binary_join_workspace_bytes(n, 4), "string_slice")
+    total, nulls = C.c_int64(0), C.c_int64(0)
+    with tracing.span("arx_binary_join_offsets"):
+        check(lib.arx_binary_join_offsets(operands, len(args), n, 4, mode, len(replacement), ws.data_ptr(), ws.numel(),
+                                          out_offsets.data_ptr(), out_valid.data_ptr(), C.byref(nulls), C.byref(total), stream))
+    out_data = alloc(total.value, dev)
+    with tracing.span("arx_binary_join_data"):
+        check(lib.arx_binary_join_data(operands, len(args), n, 4, mode, literals.data_ptr() if replacement else None, len(replacement),
+                                       out_offsets.data_ptr(), total.value, out_data.data_ptr(), stream))
+    return Array(out_type, n, [out_valid if nulls.value else None, out_offsets, out_data], nulls.value, 0)
+
+
+def binary_join_element_wise(*operands, null_handling: str = "emit_null", null_replacement="") -> Array:
+    """compute::BinaryJoinElementWise under JoinOptions: row i of the result is operands[0][i], sep[i], operands[1][i], ...
+    with the LAST operand as the separator.  An operand is an Array (utf8 or binary, all of one type and length), a str
+    (a utf8 literal), bytes (a binary literal), a Scalar or None (a null literal of the arrays' type); at least one is an
+    Array.  A null separator makes the row null; null_handling says what a null value does: "emit_null" (the row is null),
+    "skip" (it is left out with one separator) or "replace" (it contributes `null_replacement`).  Bytes are bytes.  Not the
+    reference's: under "skip" a row whose values are all null is the empty string, where Arrow 25.0.0 drops the row.  More
+    than 32 operands raise ArrowNotImplementedError (there is no CPU fallback); a result past int32 offsets raises
+    ArrowInvalid ("offset overflow").  The result stays on the device and has no bitmap when no row is null."""
+    from .array import type_from_name
+
+    name = "binary_join_element_wise"
+    arrays = [a for a in operands if isinstance(a, Array)]
+    if not arrays:
+        raise TypeError(f"{name}: at least one operand must be an arrow_amd.Array")
+    args = []
+    for a in operands:
+        if isinstance(a, str):
+            a = Scalar(a, type_from_name("string"), True)
+        elif isinstance(a, (bytes, bytearray, memoryview)):
+            a = Scalar(bytes(a), type_from_name("binary"), True)
+        elif a is None:
+            a = Scalar(None, arrays[0].type, False)
+        elif not isinstance(a, (Array, Scalar)):
+            raise TypeError(f"{name}: an operand must be an Array, str, bytes, Scalar or None, not {type(a).__name__}")
+        args.append(a)
+    return call_function(name, args, JoinOptions(null_handling, null_replacement))
 
 
 # --------------------------------------------------------------------------- string trimming

@@ -106,6 +106,7 @@ namespace {
 #include "plugin/string_trim.inc"
 #include "plugin/string_compare.inc"
 #include "plugin/string_replace.inc"
+#include "plugin/string_join.inc"
 #include "plugin/unary_arith.inc"
 #include "plugin/grouper_chain.inc"
 #include "plugin/acero_node.inc"

@@ -90,6 +90,7 @@ CounterTable string_slice_counters();
 CounterTable string_trim_counters();
 CounterTable string_compare_counters();
 CounterTable string_replace_counters();
+CounterTable string_join_counters();
 CounterTable unary_arith_counters();
 
 #define ARX_HIP(call)                                          \

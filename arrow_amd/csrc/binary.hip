@@ -152,9 +152,9 @@ __global__ __launch_bounds__(1024) void bin_scan_blocks_kernel(long long* sums, 
   if (tid == 0) sums[nblocks] = carry_s;
 }
 
-// lens (in out_offsets) -> exclusive offsets, per workgroup of 4096 slots
+// lens (out_offsets itself, or the producer's own array) -> exclusive offsets, per workgroup of 4096 slots
 template <typename O>
-__global__ __launch_bounds__(kBlock) void bin_offsets_kernel(O* __restrict__ out_offsets, int64_t length,
+__global__ __launch_bounds__(kBlock) void bin_offsets_kernel(const O* lens, O* out_offsets, int64_t length,
                                                              const long long* __restrict__ block_base) {
   __shared__ uint64_t wave_tot[kWavesPerBlock];
   const int tid = threadIdx.x;
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(kBlock) void bin_offsets_kernel(O* __restrict__ out
 #pragma unroll
   for (int k = 0; k < 16; ++k) {
     const int64_t i = base + tid * 16 + k;
-    v[k] = i < length ? static_cast<uint64_t>(out_offsets[i]) : 0u;
+    v[k] = i < length ? static_cast<uint64_t>(lens[i]) : 0u;
     mine += v[k];
   }
   const uint64_t incl = wave_inclusive_scan_u64(mine);
@@ -196,17 +196,6 @@ constexpr int kBinBatch = 2048;    // rows staged per pass
 
 // (SHIFT: the entries are list offsets in ELEMENTS of 2^SHIFT bytes — a list whose values are fixed-width and free of nulls
 //  is a binary array with offsets scaled by the element width; 0 for utf8 / binary.  Positions below are bytes.)
-template <typename O>
-__device__ __forceinline__ int64_t bin_row_of(const O* __restrict__ out_offsets, int64_t m, int64_t pos, int shift) {
-  // largest r in [0, m) with out_offsets[r] <= pos  (pos < out_offsets[m])
-  int64_t lo = 0, hi = m;  // invariant: out_offsets[lo] <= pos < out_offsets[hi]
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if ((static_cast<int64_t>(out_offsets[mid]) << shift) <= pos) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 template <typename O>
 __global__ __launch_bounds__(kBlock) void bin_copy_kernel(const uint8_t* __restrict__ data,
                                                           const O* __restrict__ src_start,
@@ -298,7 +287,8 @@ size_t bin_workspace_bytes(int64_t num_indices, int offset_width) {
 }
 
 template <typename O>
-int bin_scan_lengths(O* out_offsets, int64_t length, long long* sums, const char* what, int64_t* out_total, hipStream_t st) {
+int bin_scan_lengths(O* out_offsets, int64_t length, long long* sums, const char* what, int64_t* out_total, hipStream_t st,
+                     const O* lens) {
   const int64_t nblocks = ceil_div(length, kBinRows);
   hipLaunchKernelGGL(bin_scan_blocks_kernel, dim3(1), dim3(1024), 0, st, sums, nblocks);
   ARX_CHECK_LAUNCH("bin_scan_blocks_kernel");
@@ -310,13 +300,14 @@ int bin_scan_lengths(O* out_offsets, int64_t length, long long* sums, const char
     set_error("offset overflow while %s: %lld bytes do not fit int32 offsets", what, total);
     return ARX_INVALID;
   }
-  hipLaunchKernelGGL(bin_offsets_kernel<O>, dim3(static_cast<unsigned>(nblocks)), dim3(kBlock), 0, st, out_offsets, length, sums);
+  hipLaunchKernelGGL(bin_offsets_kernel<O>, dim3(static_cast<unsigned>(nblocks)), dim3(kBlock), 0, st,
+                     lens != nullptr ? lens : out_offsets, out_offsets, length, sums);
   ARX_CHECK_LAUNCH("bin_offsets_kernel");
   *out_total = total;
   return ARX_OK;
 }
-template int bin_scan_lengths<int32_t>(int32_t*, int64_t, long long*, const char*, int64_t*, hipStream_t);
-template int bin_scan_lengths<int64_t>(int64_t*, int64_t, long long*, const char*, int64_t*, hipStream_t);
+template int bin_scan_lengths<int32_t>(int32_t*, int64_t, long long*, const char*, int64_t*, hipStream_t, const int32_t*);
+template int bin_scan_lengths<int64_t>(int64_t*, int64_t, long long*, const char*, int64_t*, hipStream_t, const int64_t*);
 
 template <typename O>
 int bin_copy_rows(const uint8_t* data, const O* src_start, const O* out_offsets, int64_t rows, int64_t copy_bytes, uint8_t* out_data,

@@ -225,8 +225,8 @@ Status GuardAggregateKernels(cp::Function* fn, int num_stock) {
 
 // the functions whose kernel lists the shim appends to — and the string-search siblings of match_substring, the
 // temporal siblings of year .. nanosecond and the nearest string siblings of the lengths, slices and trims (replace_slice,
-// reverse, case mapping, padding, swapcase / capitalize / title, replace_substring_regex beside replace_substring, and
-// round_binary beside round), to
+// reverse, case mapping, padding, swapcase / capitalize / title, replace_substring_regex beside replace_substring,
+// binary_join and binary_repeat beside binary_join_element_wise, and round_binary beside round), to
 // which it adds nothing (every kernel of theirs is the reference's, so every one gets a guard): a device-resident input is
 // refused by name instead of being read by a CPU kernel
 const char* const kGuardedFunctions[] = {
@@ -244,6 +244,7 @@ const char* const kGuardedFunctions[] = {
     "utf8_rtrim_whitespace", "ascii_trim", "ascii_ltrim", "ascii_rtrim", "utf8_trim", "utf8_ltrim", "utf8_rtrim",
     "ascii_lpad", "ascii_rpad", "ascii_center", "utf8_lpad", "utf8_rpad", "utf8_center", "ascii_swapcase", "ascii_capitalize",
     "ascii_title", "utf8_swapcase", "utf8_capitalize", "utf8_title", "replace_substring", "replace_substring_regex",
+    "binary_join_element_wise", "binary_join", "binary_repeat",
     "negate", "negate_checked", "abs", "abs_checked", "sign", "floor", "ceil", "trunc", "round", "round_to_multiple", "round_binary"};
 
 // before the shim registers anything: how many kernels of each guarded function are the reference's

@@ -345,6 +345,7 @@ Status RegisterAll() {
   ARROW_RETURN_NOT_OK(RegisterStringTrim(reg));    // the twelve {ascii,utf8}_{,l,r}trim{,_whitespace} (plugin/string_trim.inc)
   ARROW_RETURN_NOT_OK(RegisterStringCompare(reg));   // equal .. less_equal of utf8 / binary and their large forms (plugin/string_compare.inc)
   ARROW_RETURN_NOT_OK(RegisterStringReplace(reg));   // replace_substring of utf8 / binary and their large forms (plugin/string_replace.inc)
+  ARROW_RETURN_NOT_OK(RegisterStringJoin(reg));   // binary_join_element_wise of utf8 / binary and their large forms (plugin/string_join.inc)
   ARROW_RETURN_NOT_OK(RegisterUnaryArith(reg));   // negate .. trunc, round, round_to_multiple of the numeric types (plugin/unary_arith.inc)
   // the reference's kernels of the functions extended above refuse device-resident arrays instead of reading them
   ARROW_RETURN_NOT_OK(InstallDeviceGuards(reg, stock_kernel_counts));

@@ -3,7 +3,8 @@
 // staging of a literal operand, the window walk that finds a pattern's next match in a row.  Host side: the view of a
 // values column, the grids of a one-lane-per-row and a one-wave-per-row launch, the choice between the two forms, the
 // offset type of a call from its offset_width, the argument checks of the C entry points, and offsets_call: the frame of
-// the first of the two calls that make a variable-length result (slices, trims, replace_substring).
+// the first of the two calls that make a variable-length result (slices, trims, replace_substring), over offsets_frame,
+// which serves a call of several operands (string_join.hip).
 #pragma once
 #include "binary_scan_copy.h"
 
@@ -202,34 +203,44 @@ inline int check_offsets_arguments(const char* who, const ArxBinarySpan* values,
   }
   return ARX_OK;
 }
+// offsets_frame is that rest for `length` rows of any number of operands (arx_binary_join_offsets has k + 1 of them, its
+// own checks done): `produce(out, second, sums, stream)` with O* out = out_offsets and O* second = the workspace's second
+// part.  lengths_in_ws: the producer keeps the lengths in `second` instead of out_offsets, which then stays untouched
+// when the total is refused.
 template <typename F>
-int offsets_call(const char* who, const char* sizing, const ArxBinarySpan* values, int offset_width, void* ws, size_t ws_bytes,
-                 void* out_offsets, int64_t* out_total_bytes, const char* what, hipStream_t st, F&& produce) {
-  int rc = check_common(who, values, offset_width);   // (again, where the entry point's own checks ran it in their place)
-  if (rc != ARX_OK) return rc;
-  if (values->length == 0) {
+int offsets_frame(const char* who, const char* sizing, int64_t length, int offset_width, void* ws, size_t ws_bytes, void* out_offsets,
+                  int64_t* out_total_bytes, const char* what, bool lengths_in_ws, hipStream_t st, F&& produce) {
+  if (length == 0) {
     *out_total_bytes = 0;
     ARX_HIP(hipMemsetAsync(out_offsets, 0, static_cast<size_t>(offset_width), st));
     return ARX_OK;
   }
-  if (values->offsets == nullptr) {
-    set_error("%s: NULL offsets of values", who);
-    return ARX_INVALID;
-  }
-  rc = check_offsets_workspace(who, sizing, ws, ws_bytes, values->length, offset_width);
+  const int rc = check_offsets_workspace(who, sizing, ws, ws_bytes, length, offset_width);
   if (rc != ARX_OK) return rc;
   *out_total_bytes = 0;
-  const Column c = column_of(values, offset_width);
   return with_offset_type(offset_width, [&](auto o) {
     using O = decltype(o);
     auto* sums = static_cast<unsigned long long*>(ws);
-    O* src = reinterpret_cast<O*>(static_cast<uint8_t*>(ws) + bin_sums_bytes(c.n));
-    O* lens = static_cast<O*>(out_offsets);
-    ARX_HIP(hipMemsetAsync(sums, 0, bin_sums_bytes(c.n), st));
-    const int launched = produce(c, lens, src, sums, st);
+    O* second = reinterpret_cast<O*>(static_cast<uint8_t*>(ws) + bin_sums_bytes(length));
+    O* out = static_cast<O*>(out_offsets);
+    ARX_HIP(hipMemsetAsync(sums, 0, bin_sums_bytes(length), st));
+    const int launched = produce(out, second, sums, st);
     if (launched != ARX_OK) return launched;
-    return bin_scan_lengths<O>(lens, c.n, reinterpret_cast<long long*>(sums), what, out_total_bytes, st);
+    return bin_scan_lengths<O>(out, length, reinterpret_cast<long long*>(sums), what, out_total_bytes, st, lengths_in_ws ? second : nullptr);
   });
+}
+template <typename F>
+int offsets_call(const char* who, const char* sizing, const ArxBinarySpan* values, int offset_width, void* ws, size_t ws_bytes,
+                 void* out_offsets, int64_t* out_total_bytes, const char* what, hipStream_t st, F&& produce) {
+  const int rc = check_common(who, values, offset_width);   // (again, where the entry point's own checks ran it in their place)
+  if (rc != ARX_OK) return rc;
+  if (values->length > 0 && values->offsets == nullptr) {
+    set_error("%s: NULL offsets of values", who);
+    return ARX_INVALID;
+  }
+  const Column c = column_of(values, offset_width);
+  return offsets_frame(who, sizing, c.n, offset_width, ws, ws_bytes, out_offsets, out_total_bytes, what, false, st,
+                       [&](auto* lens, auto* src, unsigned long long* sums, hipStream_t s) { return produce(c, lens, src, sums, s); });
 }
 
 }  // namespace arx

@@ -1466,6 +1466,70 @@ int arx_replace_substring_data(const ArxBinarySpan* values, int offset_width, co
                                const void* replacement, int64_t replacement_length, int64_t max_replacements, int path,
                                const void* ws, size_t ws_bytes, const void* out_offsets, int64_t total_bytes, void* out_data,
                                void* stream);
+/* binary_join_element_wise(v_1, ..., v_k, separator) of utf8 / binary rows — the reference's BinaryJoinElementWise under
+ * JoinOptions{null_handling, null_replacement} (compute/kernels/scalar_string_ascii.cc; csrc/string_join.hip).  Bytes are
+ * bytes: no UTF-8 awareness, '\0' and 0xff are ordinary bytes.  Output row i is v_1[i], separator[i], v_2[i], ...,
+ * v_k[i]; the output type is the operands' (offset_width 4: utf8 / binary, 8: the large forms, one for all operands).
+ * Outputs start at offset 0.
+ * operands: a HOST array of num_operands descriptors, read before the call returns; the LAST one is the separator, the
+ * others the values in order.  kind ARX_JOIN_COLUMN: `column`, a span of `length` rows at its own offset;
+ * ARX_JOIN_LITERAL: the same literal_length >= 0 bytes at the DEVICE pointer `literal` in every row, alive until the
+ * stream reaches the call's end; ARX_JOIN_NULL: null in every row.  1 <= num_operands <= ARX_JOIN_MAX_OPERANDS = 32,
+ * the separator included (the descriptors travel to the kernels by value: 32 x 40 bytes of the 4 KiB of kernel
+ * arguments); more is ARX_NOT_IMPLEMENTED, naming the count and the cap, with nothing launched.
+ * A null separator makes the row null under every null_handling.  ARX_JOIN_EMIT_NULL: a null value makes the row null.
+ * ARX_JOIN_REPLACE: a null value contributes the null_replacement_length bytes at the DEVICE pointer null_replacement.
+ * ARX_JOIN_SKIP: a null value is left out together with one separator: the values kept are joined by the separator
+ * between neighbours only (no value at all: the empty string).  A null output row has length 0; the bytes of a null input row are never read, whatever its
+ * offsets span.
+ * NOT the reference's: under ARX_JOIN_SKIP a row whose values are all null and whose separator is valid is the empty
+ * string, valid.  The reference (Arrow 25.0.0) drops such a row from its result, which comes back shorter than its
+ * inputs.
+ * arx_binary_join_offsets: step one.  It reads the operands' offsets and validity bits and no data byte.  ws:
+ * arx_binary_join_workspace_bytes(length, offset_width) device bytes, 8-byte aligned.  out_offsets: length + 1 entries
+ * of offset_width bytes, the result's offsets; *out_total_bytes = their last entry.  out_validity: ceil(length / 64)
+ * 64-bit words, bit i = row i of the result is valid, 0 past the end; *out_null_count (host) = the null rows, so the
+ * caller can drop the bitmap when it is 0.  Row lengths are computed in 64 bits; a total that does not fit int32 offsets
+ * (offset_width 4) is ARX_INVALID "offset overflow while joining ..." with out_offsets untouched (the reference raises
+ * ArrowCapacityError).  Synchronous (one wait: the total and the null count are read back).
+ * arx_binary_join_data: step two, writes total_bytes bytes into out_data with the same operands, null_handling,
+ * null_replacement and out_offsets; it takes no workspace.  A workgroup owns 16 KiB of consecutive output bytes, so the
+ * work does not depend on how the bytes are spread over the rows.  A load touches only aligned 8-byte pieces that hold
+ * at least one referenced byte of a valid row or of a literal.  Asynchronous.
+ * ARX_INVALID, with nothing launched or written, for NULL operands / out_offsets / out_validity / out_null_count /
+ * out_total_bytes / out_data, num_operands < 1, a kind outside the three, an operand column whose length is not
+ * `length`, a negative length, literal_length, null_replacement_length or total_bytes, an offset_width other than 4 or
+ * 8, a null_handling outside the three values, a NULL literal or null_replacement with a positive length, for length > 0
+ * NULL offsets of a column, and a ws that is NULL, unaligned or too small.  length == 0 succeeds and launches nothing;
+ * the offsets call then writes out_offsets[0] = 0, *out_total_bytes = 0 and *out_null_count = 0, the data call nothing.
+ * arx_get_counter("string_join_launches") counts the launches of the two kernels (one per call that has work). */
+enum {
+  ARX_JOIN_COLUMN = 0,
+  ARX_JOIN_LITERAL = 1,
+  ARX_JOIN_NULL = 2
+};
+enum {   /* arrow::compute::JoinOptions::NullHandlingBehavior */
+  ARX_JOIN_EMIT_NULL = 0,
+  ARX_JOIN_SKIP = 1,
+  ARX_JOIN_REPLACE = 2
+};
+enum {
+  ARX_JOIN_MAX_OPERANDS = 32
+};
+typedef struct ArxJoinOperand {
+  int32_t kind;             /* ARX_JOIN_* */
+  int32_t reserved;         /* 0 */
+  ArxBinarySpan column;     /* ARX_JOIN_COLUMN */
+  const void* literal;      /* ARX_JOIN_LITERAL: device pointer */
+  int64_t literal_length;
+} ArxJoinOperand;
+size_t arx_binary_join_workspace_bytes(int64_t length, int offset_width);
+int arx_binary_join_offsets(const ArxJoinOperand* operands, int num_operands, int64_t length, int offset_width, int null_handling,
+                            int64_t null_replacement_length, void* ws, size_t ws_bytes, void* out_offsets, void* out_validity,
+                            int64_t* out_null_count, int64_t* out_total_bytes, void* stream);
+int arx_binary_join_data(const ArxJoinOperand* operands, int num_operands, int64_t length, int offset_width, int null_handling,
+                         const void* null_replacement, int64_t null_replacement_length, const void* out_offsets,
+                         int64_t total_bytes, void* out_data, void* stream);
 /* Comparisons of utf8 / binary rows — equal, not_equal, greater, greater_equal, less, less_equal (CompareKernel on
  * BaseBinaryType, compute/kernels/scalar_compare.cc; csrc/string_compare.hip).  The order is the reference's
  * (std::string_view): bytes compare as unsigned bytes over the common length, then the shorter row is less.  No UTF-8
