@@ -1,14 +1,9 @@
 """What the string kernel tests share (test_string_slice, test_string_trim, test_string_replace, test_string_compare,
 test_match_substring): seeded generators, the knob that selects a kernel form, the comparison with the reference's
 result and the device buffers of a host array for calls through the C ABI."""
-import zlib
-
 import numpy as np
 
-
-def rng_for(seed, *key):
-    """A generator of its own for every (module seed, key): an input does not depend on the tests that ran before."""
-    return np.random.default_rng([seed, *[zlib.crc32(str(k).encode()) for k in key]])
+from .util import rng_for  # noqa: F401  (the string test modules call string_util.rng_for(SEED, ...))
 
 
 class path_set:

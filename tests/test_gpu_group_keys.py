@@ -7,10 +7,11 @@ import numpy as np
 import pytest
 
 from . import parity_cases as P
+from . import util as U
 
 
 def _rng(*key):
-    return np.random.default_rng([20260924, *[abs(hash(k)) % (1 << 31) for k in key]])
+    return U.rng_for(20260924, *key)
 
 
 @pytest.mark.gpu
@@ -38,6 +39,4 @@ def test_group_by_three_int64_keys(gpu_ctx):
 @pytest.mark.parametrize("n,null_p,offset,max_len,card", [(0, 0.0, 0, 8, 1), (200_000, 0.1, 0, 30, 400), (100_000, 0.0, 5, 11, 90_000),
                                                          (50_000, 0.3, 3, 50, 7), (1000, 1.0, 0, 5, 5), (60_000, 0.1, 2, 700, 9000)])
 def test_binary_key_columns_and_first_rows(gpu_ctx, n, null_p, offset, max_len, card):
-    from . import util as U
-
     P.check_binary_key_columns(gpu_ctx, U.random_binary_pool(_rng("bkey", n, max_len), n, card, null_p, offset, max_len), _rng("bkey2", n))

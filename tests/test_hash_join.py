@@ -3,10 +3,10 @@ canonical sort, and against a Python restatement of the documented row order exa
 
 The emu tier runs the kernel sources under the SIMT emulator (tests/emu); the gpu tier runs the same grid on the MI355X
 plus a skewed key and a full-size join (2^27 int64 probe rows against 2^24 build rows) checked in chunks."""
-import zlib
-
 import numpy as np
 import pytest
+
+from . import util as U
 
 pa = pytest.importorskip("pyarrow")
 
@@ -18,7 +18,7 @@ LENGTHS = [0, 1, 63, 64, 65, 4097]
 
 
 def rng_for(*key):
-    return np.random.default_rng([0x4A0, *[zlib.crc32(str(k).encode()) for k in key]])
+    return U.rng_for(0x4A0, *key)
 
 
 def random_keys(rng, typ, n, null_p=0.0, card=30):

@@ -6,10 +6,11 @@ MI355X plus three columns of 10^6 rows built from numpy buffers.  Width 16 (deci
 through the C ABI, as do the checks of what the call may and may not write.  Scalars are typed pyarrow scalars, so the
 reference promotes nothing."""
 import ctypes as C
-import zlib
 
 import numpy as np
 import pytest
+
+from . import util as U
 
 pa = pytest.importorskip("pyarrow")
 pc = pytest.importorskip("pyarrow.compute")
@@ -24,7 +25,7 @@ OFFSETS = {"cond": 13, "left": 5, "right": 70}       # four bit alignments at on
 
 
 def rng_for(*key):
-    return np.random.default_rng([0x1FE, *[zlib.crc32(str(k).encode()) for k in key]])
+    return U.rng_for(0x1FE, *key)
 
 
 def column(rng, t, n, null_p):

@@ -114,7 +114,7 @@ needs_pa = pytest.mark.skipif(pa is None, reason="pyarrow wheel not importable")
 
 
 def rng_for(*key):
-    return np.random.default_rng([U.kRandomSeed, *[abs(hash(str(k))) % (1 << 31) for k in key]])
+    return U.rng_for(U.kRandomSeed, *key)
 
 
 def pa_to_list(a):

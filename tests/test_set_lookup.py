@@ -2,10 +2,10 @@
 
 The emu tier runs the kernel sources under the SIMT emulator (tests/emu); the gpu tier runs the same grid on the MI355X
 plus full-size rows (10^9 int64 rows against a 16-value and a 10^6-value set, 10^7 utf8 rows) checked in chunks."""
-import zlib
-
 import numpy as np
 import pytest
+
+from . import util as U
 
 pa = pytest.importorskip("pyarrow")
 pc = pytest.importorskip("pyarrow.compute")
@@ -16,7 +16,7 @@ TEMPORAL = [pa.date32(), pa.date64(), pa.time32("ms"), pa.time64("us"), pa.times
 
 
 def rng_for(*key):
-    return np.random.default_rng([0x5E7, *[zlib.crc32(str(k).encode()) for k in key]])
+    return U.rng_for(0x5E7, *key)
 
 
 def random_values(rng, typ, n, null_p=0.0, card=40):

@@ -6,10 +6,11 @@ The emu tier runs the kernel sources under the SIMT emulator (tests/emu); the gp
 MI355X plus one column of 10^6 rows built from numpy buffers per input type.  The known answers are explicit integers
 per type (day numbers and in-unit offsets), not values that went through `datetime`."""
 import ctypes as C
-import zlib
 
 import numpy as np
 import pytest
+
+from . import util as U
 
 pa = pytest.importorskip("pyarrow")
 pc = pytest.importorskip("pyarrow.compute")
@@ -35,7 +36,7 @@ DAY_MIN, DAY_MAX = -719162, 2932896          # 0001-01-01 .. 9999-12-31
 
 
 def rng_for(*key):
-    return np.random.default_rng([0x7E3, *[zlib.crc32(str(k).encode()) for k in key]])
+    return U.rng_for(0x7E3, *key)
 
 
 def physical(t):

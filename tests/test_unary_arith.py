@@ -14,10 +14,11 @@ this instead — the reference refuses all finite rows and no other, the device 
 rows that are left (NaN, +-inf) come back with their bits."""
 import ctypes as C
 import re
-import zlib
 
 import numpy as np
 import pytest
+
+from . import util as U
 
 pa = pytest.importorskip("pyarrow")
 pc = pytest.importorskip("pyarrow.compute")
@@ -59,7 +60,7 @@ def lengths_of(name):
 
 
 def rng_for(*key):
-    return np.random.default_rng([0xA17, *[zlib.crc32(str(k).encode()) for k in key]])
+    return U.rng_for(0xA17, *key)
 
 
 # ---------------------------------------------------------------- values

@@ -5,6 +5,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import dataclasses
+import zlib
 
 import numpy as np
 
@@ -17,6 +18,12 @@ except Exception:  # pragma: no cover
     pa = pc = None
 
 kRandomSeed = 0x0FF1CE  # compute/kernels/test_util_internal.h:119
+
+
+def rng_for(seed, *key):
+    """A generator of its own for every (module seed, key): an input depends neither on the tests that ran before nor
+    on the process (crc32 of the key's text, not the built-in hash, which is salted per process for str)."""
+    return np.random.default_rng([seed, *[zlib.crc32(str(k).encode()) for k in key]])
 
 
 @dataclasses.dataclass
