@@ -5,19 +5,14 @@ the registry of the test session itself stays stock.
 There is ONE test body here.  The cases are the rows of tests/plugin_scripts.py::CASES, which the CPU tier
 (tests/test_plugin_emulated.py) runs line for line under the emulator — a script that breaks shows in the CPU gate,
 and no Python outside the scripts can rot unseen (VERDICT r4 "What's weak" 1)."""
-import subprocess
-import sys
-
 import pytest
 
 from . import plugin_scripts as S
 
 pytestmark = pytest.mark.gpu
-ROOT = S.ROOT
 
 
 @pytest.mark.parametrize("script,marker", [pytest.param(c[1], c[2], id=c[0]) for c in S.CASES])
 def test_plugin(script, marker):
     pytest.importorskip("pyarrow")
-    r = subprocess.run([sys.executable, "-c", f"ROOT = {ROOT!r}\n" + script], capture_output=True, text=True, timeout=900, cwd=ROOT)
-    assert r.returncode == 0 and marker in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+    S.assert_ran(S.run_case(script, emulated=False, scale=1, timeout=900), marker)

@@ -18,7 +18,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 WORKER = textwrap.dedent(r'''
-    import ctypes, os, pickle, sys, time
+    import ctypes, functools, os, pickle, sys, time
     import numpy as np
     import pyarrow as pa
     sys.path.insert(0, ROOT)
@@ -31,17 +31,8 @@ WORKER = textwrap.dedent(r'''
     lib.arrow_amd_plugin_last_error.restype = ctypes.c_char_p
     assert lib.arrow_amd_register() == 0, lib.arrow_amd_plugin_last_error()
 
-    def to_device(arr):
-        c_arr, c_schema, c_dev = (ctypes.create_string_buffer(m) for m in (80, 72, 128))
-        arr._export_to_c(ctypes.addressof(c_arr), ctypes.addressof(c_schema))
-        assert lib.arrow_amd_copy_to_device(c_arr, c_schema, c_dev) == 0, lib.arrow_amd_plugin_last_error()
-        return pa.Array._import_from_c_device(ctypes.addressof(c_dev), arr.type)
-
-    def to_host(darr):
-        c_dev, c_schema, c_arr, c_schema2 = (ctypes.create_string_buffer(m) for m in (128, 72, 80, 72))
-        darr._export_to_c_device(ctypes.addressof(c_dev), ctypes.addressof(c_schema))
-        assert lib.arrow_amd_copy_to_host(c_dev, c_schema, c_arr, c_schema2) == 0, lib.arrow_amd_plugin_last_error()
-        return pa.Array._import_from_c(ctypes.addressof(c_arr), ctypes.addressof(c_schema2))
+    from tests.plugin_prelude import to_device, to_host
+    to_device, to_host = functools.partial(to_device, lib), functools.partial(to_host, lib)
 
     # the unique id: rank 0 makes it, the others read it from a file (any channel will do)
     id_file = OUT + ".id"
