@@ -750,24 +750,81 @@ def rle_hybrid_encode(values, bit_width: int) -> bytes:
     return bytes(out)
 
 
-def rle_hybrid_decode(data: bytes, runs, bit_width: int, num_values: int) -> np.ndarray:
-    """Value i of an RLE / bit-packed hybrid block given its run table (out_start, kind, payload):
-    repeated run -> the payload; literal run -> bits [k*bit_width, (k+1)*bit_width) after the run's
-    first byte, LSB first (RleBitPackedDecoder + BitReader, rle_encoding_internal.h, bit_stream_utils_internal.h).
-    Row-at-a-time restatement of what arx_rle_decode_u32 computes."""
-    out = np.zeros(num_values, dtype=np.uint32)
-    big = int.from_bytes(data, "little")
-    starts = [int(r["out_start"]) for r in runs]
-    import bisect
+def rle_hybrid_write(runs, bit_width: int, cut_tail: bool = False) -> bytes:
+    """The bytes of an RLE / bit-packed hybrid block from an explicit list of runs (rle_encoding_internal.h:40-90), for
+    tests: ("rep", count, value) is a repeated run of any count >= 1, ("lit", groups, values) a literal run of `groups`
+    groups of 8 that carries len(values) <= 8 * groups values (the rest of its slots are zero).  cut_tail: the bytes of
+    the LAST run that its values do not use are left off the stream (a literal run that reaches the last value of its
+    block may stop where its needed values stop)."""
+    out = bytearray()
 
-    for i in range(num_values):
-        r = runs[bisect.bisect_right(starts, i) - 1]
-        if int(r["kind"]) == 0:
-            out[i] = int(r["payload"])
+    def varint(x):
+        while x >= 0x80:
+            out.append((x & 0x7F) | 0x80)
+            x >>= 7
+        out.append(x)
+
+    for at, (what, count, payload) in enumerate(runs):
+        if what == "rep":
+            assert count >= 1 and 0 <= int(payload) < max(1 << bit_width, 1)
+            varint(count << 1)
+            out.extend(int(payload).to_bytes((bit_width + 7) // 8, "little"))
         else:
-            bit = int(r["payload"]) * 8 + (i - int(r["out_start"])) * bit_width
-            out[i] = (big >> bit) & ((1 << bit_width) - 1)
+            values = [int(x) for x in payload]
+            assert what == "lit" and count >= 1 and len(values) <= 8 * count
+            varint((count << 1) | 1)
+            acc = 0
+            for k, x in enumerate(values):
+                assert 0 <= x < max(1 << bit_width, 1)
+                acc |= x << (k * bit_width)
+            nbytes = count * bit_width
+            if cut_tail and at == len(runs) - 1:
+                nbytes = (len(values) * bit_width + 7) // 8
+            out.extend(acc.to_bytes(nbytes, "little"))
+    return bytes(out)
+
+
+def rle_hybrid_decode(data: bytes, runs, bit_width: int, num_values: int) -> np.ndarray:
+    """Values [0, num_values) of RLE / bit-packed hybrid blocks given their run table (out_start, kind, payload), read the
+    way arx_rle_decode_u32 reads it: value i belongs to the last run whose out_start (absolute in the output) is <= i; a
+    run is repeated iff kind & 0xFF == 0 and then gives its payload; a literal run gives bits [k * w, (k + 1) * w) behind
+    byte `payload` (absolute in `data`, the byte buffer all the runs share), LSB first (RleBitPackedDecoder + BitReader,
+    rle_encoding_internal.h, bit_stream_utils_internal.h), where w = kind >> 8 when that is not zero — the pages of a column
+    chunk carry their own widths — and `bit_width` otherwise.  Bytes at or past len(data) read as zero.
+    By the bits, not by byte windows: every bit of every literal value is looked up in the unpacked bit string of `data`
+    and weighted with its power of two, all values at once."""
+    out = np.zeros(num_values, dtype=np.uint32)
+    runs = np.asarray(runs)
+    if num_values == 0 or len(runs) == 0:
+        return out
+    starts = runs["out_start"].astype(np.int64)
+    kind = runs["kind"].astype(np.int64)
+    payload = runs["payload"].astype(np.uint64)
+    i = np.arange(num_values, dtype=np.int64)
+    r = np.maximum(np.searchsorted(starts, i, side="right") - 1, 0)
+    repeated = (kind[r] & 0xFF) == 0
+    out[repeated] = (payload[r[repeated]] & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+    lit = ~repeated
+    if lit.any():
+        rl = r[lit]
+        own = kind[rl] >> 8
+        width = np.where(own != 0, own, bit_width)
+        first = payload[rl].astype(np.int64) * 8 + (i[lit] - starts[rl]) * width
+        bits = np.unpackbits(np.frombuffer(bytes(data) + b"\0", dtype=np.uint8), bitorder="little")
+        k = np.arange(32, dtype=np.int64)
+        vals = np.zeros(len(first), dtype=np.uint32)
+        for lo in range(0, len(first), 1 << 16):        # (slices only bound the memory of the (values, 32) tables)
+            at = first[lo: lo + (1 << 16), None] + k[None, :]
+            inside = (k[None, :] < width[lo: lo + (1 << 16), None]) & (at < len(bits))
+            got = np.where(inside, bits[np.where(inside, at, 0)], 0).astype(np.uint64)
+            vals[lo: lo + (1 << 16)] = (got << k.astype(np.uint64)[None, :]).sum(axis=1, dtype=np.uint64).astype(np.uint32)
+        out[lit] = vals
     return out
+
+
+def byte_stream_split_decode(split, width: int, n: int) -> np.ndarray:
+    """BYTE_STREAM_SPLIT (ByteStreamSplitDecoder, parquet/decoder.cc): stream k holds byte k of every value -> (n, width) bytes."""
+    return np.ascontiguousarray(np.frombuffer(bytes(split), dtype=np.uint8)[: width * n].reshape(width, n).T)
 
 
 def def_rep_levels_to_list(def_levels, rep_levels, def_level: int, rep_level: int, repeated_ancestor_def_level: int = 0):

@@ -1046,6 +1046,226 @@ def check_delta_decode(amd, rng, block_size=128, miniblocks=4):
             assert_equal(_data_np(out32, np.int32), v.astype(np.int32), f"delta int32 {kind} n={n}")
 
 
+# ------------------------------------------------------------------ the Parquet page primitives at their own entry points
+RLE_COUNTS = (1, 7, 8, 9, 63, 64, 65, 129, 1000)   # a 64-lane wave emits one ballot word: 63 / 64 / 65 = the last word partial, full, one bit
+RLE_GUARD = 0xA5C3F00D
+
+
+def rle_run_plan(rng, bit_width, n, form):
+    """The runs of one hand-made hybrid stream of n values for O.rle_hybrid_write -> (runs, values, cut_tail).  Forms:
+    "mixed" = repeated runs of 1..20 values and literal runs of 1..4 groups in random alternation (run boundaries fall
+    anywhere, not on multiples of 8 or 64); "short-tail" / "short-cut" = the same, ending in a literal run that announces
+    more values than are left, with and without the bytes its unused slots would take; "rep" = one repeated run; "lit" = one
+    literal run.  Values come from all of [0, 2^w); the largest one and 0 are forced into the first literal run and the
+    largest one into the first repeated run."""
+    top = (1 << bit_width) - 1
+
+    def draw(k):
+        return rng.integers(0, top, size=k, dtype=np.uint64, endpoint=True)
+
+    shape = []                                                    # (is literal, values it holds, groups)
+    if form == "rep":
+        shape.append((False, n, 0))
+    elif form == "lit":
+        shape.append((True, n, -(-n // 8)))
+    else:
+        left = n
+        while left:
+            literal, groups, count = bool(rng.integers(0, 2)), int(rng.integers(1, 5)), int(rng.integers(1, 21))
+            take = 8 * groups if literal else count
+            if take >= left:                                      # the last run: only it may hold fewer values than it announces
+                if form == "mixed":
+                    groups = -(-left // 8)
+                else:
+                    literal, groups = True, left // 8 + 1
+                take = left
+            shape.append((literal, take, groups if literal else 0))
+            left -= take
+    runs, values, forced_lit, forced_rep = [], [], False, False
+    for literal, take, groups in shape:
+        if literal:
+            v = draw(take)
+            if not forced_lit:
+                v[0], v[-1], forced_lit = top, (0 if take > 1 else top), True
+            runs.append(("lit", groups, v))
+        else:
+            v = np.full(take, top if not forced_rep else draw(1)[0], dtype=np.uint64)
+            forced_rep = True
+            runs.append(("rep", take, int(v[0])))
+        values.append(v)
+    return runs, np.concatenate(values).astype(np.uint32), form == "short-cut"
+
+
+RLE_FORMS = ("mixed", "short-tail", "short-cut", "rep", "lit")
+
+
+def rle_decode_on_device(amd, data, runs, bit_width, n):
+    """arx_rle_decode_u32 into n + 4 words pre-filled with RLE_GUARD -> (the n values, whether the 4 guard words are untouched)."""
+    from arrow_amd import _lib as L
+    from arrow_amd.array import current_stream, default_device, to_device
+
+    lib, dev = L.get_lib(), default_device()
+    d_bytes = to_device(np.frombuffer(bytes(data) or b"\0", dtype=np.uint8), dev)
+    d_runs = amd.parquet._device_runs(runs, dev)
+    out = to_device(np.full(n + 4, RLE_GUARD, dtype=np.uint32), dev)
+    L.check(lib.arx_rle_decode_u32(d_bytes.data_ptr(), len(data), d_runs.data_ptr(), len(runs), bit_width, n, out.data_ptr(),
+                                   current_stream(dev)))
+    host = out.cpu().numpy()[: 4 * (n + 4)].view(np.uint32)
+    return host[:n].copy(), bool((host[n:] == RLE_GUARD).all())
+
+
+def rle_equals_on_device(amd, data, runs, bit_width, n, equals):
+    """arx_rle_decode_equals_bitmap into ceil(n / 64) words followed by 16 guard bytes -> (the n bits, whether the padding
+    bits of the last word are zero, whether the guard bytes are untouched)."""
+    from arrow_amd import _lib as L
+    from arrow_amd.array import current_stream, default_device, to_device
+
+    lib, dev = L.get_lib(), default_device()
+    d_bytes = to_device(np.frombuffer(bytes(data) or b"\0", dtype=np.uint8), dev)
+    d_runs = amd.parquet._device_runs(runs, dev)
+    nb = 8 * ((n + 63) // 64)
+    out = to_device(np.full(nb + 16, 0xEE, dtype=np.uint8), dev)
+    L.check(lib.arx_rle_decode_equals_bitmap(d_bytes.data_ptr(), len(data), d_runs.data_ptr(), len(runs), bit_width, n, equals,
+                                             out.data_ptr(), current_stream(dev)))
+    host = out.cpu().numpy()[: nb + 16]
+    bits = np.unpackbits(host[:nb], bitorder="little")
+    return bits[:n].astype(bool), not bits[n:].any(), bool((host[nb:] == 0xEE).all())
+
+
+def check_rle_hybrid(amd, rng_for, bit_width):
+    """arx_rle_scan_runs + arx_rle_decode_u32 (and, for widths 1..16, arx_rle_scan_runs_equals +
+    arx_rle_decode_equals_bitmap) on hand-made streams of one bit width: every count of RLE_COUNTS in every form of
+    rle_run_plan.  The decoded values equal the written ones and the restatement's (oracle.rle_hybrid_decode), the bitmap
+    equals values == e for an e that occurs and for one that does not (the smallest value of [0, 2^w] that is not among
+    the values: 2^w itself when every value of the width occurs), nothing is written behind either output, and the host
+    walk's counts equal the popcounts."""
+    from arrow_amd import _lib as L
+
+    P = amd.parquet
+    for n in RLE_COUNTS:
+        for form in RLE_FORMS:
+            rng = rng_for("rle-hybrid", bit_width, n, form)
+            plan, values, cut = rle_run_plan(rng, bit_width, n, form)
+            data = O.rle_hybrid_write(plan, bit_width, cut_tail=cut)
+            tag = f"hybrid w={bit_width} n={n} {form}"
+            runs, ones = P.scan_rle_runs(data, bit_width, n)
+            assert len(runs) == len(plan), tag
+            assert_equal(O.rle_hybrid_decode(data, runs, bit_width, n), values, tag + " restatement")
+            got, guard_ok = rle_decode_on_device(amd, data, runs, bit_width, n)
+            assert_equal(got, values, tag + " arx_rle_decode_u32")
+            assert guard_ok, tag + ": arx_rle_decode_u32 wrote behind its n values"
+            if bit_width == 1:
+                assert ones == int(values.sum()), tag
+            if bit_width == 0:
+                assert P.scan_rle_runs(data, 0, n, equals=0)[1] == n and P.scan_rle_runs(data, 0, n, equals=1)[1] == 0, tag
+            if bit_width > 16:
+                with pytest.raises(L.ArrowInvalid):
+                    P.scan_rle_runs(data, bit_width, n, equals=int(values[0]))
+            if 1 <= bit_width <= 16:
+                present = int(values[int(rng.integers(0, n))])
+                absent = int(np.setdiff1d(np.arange(min(1 << bit_width, n + 1) + 1, dtype=np.int64), values)[0])
+                for e in (present, absent):
+                    want = values == e
+                    eruns, count = P.scan_rle_runs(data, bit_width, n, equals=e)
+                    assert np.array_equal(eruns, runs) and count == int(want.sum()), (tag, e, count)
+                    bits, pad_ok, guard_ok = rle_equals_on_device(amd, data, eruns, bit_width, n, e)
+                    assert_equal(bits, want, f"{tag} equals={e} bitmap")
+                    assert pad_ok, f"{tag} equals={e}: padding bits of the last word are not zero"
+                    assert guard_ok, f"{tag} equals={e}: arx_rle_decode_equals_bitmap wrote behind its words"
+
+
+def check_rle_hybrid_pages(amd, rng_for):
+    """One launch over the pages of a chunk, as read_column_chunk does it: four streams of different widths in one byte
+    buffer, their tables shifted by out_base / byte_base, every run carrying its page's width in kind >> 8 and bit_width =
+    0 passed; then pages whose runs carry no width of their own next to pages that do, with that width passed instead.  And
+    a boolean PLAIN page: one literal run of width 1 whose payload is not at byte 0."""
+    P = amd.parquet
+    for widths, passed in (((0, 3, 17, 32), 0), ((3, 17, 32, 9, 17), 17)):
+        data, tables, values = bytearray(), [], []
+        done = 0
+        for k, (w, n) in enumerate(zip(widths, (65, 129, 63, 200, 77))):
+            rng = rng_for("rle-pages", passed, k)
+            plan, v, cut = rle_run_plan(rng, w, n, ("mixed", "short-tail", "short-cut")[k % 3])
+            page = O.rle_hybrid_write(plan, w, cut_tail=cut)
+            runs, _ = P.scan_rle_runs(page, w, n, out_base=done, byte_base=len(data))
+            assert (runs["kind"] == 0).any() and (runs["kind"] == 1).any()
+            if w != passed:
+                runs["kind"] |= np.uint32(w << 8)
+            tables.append(runs)
+            data += page
+            values.append(v)
+            done += n
+        runs, values = np.concatenate(tables), np.concatenate(values)
+        tag = f"hybrid pages of widths {widths}, bit_width {passed} passed"
+        assert_equal(O.rle_hybrid_decode(bytes(data), runs, passed, done), values, tag + " restatement")
+        got, guard_ok = rle_decode_on_device(amd, bytes(data), runs, passed, done)
+        assert_equal(got, values, tag)
+        assert guard_ok, tag
+    for n in (1, 65, 1000):
+        rng = rng_for("rle-bool-plain", n)
+        values = rng.integers(0, 2, n).astype(np.uint32)
+        data = bytes(rng.integers(0, 256, 5, dtype=np.uint8)) + np.packbits(values.astype(bool), bitorder="little").tobytes()
+        run = np.zeros(1, dtype=P.RUN_DTYPE)
+        run["out_start"], run["kind"], run["payload"] = 0, 1, 5
+        assert_equal(O.rle_hybrid_decode(data, run, 1, n), values, f"boolean PLAIN n={n} restatement")
+        got, guard_ok = rle_decode_on_device(amd, data, run, 1, n)
+        assert_equal(got, values, f"boolean PLAIN n={n}")
+        bits, pad_ok, bguard_ok = rle_equals_on_device(amd, data, run, 1, n, 1)
+        assert_equal(bits, values == 1, f"boolean PLAIN n={n} bitmap")
+        assert guard_ok and pad_ok and bguard_ok, n
+
+
+def check_byte_stream_split(amd, rng_for):
+    """arx_byte_stream_split_decode at its three widths against the restatement (oracle.byte_stream_split_decode): random
+    bytes, counts around one wave, 8 guard bytes behind the output."""
+    from arrow_amd import _lib as L
+    from arrow_amd.array import current_stream, default_device, to_device
+
+    lib, dev = L.get_lib(), default_device()
+    for width in (2, 4, 8):
+        for n in (1, 63, 64, 65, 1000):
+            split = rng_for("byte-stream-split", width, n).integers(0, 256, width * n, dtype=np.uint8)
+            d_in = to_device(split, dev)
+            out = to_device(np.full(width * n + 8, 0xEE, dtype=np.uint8), dev)
+            L.check(lib.arx_byte_stream_split_decode(d_in.data_ptr(), n, width, out.data_ptr(), current_stream(dev)))
+            host = out.cpu().numpy()[: width * n + 8]
+            assert_equal(host[: width * n], O.byte_stream_split_decode(split, width, n).reshape(-1), f"byte stream split W={width} n={n}")
+            assert (host[width * n:] == 0xEE).all(), (width, n)
+
+
+DELTA_STREAM_SHAPES = ((128, 4), (256, 8), (128, 1), (384, 4), (1024, 32))
+
+
+def delta_stream_values(rng, n, kind):
+    if kind == "full":
+        return rng.integers(-2**63, 2**63 - 1, n).astype(np.int64)      # wrap-around deltas
+    if kind == "walk":
+        return np.cumsum(rng.integers(-40, 50, n)).astype(np.int64)
+    return np.full(n, -3, dtype=np.int64)
+
+
+def check_delta_streams(amd, rng_for, block_size, miniblocks):
+    """parquet.decode_delta_streams (arx_delta_decode_pages: many streams, one launch sequence) on hand-made streams: the
+    first has the block shape given, the next ones take the shapes of DELTA_STREAM_SHAPES in turn from there, so that the
+    streams of one launch differ in their values per miniblock.  Streams of 1 and 0 values between others, streams that end
+    one short of, on and one past a 4096-value tile and one past a block, full-range / random-walk / constant values in
+    turn, 0..8 bytes that are not the stream's behind every stream; INT64 and INT32 output.  The output is the streams'
+    values one after the other, and every stream reports its count and the bytes it takes."""
+    rng = rng_for("delta-streams", block_size, miniblocks)
+    first = DELTA_STREAM_SHAPES.index((block_size, miniblocks))
+    shapes = [DELTA_STREAM_SHAPES[(first + k) % len(DELTA_STREAM_SHAPES)] for k in range(9)]
+    counts = (1, 0, 2, 4095, 4096, 4097, shapes[6][0] + 1, 9001, 1)
+    values = [delta_stream_values(rng, n, ("full", "walk", "const")[k % 3]) for k, n in enumerate(counts)]
+    encoded = [O.delta_binary_packed_encode(v, *shape) for v, shape in zip(values, shapes)]
+    streams = [e + bytes(rng.integers(0, 256, int(rng.integers(0, 9)), dtype=np.uint8)) for e in encoded]
+    want = np.concatenate(values)
+    for width, dtype in ((8, np.int64), (4, np.int32)):
+        out, info = amd.parquet.decode_delta_streams(streams, width)
+        assert info == [(n, len(e)) for n, e in zip(counts, encoded)], (block_size, miniblocks, width)
+        got = out.cpu().numpy()[: width * len(want)].view(dtype)
+        assert_equal(got, want.astype(dtype), f"delta streams from {block_size}/{miniblocks} on, int{8 * width}")
+
+
 class _Groups:
     """Canonical form of a group-by result: rows sorted by (key_is_null, key) (tests sort too,
     acero/hash_aggregate_test.cc:262-280), as numpy columns — the tuple-per-group form this replaced took most of the GPU

@@ -1254,3 +1254,122 @@ def test_oracle_normal_ppf_and_rank_normal_against_the_references_known_answers(
     for v, valid, order, place, want in RANK_NORMAL_VECTORS:
         got = O.rank(np.array(v, np.int64), None if valid is None else np.array(valid, bool), order == "descending", place == "at_start", "normal")
         assert np.allclose(got, want, rtol=0, atol=1e-8) and P.max_ulps(got, want) <= 4, (v, order, place, got)
+
+
+# ------------------------------------------------------------------ the RLE / bit-packed hybrid (oracle.rle_hybrid_decode)
+def _hybrid_blocks_decoded(path, column, what, level_width=0, has_repetition=False):
+    """The hybrid blocks of every V1 data page of one uncompressed column chunk — what = "indices": the dictionary indices
+    behind their width byte; "levels": the definition levels behind their 4-byte length (and behind the repetition levels'
+    block) — walked page by page into one run table the way read_column_chunk builds it (out_base / byte_base, the page's
+    width in kind >> 8) and decoded by the restatement with bit_width 0.  -> (values, the widths seen, number of pages, the
+    bytes of the chunk's dictionary page)."""
+    import struct
+
+    import pyarrow.parquet as pq
+
+    from arrow_amd import parquet as P
+
+    col = pq.ParquetFile(path).metadata.row_group(0).column(column)
+    raw = open(path, "rb").read()
+    data, tables, done, widths, dictionary = bytearray(), [], 0, set(), b""
+    for hdr, payload in P._column_chunk_pages(raw, col):
+        if hdr[1] == P._PAGE_DICT:
+            dictionary = bytes(payload)
+        if hdr[1] != P._PAGE_DATA:
+            continue
+        page, n, pos = bytes(payload), hdr[5][1], 0
+        if what == "levels":
+            if has_repetition:
+                pos = 4 + struct.unpack_from("<i", page, 0)[0]
+            (nbytes,) = struct.unpack_from("<i", page, pos)
+            bw, block = level_width, page[pos + 4: pos + 4 + nbytes]
+        else:
+            assert hdr[5][2] in (P._ENC_PLAIN_DICT, P._ENC_RLE_DICT), hdr[5][2]
+            bw, block = page[0], page[1:]
+        runs, _ = P.scan_rle_runs(block, bw, n, out_base=done, byte_base=len(data))
+        runs["kind"] |= np.uint32(bw << 8)
+        tables.append(runs)
+        data += block
+        done += n
+        widths.add(bw)
+    return O.rle_hybrid_decode(bytes(data), np.concatenate(tables), 0, done), widths, len(tables), dictionary
+
+
+@needs_pa
+def test_rle_hybrid_restatement_against_the_reference_writer(tmp_path):
+    """oracle.rle_hybrid_decode — the restatement the hybrid kernels are compared with — decodes what the reference's
+    RleBitPackedEncoder wrote to the reference reader's own values: the dictionary indices of one required column per index
+    width 1..17 (2^(w-1) + 1 .. 2^w distinct values; every width must show up in a page's width byte, or the pin says
+    nothing about it), the definition levels of a nullable column (width 1) and of a list column (width 2).  The reference
+    reader hands out dictionary indices for BYTE_ARRAY columns only (read_dictionary), so every file carries the same
+    indices twice: as a string column, compared with those indices directly, and as an int32 column, whose indices are
+    looked up from the reader's values in the chunk's dictionary page (its entries are distinct: one index per value).
+    Widths 18..32
+    are out of a writer's reach at any reasonable size; the packing rule (value k of a literal run = bits [k * w, (k + 1) * w)
+    behind the run's first byte, LSB first) is one formula in the width, and the pin of the wider widths rests on that."""
+    import pyarrow.parquet as pq
+
+    seen = set()
+    for w in range(1, 18):
+        rng = rng_for("rle-pin", w)
+        distinct = (1 << w) if w % 2 == 0 or w == 1 else (1 << (w - 1)) + 1 + int(rng.integers(0, 1 << (w - 2)))
+        n = max(2 * distinct, 20_000)
+        # every distinct value early (the dictionary, and with it the index width, grows page by page), then random draws
+        # with a few long stretches of one value: repeated runs and literal runs, several pages at the full width
+        idx = np.concatenate([rng.permutation(distinct), rng.integers(0, distinct, n - distinct)])
+        for at in rng.integers(distinct, n - 300, 8):
+            idx[at: at + int(rng.integers(8, 300))] = idx[at]
+        values = (idx * 3 - 7).astype(np.int32)
+        path = os.path.join(str(tmp_path), f"w{w}.parquet")
+        words = np.array(["%x" % k for k in range(distinct)], dtype=object)[idx]
+        schema = pa.schema([pa.field("v", pa.int32(), nullable=False), pa.field("s", pa.string(), nullable=False)])
+        pq.write_table(pa.table({"v": pa.array(values), "s": pa.array(words, pa.string())}).cast(schema), path, use_dictionary=True,
+                       compression="none", data_page_version="1.0", data_page_size=2048, dictionary_pagesize_limit=8 << 20,
+                       row_group_size=n)
+        ref = pq.read_table(path, read_dictionary=["s"])
+        got, widths, pages, dictionary = _hybrid_blocks_decoded(path, 0, "indices")
+        assert w in widths and max(widths) == w and pages > 2, (w, sorted(widths), pages)
+        entries = np.frombuffer(dictionary, dtype=np.int32)
+        assert len(entries) == distinct == len(np.unique(entries))
+        order = np.argsort(entries, kind="stable")
+        want = order[np.searchsorted(entries[order], ref.column("v").to_numpy())]
+        assert np.array_equal(entries[want], values) and np.array_equal(got, want), w
+        seen_here = widths
+        got, widths, pages, _ = _hybrid_blocks_decoded(path, 1, "indices")
+        assert w in widths and max(widths) == w and pages > 2, (w, sorted(widths), pages)
+        chunks = ref.column("s").chunks
+        assert all(c.dictionary.equals(chunks[0].dictionary) for c in chunks)
+        assert np.array_equal(got, np.concatenate([c.indices.to_numpy() for c in chunks])), w
+        seen |= seen_here & widths
+    assert seen >= set(range(1, 18)), sorted(seen)
+
+    rng = rng_for("rle-pin", "levels")
+    n = 30_000
+    valid = rng.random(n) < 0.7
+    valid[1000:4000] = True
+    valid[9000:9500] = False
+    path = os.path.join(str(tmp_path), "nullable.parquet")
+    pq.write_table(pa.table({"v": pa.array(rng.integers(0, 2**40, n), mask=~valid)}), path, use_dictionary=False,
+                   compression="none", data_page_version="1.0", data_page_size=4096, row_group_size=n)
+    got, _, pages, _ = _hybrid_blocks_decoded(path, 0, "levels", level_width=1)
+    ref = pq.read_table(path).column("v").combine_chunks()
+    assert pages > 2 and np.array_equal(got.astype(bool), ref.is_valid().to_numpy(zero_copy_only=False)) and np.array_equal(got.astype(bool), valid)
+
+    rows = []
+    for k in range(6000):                # null list: 0, empty list: 1, null element: 2, element: 3
+        what = rng.random()
+        if 2000 <= k < 2400 or what < 0.15:
+            rows.append(None)
+        elif what < 0.3:
+            rows.append([])
+        else:
+            rows.append([None if rng.random() < 0.2 else int(x) for x in rng.integers(0, 99, int(rng.integers(1, 12)))])
+    path = os.path.join(str(tmp_path), "list.parquet")
+    pq.write_table(pa.table({"l": pa.array(rows, pa.list_(pa.field("element", pa.int64())))}), path, use_dictionary=False,
+                   compression="none", data_page_version="1.0", data_page_size=4096, row_group_size=len(rows))
+    got, _, pages, _ = _hybrid_blocks_decoded(path, 0, "levels", level_width=2, has_repetition=True)
+    ref = pq.read_table(path).column("l").combine_chunks()
+    want = []
+    for row_valid, row in zip(ref.is_valid().to_pylist(), ref.to_pylist()):
+        want += [0] if not row_valid else [1] if not row else [2 if x is None else 3 for x in row]
+    assert pages > 2 and ref.to_pylist() == rows and np.array_equal(got, want)

@@ -830,8 +830,10 @@ def test_delta_decode_kernel_vs_restatement(emu_ctx, block_size, miniblocks):
 
 
 def test_rle_run_walk_and_decode_vs_numpy_restatement():
-    """scan_rle_runs + the oracle's hybrid decode reproduce what the reference's encoder wrote:
-    definition levels and dictionary indices of a written file decode to pyarrow's own values."""
+    """The oracle's own writer (rle_hybrid_encode) against the oracle's own decoder (rle_hybrid_decode) through the host
+    walk (scan_rle_runs), at five widths: the two halves of the oracle agree with each other and with the walk's run
+    table.  No device code runs and no file is written here; the restatement is pinned to the reference's writer in
+    tests/test_oracle_pin.py, and the kernels are compared with it in test_rle_hybrid_kernels_vs_restatement."""
     from arrow_amd import parquet as P
 
     rng = np.random.default_rng(11)
@@ -845,6 +847,83 @@ def test_rle_run_walk_and_decode_vs_numpy_restatement():
         assert (got == vals).all()
         if bit_width == 1:
             assert ones == int(vals.sum())
+
+
+def _rng_for(*key):
+    return U.rng_for(U.kRandomSeed, *key)
+
+
+@pytest.mark.emu
+@pytest.mark.parametrize("bit_width", range(33))
+def test_rle_hybrid_kernels_vs_restatement(emu_ctx, bit_width):
+    """arx_rle_decode_u32 / arx_rle_decode_equals_bitmap at their own entry points, on hand-made streams of every bit width
+    0..32 (the reference's writer reaches 17 at most, and emits neither short repeated runs nor a cut last run)."""
+    PC.check_rle_hybrid(emu_ctx, _rng_for, bit_width)
+
+
+@pytest.mark.emu
+def test_rle_hybrid_pages_of_several_widths_in_one_launch(emu_ctx):
+    PC.check_rle_hybrid_pages(emu_ctx, _rng_for)
+
+
+@pytest.mark.emu
+def test_byte_stream_split_kernel_vs_restatement(emu_ctx):
+    PC.check_byte_stream_split(emu_ctx, _rng_for)
+
+
+@pytest.mark.emu
+@pytest.mark.parametrize("block_size,miniblocks", PC.DELTA_STREAM_SHAPES)
+def test_delta_streams_in_one_launch_vs_their_values(emu_ctx, block_size, miniblocks):
+    PC.check_delta_streams(emu_ctx, _rng_for, block_size, miniblocks)
+
+
+def _byte_array_page(rng, count):
+    lengths = rng.integers(0, 21, count)
+    lengths[rng.random(count) < 0.2] = 0
+    return b"".join(struct.pack("<I", int(ln)) + bytes(rng.integers(0, 256, int(ln), dtype=np.uint8)) for ln in lengths)
+
+
+def _plain_byte_array_offsets(page, count, base):
+    """arx_plain_byte_array_offsets -> (return code, the 2 * count + 1 offsets, whether the two words behind them are untouched)."""
+    from arrow_amd import _lib
+
+    buf = np.frombuffer(page, dtype=np.uint8)
+    out = np.full(2 * count + 3, -77, dtype=np.int32)
+    rc = _lib.get_lib().arx_plain_byte_array_offsets(buf.ctypes.data if len(buf) else None, len(buf), count, base, out.ctypes.data)
+    return rc, out[: 2 * count + 1], bool((out[2 * count + 1:] == -77).all())
+
+
+def test_plain_byte_array_offsets_vs_a_python_walk():
+    """The host walk over PLAIN BYTE_ARRAY values: the alternating {length prefix, value} offsets equal a Python walk over
+    the same bytes, for no, one, two and many values, empty ones among them, from base 0 and from another base; a length
+    that runs past the page, a value that starts in the page's last 3 bytes and a position beyond the int32 range are
+    refused, not wrapped."""
+    from arrow_amd import _lib
+
+    for count in (0, 1, 2, 1000):
+        for base in (0, 12345):
+            rng = _rng_for("plain-byte-array", count, base)
+            page = _byte_array_page(rng, count) + b"not a value"
+            want, pos = [base], 0
+            for _ in range(count):
+                (ln,) = struct.unpack_from("<I", page, pos)
+                want += [base + pos + 4, base + pos + 4 + ln]
+                pos += 4 + ln
+            rc, got, clean = _plain_byte_array_offsets(page, count, base)
+            assert rc == 0 and got.tolist() == want and clean, (count, base)
+    rng = _rng_for("plain-byte-array", "invalid")
+    page = _byte_array_page(rng, 10)
+    long_last = page + struct.pack("<I", 6) + b"12345"                  # 6 bytes announced, 5 present
+    assert _plain_byte_array_offsets(long_last + b"6", 11, 0)[0] == 0
+    assert _plain_byte_array_offsets(long_last, 11, 0)[0] == _lib.ARX_INVALID
+    assert _plain_byte_array_offsets(page + struct.pack("<I", 0xFFFFFFFF) + b"12345", 11, 0)[0] == _lib.ARX_INVALID
+    for tail in (1, 2, 3):                                              # the 11th value would start in the last `tail` bytes
+        assert _plain_byte_array_offsets(page + bytes(tail), 11, 0)[0] == _lib.ARX_INVALID, tail
+    assert _plain_byte_array_offsets(page + bytes(4), 11, 0)[0] == 0
+    top = 2**31 - 1
+    assert _plain_byte_array_offsets(page, 10, top - len(page))[0] == 0       # the last offset is INT32_MAX exactly
+    assert _plain_byte_array_offsets(page, 10, top - len(page) + 1)[0] == _lib.ARX_INVALID
+    assert _plain_byte_array_offsets(page, 10, top)[0] == _lib.ARX_INVALID
 
 
 @pytest.mark.emu
@@ -1146,6 +1225,28 @@ def test_parquet_delta_length_byte_array_gpu(gpu_ctx, tmp_path, null_p):
 def test_delta_decode_kernel_vs_restatement_gpu(gpu_ctx):
     PC.check_delta_decode(gpu_ctx, np.random.default_rng(5), 128, 4)
     PC.check_delta_decode(gpu_ctx, np.random.default_rng(6), 512, 2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bit_width", range(33))
+def test_rle_hybrid_kernels_vs_restatement_gpu(gpu_ctx, bit_width):
+    PC.check_rle_hybrid(gpu_ctx, _rng_for, bit_width)
+
+
+@pytest.mark.gpu
+def test_rle_hybrid_pages_of_several_widths_in_one_launch_gpu(gpu_ctx):
+    PC.check_rle_hybrid_pages(gpu_ctx, _rng_for)
+
+
+@pytest.mark.gpu
+def test_byte_stream_split_kernel_vs_restatement_gpu(gpu_ctx):
+    PC.check_byte_stream_split(gpu_ctx, _rng_for)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("block_size,miniblocks", PC.DELTA_STREAM_SHAPES)
+def test_delta_streams_in_one_launch_vs_their_values_gpu(gpu_ctx, block_size, miniblocks):
+    PC.check_delta_streams(gpu_ctx, _rng_for, block_size, miniblocks)
 
 
 @pytest.mark.gpu
@@ -1909,7 +2010,11 @@ def test_lz4_independent_blocks_are_decoded_as_linked(emu_ctx):
 
 def _decoder_corpus():
     """(kind, input, dst_size) of every hand-made stream, valid and invalid, and of a few hundred damaged ones: kind 0 a
-    gzip / zlib page, 1 / 2 a Snappy block for the LDS / the global form, 3 an LZ4 frame."""
+    gzip / zlib page, 1 / 2 a Snappy block for the LDS / the global form, 3 an LZ4 frame, 4 an RLE / bit-packed hybrid block
+    (dst_size = n | bit width << 24: one hand-made stream of parity_cases.rle_run_plan per width 0..32), 5 a
+    DELTA_BINARY_PACKED stream (dst_size = n | output byte width << 24: three streams per block shape of
+    parity_cases.DELTA_STREAM_SHAPES); each stream of kinds 4 and 5 intact and in 6 damaged copies.  -> (the cases, the
+    positions of the damaged copies of kinds 4 and 5)."""
     from . import deflate_writer as DW
     from . import decoder_streams as DS
 
@@ -1935,19 +2040,93 @@ def _decoder_corpus():
         cases.append((3, frame, len(payload)))
         cases += [(3, DS.damage(rng, frame, 7, len(frame) - 4), len(payload)) for _ in range(6)]         # (the frame's structure too)
     cases += [(3, frame, n) for name, frame, n, _ in DS.invalid_lz4()]
-    return cases
+    damaged = set()
+    for w in range(33):
+        n, form = (7, 9, 63, 65, 129)[w % 5], PC.RLE_FORMS[w % 3]
+        plan, _, cut = PC.rle_run_plan(_rng_for("reads-hybrid", w), w, n, form)
+        block = O.rle_hybrid_write(plan, w, cut_tail=cut)
+        cases.append((4, block, n | w << 24))
+        if len(block) < 5000:
+            damaged |= set(range(len(cases), len(cases) + 6))
+            cases += [(4, DS.damage(rng, block, 0, len(block)), n | w << 24) for _ in range(6)]
+    for k, (block_size, miniblocks) in enumerate(PC.DELTA_STREAM_SHAPES):
+        for j, (n, kind) in enumerate(((2, "full"), (65, "full"), (block_size + 1, "walk"))):
+            width = 8 if (k + j) % 2 else 4
+            stream = O.delta_binary_packed_encode(PC.delta_stream_values(_rng_for("reads-delta", k, j), n, kind), block_size, miniblocks)
+            cases.append((5, stream, n | width << 24))
+            if len(stream) < 5000:
+                damaged |= set(range(len(cases), len(cases) + 6))
+                cases += [(5, DS.damage(rng, stream, 0, len(stream)), n | width << 24) for _ in range(6)]
+    return cases, damaged
+
+
+def _hybrid_case_python_route(amd, data, packed):
+    """Kind 4 of the corpus through the Python route -> what tests/emu/decoder_reads_main.cpp prints for it, and the same from
+    the restatement applied to the walk's run table (None when the walk refuses the block)."""
+    import ctypes as C
+    import zlib
+
+    from arrow_amd import _lib
+
+    n, w = packed & 0xFFFFFF, packed >> 24
+    lib = _lib.get_lib()
+    nr, ones = C.c_int64(0), C.c_int64(0)
+    rc = lib.arx_rle_scan_runs(data, len(data), w, n, 0, 0, None, 0, C.byref(nr), C.byref(ones))
+    if rc:
+        return ["scan", str(rc)], None
+    def line(values, bits=None, count=None):             # as the program sums them: the values, the bitmap's words, the count
+        crc = zlib.crc32(values.astype("<u4").tobytes())
+        if bits is not None:
+            words = np.zeros(64 * ((n + 63) // 64), dtype=bool)
+            words[:n] = bits
+            crc = zlib.crc32(struct.pack("<q", count), zlib.crc32(np.packbits(words, bitorder="little").tobytes(), crc))
+        return ["sum", str(crc)]
+
+    runs, _ = amd.parquet.scan_rle_runs(data, w, n)
+    got, _ = PC.rle_decode_on_device(amd, data, runs, w, n)
+    want = O.rle_hybrid_decode(data, runs, w, n)
+    if not 1 <= w <= 16:
+        return line(got), line(want)
+    _, count = amd.parquet.scan_rle_runs(data, w, n, equals=int(got[0]))
+    bits, _, _ = PC.rle_equals_on_device(amd, data, runs, w, n, int(got[0]))
+    return line(got, bits, count), line(want, want == want[0], int((want == want[0]).sum()))
+
+
+def _delta_case_python_route(amd, data, packed):
+    """Kind 5 of the corpus through the Python route (scan_delta_miniblocks + decode_delta_binary_packed)."""
+    import ctypes as C
+    import zlib
+
+    from arrow_amd import _lib
+
+    n, width = packed & 0xFFFFFF, packed >> 24
+    lib = _lib.get_lib()
+    nmb, vpm, total, first, used = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_size_t(0)
+    rc = lib.arx_delta_scan_miniblocks(data, len(data), 0, None, 0, C.byref(nmb), C.byref(vpm), C.byref(total), C.byref(first),
+                                       C.byref(used))
+    if rc:
+        return ["scan", str(rc)]
+    if total.value != n:
+        return ["total", str(total.value)]
+    out = amd.parquet.decode_delta_binary_packed(data, width)
+    return ["sum", str(zlib.crc32(out.data.cpu().numpy()[: n * width].tobytes()))]
 
 
 @pytest.mark.emu
 def test_decoders_do_not_read_past_their_input(emu_ctx, tmp_path):
     """The hand-made, invalid and damaged streams once more, each in an allocation of exactly its size and with a
     destination of exactly dst_size, in a stand-alone program built with AddressSanitizer from the emulated kernel sources
-    (tests/emu/decoder_reads_main.cpp): a clean exit, and the statuses the Python route gives."""
+    (tests/emu/decoder_reads_main.cpp): a clean exit, and the statuses the Python route gives.  Hybrid blocks and delta
+    streams (kinds 4 and 5) go through both passes of their host walk and through the kernels the walk feeds, the outputs
+    exactly as large as their values: the program prints the walk's return code or a checksum of the outputs, which must
+    be the Python route's on the emulator and, for a hybrid block, the restatement's on the walk's run table.  At least
+    half of the damaged hybrid blocks and a third of the damaged delta streams must get past the walk to the kernels.
+    Measured on the emulator: 162 of 198 damaged hybrid blocks and 69 of 90 damaged delta streams reach the kernels."""
     import subprocess
 
     from tests.emu.build_emu import build_decoder_reads
 
-    cases = _decoder_corpus()
+    cases, damaged = _decoder_corpus()
     corpus = os.path.join(str(tmp_path), "corpus.bin")
     with open(corpus, "wb") as f:
         f.write(struct.pack("<I", len(cases)))
@@ -1959,7 +2138,21 @@ def test_decoders_do_not_read_past_their_input(emu_ctx, tmp_path):
     assert len(told) == len(cases)
     lib = emu_ctx._lib.get_lib()
     want = []
-    for kind, data, n in cases:
+    reached = {4: [0, 0], 5: [0, 0]}                       # kind -> [damaged cases, those of them that reach the kernels]
+    for i, (kind, data, n) in enumerate(cases):
+        if kind in (4, 5):
+            if kind == 4:
+                route, restated = _hybrid_case_python_route(emu_ctx, data, n)
+                assert restated is None or restated == route, (i, route, restated)
+            else:
+                route = _delta_case_python_route(emu_ctx, data, n)
+            want.append(route)
+            if i in damaged:
+                reached[kind][0] += 1
+                reached[kind][1] += route[0] == "sum"
+            else:
+                assert route[0] == "sum", (i, route)
+            continue
         if kind == 0:
             want.append(["status", str(_launch_pages("arx_gzip_decompress_pages", [n], [data])[2][0])])
         elif kind in (1, 2):
@@ -1972,3 +2165,7 @@ def test_decoders_do_not_read_past_their_input(emu_ctx, tmp_path):
             rc = lib.arx_lz4_frame_scan(data, len(data), 0, None, 0, C.byref(nb), None)
             want.append(["scan", str(rc)] if rc else ["status", str(_launch_lz4([data], [n])[2][0])])
     assert [(i, t, w) for i, (t, w) in enumerate(zip(told, want)) if t != w] == []
+    print("damaged hybrid blocks that reach the kernels: %d of %d; damaged delta streams: %d of %d" % (reached[4][1], reached[4][0],
+                                                                                                       reached[5][1], reached[5][0]))
+    assert reached[4][0] == 198 and 2 * reached[4][1] >= reached[4][0], reached
+    assert reached[5][0] == 90 and 3 * reached[5][1] >= reached[5][0], reached
