@@ -28,6 +28,9 @@ FILTER_DROP, FILTER_EMIT_NULL = 0, 1
 JOIN_COLUMN, JOIN_LITERAL, JOIN_NULL = 0, 1, 2          # ARX_JOIN_* operand kinds
 JOIN_NULL_HANDLING = {"emit_null": 0, "skip": 1, "replace": 2}
 JOIN_MAX_OPERANDS = 32                                  # ARX_JOIN_MAX_OPERANDS, the separator included
+CASE_WHEN_MAX_CONDS = 16                                # ARX_CASE_WHEN_MAX_CONDS
+ELEMENT_WISE_MIN, ELEMENT_WISE_MAX = 0, 1               # ARX_ELEMENT_WISE_*
+ELEMENT_WISE_MAX_OPERANDS = 32                          # ARX_ELEMENT_WISE_MAX_OPERANDS
 SORT_ASCENDING, SORT_DESCENDING = 0, 1
 NULLS_AT_START, NULLS_AT_END = 0, 1
 
@@ -106,6 +109,12 @@ class ArxBinarySpan(C.Structure):
         ("length", C.c_int64),
         ("null_count", C.c_int64),
     ]
+
+
+class ArxOperand(C.Structure):
+    """struct ArxOperand of include/arrow_amd.h: an array (span), a valid scalar (host bytes) or a null scalar (both NULL)."""
+
+    _fields_ = [("span", C.POINTER(ArxSpan)), ("scalar", C.c_void_p)]
 
 
 class ArxJoinOperand(C.Structure):
@@ -266,6 +275,8 @@ SIGNATURES = {
     "arx_binary_join_data": (_int, [C.POINTER(ArxJoinOperand), _int, _i64, _int, _int, _p, _i64, _p, _i64, _p, _p]),
     "arx_compare_binary": (_int, [_int, _bspan, _bspan, _int, _p, _i64, _i64, _int, _p, _p]),
     "arx_if_else": (_int, [_int, _span, _span, _p, _span, _p, _i64, _p, _p, _p]),
+    "arx_case_when": (_int, [_int, C.POINTER(_span), _int, C.POINTER(ArxOperand), _int, _i64, _p, _p, _p]),
+    "arx_min_max_element_wise": (_int, [_int, _int, _int, C.POINTER(ArxOperand), _int, _i64, _p, _p, _p]),
     "arx_temporal_component": (_int, [_int, _int, _span, _i64, _int, _int, _p, _p, _p]),
     "arx_hash_join_workspace_bytes": (_sz, [_i64]),
     "arx_hash_join_key_validity": (_int, [_span, _int, _i64, _p, _p]),

@@ -131,6 +131,13 @@ class JoinOptions(FunctionOptions):
         self.null_replacement = null_replacement
 
 
+class ElementWiseAggregateOptions(FunctionOptions):
+    """api_scalar.h ElementWiseAggregateOptions: skip_nulls (a row is null only where every operand is null)."""
+
+    def __init__(self, skip_nulls: bool = True):
+        self.skip_nulls = bool(skip_nulls)
+
+
 class DayOfWeekOptions(FunctionOptions):
     """api_scalar.h DayOfWeekOptions: count_from_zero (Monday = 0 rather than 1 at the defaults) and week_start, the ISO
     weekday (Monday = 1 .. Sunday = 7) the numbering starts at."""
@@ -1141,6 +1148,15 @@ def _build_registry() -> FunctionRegistry:
     f = Function("if_else", Function.SCALAR, 3)
     f.add_kernel(Kernel((bool_, _IF_ELSE_VALUE, _IF_ELSE_VALUE), _exec_if_else))
     reg.add_function(f)
+
+    # case_when(conds, v_0 .. v_{k-1} [, else]): values of ONE type, as if_else takes them (csrc/case_when.hip).  conds is a
+    # list of boolean Arrays (or a StructArray of them), not a typed argument: the function checks its arguments itself.
+    reg.add_function(Function("case_when", Function.META, 2, None, lambda args, options: case_when(args[0], *args[1:]), is_varargs=True))
+    # min_element_wise / max_element_wise of 1 .. 32 operands of ONE numeric or physically-integer temporal type (csrc/element_wise.hip)
+    for name in _ELEMENT_WISE_OPS:
+        f = Function(name, Function.SCALAR, 1, ElementWiseAggregateOptions(), is_varargs=True)
+        f.add_kernel(Kernel((_ELEMENT_WISE_VALUE,), _exec_min_max_element_wise(name), is_varargs=True))
+        reg.add_function(f)
 
     # year .. iso_week of dates and timestamps, hour .. nanosecond of timestamps and times (csrc/temporal.hip)
     for name in _TEMPORAL_COMPONENTS:
@@ -3002,6 +3018,179 @@ def if_else(cond: Array, left, right) -> Array:
                                        "arrow_amd.Scalar on one side")
     wrap = lambda x: x if isinstance(x, (Array, Scalar)) else Scalar(x, typed[0], x is not None)  # noqa: E731
     return call_function("if_else", [cond, wrap(left), wrap(right)])
+
+
+# --------------------------------------------------------------------------- case_when
+# case_when(conds, v_0 .. v_{k-1} [, else]) (compute/kernels/scalar_if_else.cc, CaseWhenFunctor): csrc/case_when.hip.
+# As for if_else there are no implicit casts: every value is of one type.
+def _operand_holder(x: Scalar, t: DataType):
+    """The host bytes of a valid scalar as the C ABI takes them (booleans: one byte 0 / 1)."""
+    holder = np.zeros(1, dtype=np.uint8 if t == bool_ else t.np_dtype)
+    holder[0] = bool(x.value) if t == bool_ else t.np_dtype.type(x.value)
+    return holder
+
+
+def _operand_table(operands, t: DataType, keep: list):
+    """ArxOperand[len(operands)] of Arrays and Scalars of type t; `keep` holds what the pointers refer to."""
+    table = (_lib.ArxOperand * len(operands))()
+    for j, x in enumerate(operands):
+        if isinstance(x, Array):
+            keep.append(x.span())
+            table[j].span = C.pointer(keep[-1])
+        elif x.is_valid:
+            keep.append(_operand_holder(x, t))
+            table[j].scalar = keep[-1].ctypes.data
+    return table
+
+
+def _typed_operands(name: str, values, what: str):
+    """values with every Python number, bool or None made a Scalar of the type the typed operands carry."""
+    typed = [x.type for x in values if isinstance(x, (Array, Scalar))]
+    if not typed:
+        raise ArrowNotImplementedError(f"{name}: none of the {what} ({', '.join(repr(x) for x in values)}) carries a type; pass an Array "
+                                       "or an arrow_amd.Scalar as one of them")
+    return [x if isinstance(x, (Array, Scalar)) else Scalar(x, typed[0], x is not None) for x in values]
+
+
+def _one_type(name: str, values, what: str) -> DataType:
+    t = values[0].type
+    for j, x in enumerate(values):
+        if x.type != t:
+            raise ArrowNotImplementedError(f"{name}: {what} 0 is {t.name}, {what} {j} is {x.type.name}; the device kernel takes every "
+                                           f"{what} of one type (no implicit casts)")
+    return t
+
+
+_CASE_WHEN_TOP_LEVEL_NULLS = "cond struct must not be a null scalar or have top-level nulls"
+
+
+def case_when(conds, *values) -> Array:
+    """compute::CaseWhen (scalar_if_else.cc): row i takes values[j][i] of the first j whose conds[j][i] is true and valid (a
+    null cond is false); a row no cond takes comes from the else — the value after the last cond's, if given — or is null.
+    conds: a list or tuple of 1 .. 16 boolean Arrays (or a StructArray whose children they are).  values: as many as conds,
+    or one more; each an Array, an arrow_amd.Scalar, a Python number or bool (it takes the other values' type) or None (a
+    null scalar); all of one type — boolean or 1 / 2 / 4 / 8 bytes wide, temporal types included — since the mirror casts
+    nothing implicitly.  The result stays on the device and has no validity buffer when it cannot hold a null."""
+    from .array import StructArray
+
+    if conds is None or isinstance(conds, Scalar):
+        raise ArrowInvalid(_CASE_WHEN_TOP_LEVEL_NULLS)
+    if isinstance(conds, StructArray):
+        if conds.buffers[0] is not None and conds.null_count != 0:
+            raise ArrowInvalid(_CASE_WHEN_TOP_LEVEL_NULLS)
+        conds = conds.children
+    if not isinstance(conds, (list, tuple)):
+        raise ArrowNotImplementedError(f"case_when: conds must be a list of boolean arrow_amd.Arrays, not {type(conds).__name__}")
+    conds = list(conds)
+    for c in conds:
+        if not isinstance(c, Array) or c.type != bool_:
+            got = c.type.name if isinstance(c, (Array, Scalar)) else type(c).__name__
+            raise ArrowNotImplementedError(f"case_when: every cond must be a boolean arrow_amd.Array, not {got}")
+    if not values:
+        raise ArrowInvalid("VarArgs function 'case_when' needs at least 2 arguments but only 1 passed")
+    if len(values) not in (len(conds), len(conds) + 1) or not conds:
+        raise ArrowInvalid("case_when: number of struct fields must be equal to or one less than count of remaining arguments "
+                           f"({len(values)}), got: {len(conds)}")
+    values = _typed_operands("case_when", values, "values")
+    t = _one_type("case_when", values, "value")
+    if not _IF_ELSE_VALUE(t):
+        names = ", ".join([f"struct<{', '.join(['bool'] * len(conds))}>"] + [x.type.name for x in values])
+        raise ArrowNotImplementedError(f"Function 'case_when' has no kernel matching input types ({names})")
+    if len(conds) > _lib.CASE_WHEN_MAX_CONDS:
+        raise ArrowNotImplementedError(f"arrow_amd: case_when with {len(conds)} conds on device-resident arrays: the device kernel "
+                                       f"takes up to {_lib.CASE_WHEN_MAX_CONDS}")
+    n = conds[0].length
+    if any(isinstance(a, Array) and a.length != n for a in conds + values):
+        raise ArrowInvalid("Array arguments must all be the same length")
+    dev = conds[0].device
+    lib, stream = _lib_and_stream(dev)
+    width = 0 if t == bool_ else t.byte_width
+    keep = []
+    cspans = [c.span() for c in conds]
+    ctable = (C.POINTER(_lib.ArxSpan) * len(conds))(*[C.pointer(sp) for sp in cspans])
+    vtable = _operand_table(values, t, keep)
+    null_scalars = [isinstance(a, Scalar) and not a.is_valid for a in values]
+    nulls = len(values) == len(conds) or any(null_scalars) or any(isinstance(a, Array) and a.may_have_nulls() for a in values)
+    out = alloc(bitmap_nbytes(n) if width == 0 else n * width, dev)
+    valid = alloc(bitmap_nbytes(n), dev) if nulls else None
+    with tracing.span("arx_case_when"):
+        check(lib.arx_case_when(width, ctable, len(conds), vtable, len(values), n, out.data_ptr(), _ptr_or_none(valid), stream))
+    if not nulls:
+        return Array(t, n, [None, out], 0, 0)
+    res = Array(t, n, [valid, out], kUnknownNullCount, 0)
+    if all(null_scalars):
+        res._null_count = n
+    else:
+        res.set_lazy_null_count(_lazy_null_count(valid, n))
+    return res
+
+
+# --------------------------------------------------------------------------- min_element_wise / max_element_wise
+# MinMaxFunctor / ScalarMinMax (compute/kernels/scalar_compare.cc): csrc/element_wise.hip.  One type for every operand (the
+# reference's DispatchBest casts; the mirror casts nothing).
+_ELEMENT_WISE_OPS = {"min_element_wise": _lib.ELEMENT_WISE_MIN, "max_element_wise": _lib.ELEMENT_WISE_MAX}
+
+
+def _ELEMENT_WISE_VALUE(t: DataType) -> bool:
+    from .array import is_temporal
+
+    return t.name in _NUM_TYPE_ID or is_temporal(t)
+
+
+def _exec_min_max_element_wise(name: str):
+    def run(args, options):
+        t = _one_type(name, args, "operand")
+        if len(args) > _lib.ELEMENT_WISE_MAX_OPERANDS:
+            raise ArrowNotImplementedError(f"arrow_amd: {name} with {len(args)} operands on device-resident arrays: the device kernel "
+                                           f"takes up to {_lib.ELEMENT_WISE_MAX_OPERANDS}")
+        arrays = [a for a in args if isinstance(a, Array)]
+        if not arrays:
+            raise ArrowNotImplementedError(f"arrow_amd: {name} of scalars only; pass an arrow_amd.Array as one of the operands")
+        n = arrays[0].length
+        if any(a.length != n for a in arrays):
+            raise ArrowInvalid("Array arguments must all be the same length")
+        skip_nulls = bool(options.skip_nulls)
+        dev = arrays[0].device
+        lib, stream = _lib_and_stream(dev)
+        keep = []
+        table = _operand_table(args, t, keep)
+        nullable = [a.may_have_nulls() if isinstance(a, Array) else not a.is_valid for a in args]
+        nulls = all(nullable) if skip_nulls else any(nullable)
+        out = alloc(n * t.byte_width, dev)
+        valid = alloc(bitmap_nbytes(n), dev) if nulls else None
+        with tracing.span("arx_min_max_element_wise"):
+            check(lib.arx_min_max_element_wise(_num_type_id(t), _ELEMENT_WISE_OPS[name], 1 if skip_nulls else 0, table, len(args), n,
+                                               out.data_ptr(), _ptr_or_none(valid), stream))
+        if not nulls:
+            return Array(t, n, [None, out], 0, 0)
+        res = Array(t, n, [valid, out], kUnknownNullCount, 0)
+        null_scalar = any(isinstance(a, Scalar) and not a.is_valid for a in args)
+        if null_scalar and not skip_nulls:
+            res._null_count = n
+        else:
+            res.set_lazy_null_count(_lazy_null_count(valid, n))
+        return res
+    return run
+
+
+def _make_element_wise(name: str):
+    def fn(*args, skip_nulls: bool = True) -> Array:
+        if not args:
+            return call_function(name, [], ElementWiseAggregateOptions(skip_nulls))
+        return call_function(name, _typed_operands(name, args, "operands"), ElementWiseAggregateOptions(skip_nulls))
+    fn.__name__ = fn.__qualname__ = name
+    fn.__doc__ = (f"compute::{'Min' if name.startswith('min') else 'Max'}ElementWise (scalar_compare.cc): the row-wise "
+                  f"{'smallest' if name.startswith('min') else 'largest'} of 1 .. 32 operands of one numeric type (or a temporal one that "
+                  "is physically int32 / int64).  Each operand: an Array, an arrow_amd.Scalar, a Python number (it takes the other "
+                  "operands' type) or None (a null scalar).  skip_nulls: null only where every operand is null; otherwise where any is.  "
+                  "The fold is the reference's (scalars first, then the arrays left to right; a NaN loses to every number).  The "
+                  "result stays on the device and has no validity buffer when it cannot hold a null.")
+    return fn
+
+
+for _name in _ELEMENT_WISE_OPS:
+    globals()[_name] = _make_element_wise(_name)
+del _name
 
 
 # --------------------------------------------------------------------------- date / time fields

@@ -108,6 +108,8 @@ namespace {
 #include "plugin/string_replace.inc"
 #include "plugin/string_join.inc"
 #include "plugin/unary_arith.inc"
+#include "plugin/case_when.inc"
+#include "plugin/element_wise.inc"
 #include "plugin/grouper_chain.inc"
 #include "plugin/acero_node.inc"
 #include "plugin/acero_node_general.inc"

@@ -92,6 +92,8 @@ CounterTable string_compare_counters();
 CounterTable string_replace_counters();
 CounterTable string_join_counters();
 CounterTable unary_arith_counters();
+CounterTable case_when_counters();
+CounterTable element_wise_counters();
 
 #define ARX_HIP(call)                                          \
   do {                                                         \

@@ -43,7 +43,7 @@ static const CounterRow* find_counter(const char* name) {
   const CounterTable tables[] = {groupby_counters(), groupby_lines_counters(), sort_counters(), set_lookup_counters(),
                                  match_substring_counters(), if_else_counters(), temporal_counters(), string_slice_counters(),
                                  string_trim_counters(), string_compare_counters(), string_replace_counters(), string_join_counters(),
-                                 unary_arith_counters()};
+                                 unary_arith_counters(), case_when_counters(), element_wise_counters()};
   if (name != nullptr) {
     for (const CounterTable& t : tables) {
       for (size_t i = 0; i < t.n; ++i) {

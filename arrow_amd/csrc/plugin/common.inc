@@ -95,7 +95,7 @@ enum Fn { kFnFilter = 0, kFnTake, kFnGreater, kFnSort, kFnCast, kFnHashSum, kFnA
           kFnBinaryLength, kFnUtf8Length, kFnBinarySlice, kFnUtf8SliceCodeunits, kFnAsciiTrimWhitespace, kFnAsciiLtrimWhitespace,
           kFnAsciiRtrimWhitespace, kFnUtf8TrimWhitespace, kFnUtf8LtrimWhitespace, kFnUtf8RtrimWhitespace, kFnAsciiTrim, kFnAsciiLtrim,
           kFnAsciiRtrim, kFnUtf8Trim, kFnUtf8Ltrim, kFnUtf8Rtrim, kFnCompareString, kFnReplaceSubstring, kFnUnaryArith, kFnRound,
-          kFnBinaryJoinElementWise,
+          kFnBinaryJoinElementWise, kFnCaseWhen, kFnMinElementWise, kFnMaxElementWise,
           kNumFn };
 const char* const kFnNames[kNumFn] = {"array_filter", "array_take", "greater", "array_sort_indices",
                                       "cast", "hash_sum", "add", "boolean", "compare", "parquet", "reduce", "order_by",
@@ -107,7 +107,7 @@ const char* const kFnNames[kNumFn] = {"array_filter", "array_take", "greater", "
                                       "ascii_rtrim_whitespace", "utf8_trim_whitespace", "utf8_ltrim_whitespace",
                                       "utf8_rtrim_whitespace", "ascii_trim", "ascii_ltrim", "ascii_rtrim", "utf8_trim", "utf8_ltrim",
                                       "utf8_rtrim", "compare_string", "replace_substring", "unary_arith", "round",
-                                      "binary_join_element_wise"};
+                                      "binary_join_element_wise", "case_when", "min_element_wise", "max_element_wise"};
 std::atomic<int64_t> g_fn_gpu[kNumFn];
 std::atomic<int64_t> g_fn_stock[kNumFn];
 void CountGpu(Fn f) {

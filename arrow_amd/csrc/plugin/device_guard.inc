@@ -226,7 +226,7 @@ Status GuardAggregateKernels(cp::Function* fn, int num_stock) {
 // the functions whose kernel lists the shim appends to — and the string-search siblings of match_substring, the
 // temporal siblings of year .. nanosecond and the nearest string siblings of the lengths, slices and trims (replace_slice,
 // reverse, case mapping, padding, swapcase / capitalize / title, replace_substring_regex beside replace_substring,
-// binary_join and binary_repeat beside binary_join_element_wise, and round_binary beside round), to
+// binary_join and binary_repeat beside binary_join_element_wise, round_binary beside round, and choose beside case_when), to
 // which it adds nothing (every kernel of theirs is the reference's, so every one gets a guard): a device-resident input is
 // refused by name instead of being read by a CPU kernel
 const char* const kGuardedFunctions[] = {
@@ -245,7 +245,8 @@ const char* const kGuardedFunctions[] = {
     "ascii_lpad", "ascii_rpad", "ascii_center", "utf8_lpad", "utf8_rpad", "utf8_center", "ascii_swapcase", "ascii_capitalize",
     "ascii_title", "utf8_swapcase", "utf8_capitalize", "utf8_title", "replace_substring", "replace_substring_regex",
     "binary_join_element_wise", "binary_join", "binary_repeat",
-    "negate", "negate_checked", "abs", "abs_checked", "sign", "floor", "ceil", "trunc", "round", "round_to_multiple", "round_binary"};
+    "negate", "negate_checked", "abs", "abs_checked", "sign", "floor", "ceil", "trunc", "round", "round_to_multiple", "round_binary",
+    "case_when", "min_element_wise", "max_element_wise", "choose"};
 
 // before the shim registers anything: how many kernels of each guarded function are the reference's
 arrow::Result<std::vector<int>> CountStockKernels(cp::FunctionRegistry* reg) {

@@ -347,6 +347,10 @@ Status RegisterAll() {
   ARROW_RETURN_NOT_OK(RegisterStringReplace(reg));   // replace_substring of utf8 / binary and their large forms (plugin/string_replace.inc)
   ARROW_RETURN_NOT_OK(RegisterStringJoin(reg));   // binary_join_element_wise of utf8 / binary and their large forms (plugin/string_join.inc)
   ARROW_RETURN_NOT_OK(RegisterUnaryArith(reg));   // negate .. trunc, round, round_to_multiple of the numeric types (plugin/unary_arith.inc)
+  ARROW_RETURN_NOT_OK(RegisterCaseWhen(reg));   // case_when(cond struct, values ..., [else]) of boolean and the fixed-width types (plugin/case_when.inc)
+  // min_element_wise / max_element_wise of the numeric types and the physically-integer temporal ones (plugin/element_wise.inc)
+  ARROW_RETURN_NOT_OK(RegisterElementWise(reg, "min_element_wise", ARX_ELEMENT_WISE_MIN, kFnMinElementWise));
+  ARROW_RETURN_NOT_OK(RegisterElementWise(reg, "max_element_wise", ARX_ELEMENT_WISE_MAX, kFnMaxElementWise));
   // the reference's kernels of the functions extended above refuse device-resident arrays instead of reading them
   ARROW_RETURN_NOT_OK(InstallDeviceGuards(reg, stock_kernel_counts));
   ARROW_RETURN_NOT_OK(RefreshMinMaxKernels(reg));   // (the guards re-added kernels: pointers into min_max's list moved)

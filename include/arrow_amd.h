@@ -1576,6 +1576,67 @@ int arx_compare_binary(int op, const ArxBinarySpan* left, const ArxBinarySpan* r
  * counts the launches of the kernel of widths 8 and 16, of widths 1, 2 and 4 (8 / width rows a lane) and of booleans. */
 int arx_if_else(int byte_width, const ArxSpan* cond, const ArxSpan* left, const void* left_scalar, const ArxSpan* right,
                 const void* right_scalar, int64_t length, void* out_data, void* out_validity, void* stream);
+/* One operand of arx_case_when / arx_min_max_element_wise, in one of three forms: an array (span != NULL, scalar == NULL),
+ * a valid scalar (span == NULL, scalar -> the type's host bytes; booleans: one byte 0 / 1), a null scalar (both NULL). */
+typedef struct ArxOperand {
+  const ArxSpan* span;
+  const void* scalar;
+} ArxOperand;
+/* case_when(conds, v_0 .. v_{k-1} [, else]) of ONE fixed-width type or boolean (CaseWhenFunctor, compute/kernels/scalar_if_else.cc;
+ * csrc/case_when.hip): row i takes values[j][i] of the first j whose cond is true AND valid (a null cond is false); a row
+ * no cond takes comes from values[num_conds] (the else, present when num_values == num_conds + 1) or is null.  The
+ * result's validity is that of the chosen operand.  On the 64-row words: remaining = ~0; take_j = remaining & c_j & cv_j;
+ * remaining &= ~take_j; the else takes what remains; valid = OR_j (take_j & vv_j).
+ * byte_width 1 / 2 / 4 / 8 / 16, or 0 for booleans (bitmaps).  conds: num_conds pointers to boolean arrays (data = bitmap,
+ * offset = bit offset), each with its own offset and validity; 1 .. ARX_CASE_WHEN_MAX_CONDS of them, more is ARX_INVALID
+ * naming the cap.  values: num_values = num_conds or num_conds + 1 operands in any mix of the three forms, each array with
+ * its own offset.  The output starts at offset 0; a null result slot is written as zero.
+ * out_validity: ceil(length / 64) whole words; it may be NULL exactly when an else is present and no value has a bitmap
+ * (validity != NULL and null_count != 0) or is a null scalar — the result then has no nulls and no bitmap is written.
+ * Nothing is written past length * byte_width data bytes (booleans: past the last data word) or past the last validity
+ * word.  A value whose row is not taken is not loaded, and the walk over the conds of a wave's rows stops once every row
+ * has its value: later cond bitmaps are not read either.
+ * ARX_INVALID, with nothing launched or written, for a byte_width or a count outside the above, a negative length, NULL
+ * conds / values / a NULL cond, a span whose length is not `length`, an operand given as an array and as a scalar, and for
+ * length > 0 a NULL out_data or data buffer and a NULL out_validity that is required; length == 0 succeeds, launches
+ * nothing and writes nothing.  Asynchronous; no read-back.  arx_get_counter("case_when_launches" /
+ * "case_when_packed_launches" / "case_when_bool_launches") counts the launches of the kernel of widths 8 and 16, of
+ * widths 1, 2 and 4 (8 / width rows a lane) and of booleans. */
+enum {
+  ARX_CASE_WHEN_MAX_CONDS = 16
+};
+int arx_case_when(int byte_width, const ArxSpan* const* conds, int num_conds, const ArxOperand* values, int num_values,
+                  int64_t length, void* out_data, void* out_validity, void* stream);
+/* min_element_wise / max_element_wise of 1 .. ARX_ELEMENT_WISE_MAX_OPERANDS operands of ONE numeric type (MinMaxFunctor
+ * / ScalarMinMax, compute/kernels/scalar_compare.cc; csrc/element_wise.hip).  num_type: ARX_NUM_*; op: ARX_ELEMENT_WISE_MIN
+ * / _MAX.  skip_nulls != 0: a row is null only where every operand is null; skip_nulls == 0: where any operand is null (a
+ * null scalar then makes every row null).  The fold is the reference's and shows on floats: the accumulator starts as the
+ * fold of all scalar operands (made on the host, in argument order, the first valid one starting it) or, without a valid
+ * scalar, as the default quiet NaN (integers: the type's largest value for min, smallest for max); then every valid value
+ * of the arrays, left to right, goes through the step.  The step is std::fmin / std::fmax as the reference's build resolves
+ * them, and the two float widths differ (pyarrow 25.0.0, x86-64).  float64, min: isnan(acc) ? x : isnan(x) ? acc :
+ * (x < acc ? x : acc) — a tie of +0.0 and -0.0 keeps the accumulator, of two NaNs the right one's bits come out.  float32,
+ * min: isnan(x) ? acc : isnan(acc) ? x : (acc < x ? acc : x) — a tie takes the right operand, of two NaNs the accumulator
+ * stays, so a float32 NaN that comes from arrays alone is the default NaN (max: > for <).  A NaN loses to every number.
+ * Integers compare as their own signed or unsigned type.  One operand is a copy (float32: but for its NaNs' bits).  Every
+ * array carries its own offset;
+ * the output starts at offset 0; a null result slot is written as zero.
+ * out_validity: ceil(length / 64) whole words; it may be NULL exactly when the result cannot hold a null: no operand has
+ * a bitmap (validity != NULL and null_count != 0) or is a null scalar — under skip_nulls it is enough that one operand
+ * can never be null.  Nothing is written past length * width data bytes or past the last validity word.
+ * ARX_INVALID, with nothing launched or written, for a num_type, op or count outside the above, a negative length, NULL
+ * operands, a span whose length is not `length`, an operand given as an array and as a scalar, and for length > 0 a NULL
+ * out_data or data buffer and a NULL out_validity that is required; length == 0 succeeds, launches nothing and writes
+ * nothing.  Asynchronous; no read-back.  arx_get_counter("element_wise_launches") counts the launches. */
+enum {
+  ARX_ELEMENT_WISE_MIN = 0,
+  ARX_ELEMENT_WISE_MAX = 1
+};
+enum {
+  ARX_ELEMENT_WISE_MAX_OPERANDS = 32
+};
+int arx_min_max_element_wise(int num_type, int op, int skip_nulls, const ArxOperand* operands, int num_operands, int64_t length,
+                             void* out_data, void* out_validity, void* stream);
 /* Date / time field extraction (Year .. ISOWeek, Hour .. Nanosecond, compute/kernels/scalar_temporal_unary.cc; csrc/temporal.hip):
  * out[i] = the `component` of values[i] as int64, in the proleptic Gregorian calendar without a time zone; every division
  * is a floor division, so instants before the epoch are right (timestamp[ms] -1: year 1969, hour 23, millisecond 999).
